@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- MinHash signatures/sec on MI355X (BASELINE.json metric), one process per GPU.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          # N > 1: spawns its own N ranks
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]   # N > 1: spawns its own N ranks
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
            --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -11,12 +11,19 @@ is one pass of the hot path (``mhx_minhash_bulk_dev``) over the whole resident c
 the [N, K] uint64 signature matrix in HBM.  Inputs are in HBM before the timed region starts.
 Weak scaling: every rank hashes its own 1M-set shard; there is no collective in the data path, so
 ``value`` is the compute-only rate.  At N > 1 the config-3 exchange step -- one RCCL all-gather of the
-uint32 shards over xGMI -- is measured on its own after the timed region and reported under
+uint32 shards over xGMI -- is measured on its own after the timed region (``--full``) and reported under
 ``allgather`` (ms, bytes, ranks RCCL itself counts); ``--allgather`` puts it inside every step.
 
 No PyTorch anywhere: ranks find each other over datasketch_amd.rendezvous (TCP; MASTER_ADDR /
 MASTER_PORT of the launcher, or the port the self-spawning parent picked), which carries the
 barriers, the max-over-ranks reduction and the 128-byte RCCL id.
+
+A plain run sets up, warms up, times the K steps, writes ``--dump-outputs`` and prints the line: nothing else.
+``--dump-outputs DIR`` writes what the last timed step computed as ``DIR/signatures.npy`` (float64, exact: every
+signature value is below 2**32): a fixed, seeded sample of 32768 rows of rank 0's [N, K] matrix, so that two builds can
+be compared output for output.  Everything below that the line can also carry -- the parity gates, the counted launch,
+the CPU baseline, the PCIe-inclusive rates, the extra configs and, at N > 1, the exchange probes -- runs only with
+``--full``.
 
 Prints ONE JSON line on rank 0.  ``roofline.achieved`` = algorithmic bytes (8*T + 8*K per
 signature) / average launch duration measured with HIP events on the
@@ -78,6 +85,9 @@ def parse_args(argv=None):
     ap.add_argument("--u32", action="store_true", help="compact variant: uint32 tokens in, uint32 signatures out")
     ap.add_argument("--share-devices", action="store_true", help="testing only: let several ranks use one GPU (no RCCL then)")
     ap.add_argument("--opt", action="append", default=[], metavar="KEY=VALUE", help="libmhx tuning knob (mhx_ctx_set_option), e.g. blocks_per_cu=4")
+    ap.add_argument("--full", action="store_true", help="after the headline figure, run every check and every other measurement (parity gates, "
+                    "counted launch, CPU baseline, PCIe-inclusive rates, configs 3/4/5, the N > 1 exchange probes); off: the headline alone")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="write a fixed sample of the last timed step's signatures to DIR/signatures.npy (float64)")
     return ap.parse_args(argv)
 
 
@@ -160,7 +170,7 @@ def main():
     tok_dtype, out_dtype, out_np, tok_bytes, out_bytes = ((_native.MHX_U32, _native.MHX_U32, np.uint32, 4, 4) if args.u32
                                                           else (_native.MHX_U64, _native.MHX_U64, np.uint64, 8, 8))
     tok_np = np.uint32 if args.u32 else np.uint64
-    check = max(0, min(args.check_rows, n))
+    check = max(0, min(args.check_rows, n)) if args.full else 0
     check_rows_idx = np.unique(np.linspace(0, n - 1, check).astype(np.int64)) if check else np.empty(0, dtype=np.int64)
     if world == 1:
         tokens = rng.randint(0, 2**32, size=(n, t), dtype=np.uint64)
@@ -237,14 +247,19 @@ def main():
     kernel_ms = float(np.mean(launch_ms))
     kernel_ms_ranks = [float(np.frombuffer(p, dtype=np.float64)[0]) for p in group.allgather(np.float64(kernel_ms).tobytes())]
 
-    # ---- one counted launch outside the timed region: how often the sieve's proof failed
-    ctx.counters(True)
-    ctx.minhash_bulk_dev(perms, d_tok.ptr, tok_dtype, None, t, n, n * t, None, 0, d_out.ptr, out_dtype)
-    counters = ctx.counters(False)
-    try:  # which sets left the first launch's proof (the launches' own hand-over bytes: mhx_ctx_minhash_flags)
-        flags = ctx.minhash_flags(n)
-    except ValueError:  # (a shape that keeps none: one huge set split over waves)
-        flags = None
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, d_out.download((n, k), out_np), k)
+
+    counters, flags = {}, None
+    if args.full:
+        # ---- one counted launch outside the timed region: how often the sieve's proof failed
+        ctx.counters(True)
+        ctx.minhash_bulk_dev(perms, d_tok.ptr, tok_dtype, None, t, n, n * t, None, 0, d_out.ptr, out_dtype)
+        counters = ctx.counters(False)
+        try:  # which sets left the first launch's proof (the launches' own hand-over bytes: mhx_ctx_minhash_flags)
+            flags = ctx.minhash_flags(n)
+        except ValueError:  # (a shape that keeps none: one huge set split over waves)
+            flags = None
 
     # ---- parity: rows spread over the whole matrix against the package's numpy path (gpu_mode="disable": the
     # reference's arithmetic, minhash.py:293-297), bit-exact or fail.  The oracle itself is only used in the
@@ -254,7 +269,7 @@ def main():
     a, b = perms
     sig_head = None
     all_rows = None
-    if check or (args.cpu_sample > 0 and rank == 0 and world == 1):
+    if check or (args.full and args.cpu_sample > 0 and rank == 0 and world == 1):
         sig = d_out.download((n, k), out_np)
         if check:
             want = MinHash.bulk_signatures(check_tokens, num_perm=k, seed=args.seed, hashfunc=prehashed, gpu_mode="disable")
@@ -311,8 +326,8 @@ def main():
             "rendezvous": "datasketch_amd.rendezvous (TCP, no PyTorch)",
             "parity_rows_checked": int(all_rows["rows"]) if all_rows else int(check),
             **({"parity_all_rows": all_rows} if all_rows else {}),
-            "sets_redone_by_full_evaluation": counters["sieve_sets_redone"],
-            "sets_redone_by_exact_fold": counters["exact_sets_redone"],
+            **({"sets_redone_by_full_evaluation": counters["sieve_sets_redone"],
+                "sets_redone_by_exact_fold": counters["exact_sets_redone"]} if counters else {}),
         },
         "per_rank": {
             "ms_per_step": [1e3 * x / args.steps for x in per_rank],
@@ -342,7 +357,7 @@ def main():
     }
 
     # ---- N > 1: the exchange step of config 3 on its own (uint32 shards, RCCL over xGMI)
-    if world > 1 and not args.no_allgather_probe:
+    if world > 1 and args.full and not args.no_allgather_probe:
         # RCCL blocks inside the library when a peer is missing or a topology is refused on one rank only; the compute
         # numbers above are complete, so a probe that does not come back in time is reported as such instead of
         # hanging the job: the watchdog prints the line (rank 0) and leaves
@@ -395,7 +410,7 @@ def main():
             os._exit(0)  # (a non-zero status would make the launcher kill rank 0 before its watchdog prints the line; the traceback is on stderr)
         dog.cancel()
 
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         if not args.no_e2e:
             # host numpy in -> host numpy out through mhx_minhash_bulk (pageable memory): the first call
             # also allocates device scratch and first-touches a fresh result array; the second reuses both
@@ -438,6 +453,19 @@ def main():
         sys.stdout.flush()
         sys.stderr.flush()
         os._exit(0)
+
+
+DUMP_ROWS = 32768  # x K=128 float64 = 32 MB at the default shape
+
+
+def dump_outputs(path, sig, k):
+    """DIR/signatures.npy: the rows of a fixed, seeded sample (the same rows for the same --sets) of the [N, K] signature
+    matrix as float64 -- exact, since every signature value is below 2**32 -- capped at 64 MB."""
+    n = sig.shape[0]
+    m = min(n, DUMP_ROWS, (64 << 20) // (8 * k))
+    rows = np.sort(np.random.RandomState(0).choice(n, m, replace=False)) if m < n else np.arange(n)
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "signatures.npy"), sig[rows].astype(np.float64))
 
 
 def measured_traffic(n, t, k, args, field="traffic_bytes_per_launch"):

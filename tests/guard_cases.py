@@ -2,7 +2,8 @@
 script in a process of its own by tests/test_guard_pages.py -- a kernel that over-reads kills the process).
 
     python tests/guard_cases.py <align>            all cases; prints "GUARD OK <n> cases" and exits 0
-    python tests/guard_cases.py <align> overread   the positive control: a launch told to read past its buffer must die
+    python tests/guard_cases.py <align> layout     the positive control, by query alone: the byte past every buffer's edge
+                                                   is mapped by nothing; prints "GUARD LAYOUT OK <n> buffers"
 
 <align> > 0: the LAST byte of every buffer (size rounded up to <align> bytes) is the last byte of its mapping;
 <align> < 0: the FIRST byte is the first byte of its mapping.  mhx_debug_guard_alloc (include/mhx.h) does the mapping
@@ -302,16 +303,34 @@ def inverse_format_cases(ctx):
                 _done(f"lean round trip n={n} K={k} big={big} code={code}")
 
 
-def overread(ctx):
-    """The positive control: mhx_minhash_merge_dev told that its inputs are one granule longer than they are."""
-    granule, _ = _native.guard_alloc(int(sys.argv[1]))
-    count = 1 << 10
-    d_x, d_y = _dev(ctx, np.zeros(count, dtype=np.uint64)), _dev(ctx, np.zeros(count, dtype=np.uint64))
-    d_o = ctx.alloc(8 * count + 2 * granule)
-    print("launching an over-read of", granule, "bytes", flush=True)
-    check(ctx.lib.mhx_minhash_merge_dev(ctx.handle, _p(d_x), _p(d_y), count + granule // 8, _p(d_o)))
-    ctx.synchronize()
-    print("OVERREAD SURVIVED", flush=True)
+def layout(ctx, align, granule):
+    """The positive control without touching an unmapped byte: for buffers around the granule size, hipMemGetAddressRange --
+    a host-side lookup in the runtime's table of mappings -- finds the buffer's first and last byte inside one mapping whose
+    edge is the buffer's edge (its end for align > 0, its start for align < 0), and finds no mapping at the byte just past
+    that edge: a kernel that read or wrote there would fault instead of touching a neighbour."""
+    hip = ctypes.CDLL(next(line.split()[-1] for line in open("/proc/self/maps") if "libamdhip64.so" in line))
+    hip.hipMemGetAddressRange.argtypes = [ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(ctypes.c_size_t), ctypes.c_void_p]
+
+    def mapping(addr):
+        base, size = ctypes.c_void_p(), ctypes.c_size_t()
+        rc = hip.hipMemGetAddressRange(ctypes.byref(base), ctypes.byref(size), ctypes.c_void_p(addr))
+        return (base.value, size.value) if rc == 0 else None
+
+    a = abs(align)
+    for nbytes in (1, 8, 100, granule - 1, granule, granule + 8, 3 * granule - 24):
+        buf = ctx.alloc(nbytes)
+        want = (nbytes + a - 1) // a * a
+        first, last = buf.ptr, buf.ptr + want - 1
+        m = mapping(first)
+        assert m is not None and mapping(last) == m, f"{nbytes} bytes: the buffer is not inside one mapping ({m}, {mapping(last)})"
+        base, size = m
+        if align > 0:
+            assert base + size == last + 1, f"{nbytes} bytes: the mapping ends {base + size - last - 1} bytes past the buffer"
+            assert mapping(last + 1) is None, f"{nbytes} bytes: the byte past the buffer is mapped"
+        else:
+            assert base == first, f"{nbytes} bytes: the mapping starts {first - base} bytes before the buffer"
+            assert mapping(first - 1) is None, f"{nbytes} bytes: the byte before the buffer is mapped"
+        _done(f"layout {nbytes} bytes")
 
 
 def main():
@@ -319,8 +338,9 @@ def main():
     granule, _ = _native.guard_alloc(align)  # before the first allocation of the process
     assert granule > 0
     ctx = _native.context()
-    if len(sys.argv) > 2 and sys.argv[2] == "overread":
-        overread(ctx)
+    if len(sys.argv) > 2 and sys.argv[2] == "layout":
+        layout(ctx, align, granule)
+        print(f"GUARD LAYOUT OK {CASES} buffers (align {align}, granule {granule} bytes)", flush=True)
         return
     minhash_cases(ctx)
     sha1_cases(ctx)

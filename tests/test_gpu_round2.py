@@ -578,7 +578,7 @@ def test_bench_spawns_two_ranks_on_one_gpu_for_the_plumbing():
     rendezvous, barrier, time, reduce MAX, and rank 0 prints the line.  Two ranks share this box's one GPU
     (--share-devices), so the numbers mean nothing and RCCL is left out (next test)."""
     p = _bench(["--gpus", "2", "--steps", "3", "--warmup", "1", "--sets", "20000", "--check-rows", "256", "--share-devices",
-                "--no-allgather-probe"])
+                "--no-allgather-probe", "--full"])
     assert p.returncode == 0, p.stdout + p.stderr
     line = json.loads(p.stdout.strip().splitlines()[-1])
     assert line["n_gpus"] == 2 and line["config"]["launcher"] == "self-spawned ranks"
@@ -604,7 +604,7 @@ def test_bench_under_torch_distributed_run_environment():
                    MASTER_PORT=str(port), TORCHELASTIC_RUN_ID="none")
         env.pop("MHX_RDZV_ADDR", None)
         procs.append(subprocess.Popen([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--sets",
-                                       "10000", "--check-rows", "64", "--share-devices", "--no-allgather-probe"],
+                                       "10000", "--check-rows", "64", "--share-devices", "--no-allgather-probe", "--full"],
                                       env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
     outs = [p.communicate(timeout=600) for p in procs]
     assert all(p.returncode == 0 for p in procs), outs

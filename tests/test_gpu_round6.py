@@ -3,7 +3,7 @@
 * the headline corpus compared with the C oracle on EVERY row (1M x 256, K = 128), the sets the launches' own hand-over flags name
   (mhx_ctx_minhash_flags: the rare-event paths) checked by id, and the same on corpora full of repeated tokens where nearly all
   sets take the tie-tolerant proof (ref: minhash.py:293-297);
-* configs 3 / 5 with the index partitioned by band: worlds of 2 and 8 on one GPU, equal and unequal shards, the by-band exchange of
+* configs 3 / 5 with the index partitioned by band: worlds of 2 and 4 on one GPU, equal and unequal shards, the by-band exchange of
   band digests (mhx_comm_exchange_dev) over the host-staged transport and over the RCCL binding with the stand-in library -- every
   rank's sorted bands byte-identical to the single-process result and the oracle (ref: lsh.py:199,326-347; b_bit_minhash.py:78-101);
 * ragged (heavy-tailed) shards through dist.bulk_signatures_sharded (ref: minhash.py:491-522);
@@ -161,7 +161,8 @@ def _check_by_band(recs, arrays, n, t, k, bands, r, world, scheme, transport_nam
     return want, dig
 
 
-@pytest.mark.parametrize("world,scheme", [(2, "equal"), (2, "unequal"), (8, "equal"), (8, "unequal")])
+# (4 ranks at most, here and below: with the test process, five hold the GPU at once -- what a shared GPU node admits)
+@pytest.mark.parametrize("world,scheme", [(2, "equal"), (2, "unequal"), (4, "equal"), (4, "unequal")])
 def test_band_partitioned_index_with_ranks_sharing_one_gpu(ctx, tmp_path, world, scheme):
     """`world` processes, one GPU, host-staged transport: every rank hashes its shard, packs b = 1 blocks and band-major digests of
     ITS rows in one read, sends every peer that peer's bands and buckets its own bands over all rows.  No signature matrix is ever
@@ -183,11 +184,11 @@ def test_band_partitioned_index_with_ranks_sharing_one_gpu(ctx, tmp_path, world,
         assert arrays[q]["sorted_digests"].tobytes() == sd[lo:hi].tobytes() and arrays[q]["sorted_rows"].tobytes() == sr[lo:hi].tobytes()
 
 
-@pytest.mark.parametrize("world,scheme", [(2, "unequal"), (8, "equal"), (8, "unequal")])
+@pytest.mark.parametrize("world,scheme", [(2, "unequal"), (4, "equal"), (4, "unequal")])
 def test_by_band_exchange_through_the_rccl_binding_with_the_stand_in_library(ctx, tmp_path, fake_rccl, world, scheme):
     """mhx_comm_exchange_dev (one group of ncclSend / ncclRecv, a run per (peer, band), self-runs as device copies) executed for
     real from `world` processes against tests/fake_rccl.c: pins OUR marshalling -- peers, offsets, sizes, order -- with worlds of 2
-    and 8; RCCL and xGMI are not in the picture."""
+    and 4; RCCL and xGMI are not in the picture."""
     n, t, k, bands, r = 24_000, 64, 128, 16, 8
     recs, arrays = _run_ranks(["byband", n, t, k, bands, r, scheme], world, str(tmp_path / f"bbr_{world}_{scheme}"), transport="rccl",
                               extra_env={"MHX_RCCL_LIBRARY": fake_rccl})
@@ -195,9 +196,9 @@ def test_by_band_exchange_through_the_rccl_binding_with_the_stand_in_library(ctx
 
 
 def test_by_band_exchange_with_more_ranks_than_bands_and_a_non_fused_shape(ctx, tmp_path):
-    """bands = 6 over 8 ranks: two ranks own no band (they still send); K = 96, r = 16 is a shape the fused kernel declines."""
-    n, t, k, bands, r = 12_000, 48, 96, 6, 16
-    world = 8
+    """bands = 2 over 4 ranks: two ranks own no band (they still send); K = 96, r = 16 is a shape the fused kernel declines."""
+    n, t, k, bands, r = 12_000, 48, 96, 2, 16
+    world = 4
     recs, arrays = _run_ranks(["byband", n, t, k, bands, r, "unequal"], world, str(tmp_path / "bb_few_bands"))
     import rank_c3
 
@@ -242,7 +243,7 @@ def test_exchange_with_one_rank_through_rccl(ctx):
 
 
 # ------------------------------------------------------------------ ragged shards
-@pytest.mark.parametrize("world,transport", [(8, "host"), (2, "rccl")])
+@pytest.mark.parametrize("world,transport", [(4, "host"), (2, "rccl")])
 def test_ragged_shards_balanced_by_tokens_equal_the_single_process_csr_call(ctx, tmp_path, fake_rccl, world, transport):
     """A heavy-tailed corpus (Pareto lengths, empty sets, a few 64-bit tokens) cut by token count, every rank hashing its CSR shard
     (ref: minhash.py:491-522 takes arbitrary iterables), all-gathered in unequal shards: equal to the single-process CSR call and to

@@ -1,8 +1,13 @@
 """Consumer-side bulk helpers (datasketch_amd/lsh_bulk.py): band keys, digests, bulk LSH insert,
-candidate pairs, batched Jaccard.  The CPU tests use the numpy fallbacks; where the reference
-repository is mounted (/root/reference, build container only) its own MinHashLSH is the oracle."""
+candidate pairs, batched Jaccard.  The CPU tests use the numpy fallbacks.  Where the reference's own
+MinHashLSH is the oracle, its index -- built key by key from the same seeded inputs -- is pinned in
+tests/golden/lsh_index.json (oracle/gen_golden_lsh.py): its (b, r), a sha256 of its dictionaries and of
+its answers to the probes."""
+import collections
+import hashlib
+import json
 import os
-import sys
+import pickle
 
 import numpy as np
 import pytest
@@ -10,7 +15,48 @@ import pytest
 from datasketch_amd import MinHash, prehashed
 from datasketch_amd import lsh_bulk as LB
 
-REFERENCE = "/root/reference"
+GOLDEN_LSH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "lsh_index.json")
+
+
+def lsh_golden(case):
+    with open(GOLDEN_LSH) as f:
+        return json.load(f)[case]
+
+
+class _DictStore:
+    """The reference's in-memory storage as insert_bulk / query_bulk recognise it: a defaultdict behind ``_dict``."""
+
+    def __init__(self, factory):
+        self._dict = collections.defaultdict(factory)
+
+    def __contains__(self, key):
+        return key in self._dict
+
+
+class _DictIndex:
+    """The attributes of a reference MinHashLSH over the in-memory storage, with the (b, r) the reference chose."""
+
+    def __init__(self, h, b, r, prepickle=False, hashfunc=None):
+        self.h, self.b, self.r, self.prepickle, self.hashfunc = h, b, r, prepickle, hashfunc
+        self.keys = _DictStore(list)
+        self.hashtables = [_DictStore(set) for _ in range(b)]
+
+
+def _sha(obj):
+    return hashlib.sha256(repr(obj).encode()).hexdigest()
+
+
+def index_digest(lsh):
+    """sha256 of an index's dictionaries in a canonical order (keys unpickled, so the pickle protocol does not enter)."""
+    key = pickle.loads if lsh.prepickle else (lambda k: k)
+    keys = sorted((repr(key(k)), [repr(h) for h in hs]) for k, hs in lsh.keys._dict.items())
+    tables = [sorted((repr(h), sorted(repr(key(k)) for k in members)) for h, members in t._dict.items()) for t in lsh.hashtables]
+    return _sha((keys, tables))
+
+
+def results_digest(results):
+    """sha256 of query answers, each taken as the set it is."""
+    return _sha([sorted(map(repr, res)) for res in results])
 
 
 def _signatures(n=300, t=40, k=64, seed=0, dup_every=7):
@@ -62,36 +108,24 @@ def test_candidate_pairs_and_jaccard_pairs():
     assert LB.jaccard_pairs(sig, np.empty((0, 2), np.int64), gpu_mode="disable").size == 0
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference repository not mounted")
 @pytest.mark.parametrize("prepickle,use_hashfunc", [(False, False), (True, False), (False, True)])
 def test_insert_bulk_leaves_the_reference_index_in_the_same_state(prepickle, use_hashfunc):
-    sys.path.insert(0, REFERENCE)
-    try:
-        import datasketch as ref
-    finally:
-        sys.path.remove(REFERENCE)
+    """insert_bulk leaves the dictionaries the reference's per-key MinHashLSH.insert leaves (threshold 0.5, num_perm 64)."""
+    gold = lsh_golden(f"insert-{int(prepickle)}{int(use_hashfunc)}")
     sig = _signatures(n=200, k=64)
     keys = [f"doc-{i}" for i in range(sig.shape[0])]
-    kw = dict(threshold=0.5, num_perm=64, prepickle=prepickle)
-    if use_hashfunc:
-        kw["hashfunc"] = LB.fnv1a_64
-    one, bulk = ref.MinHashLSH(**kw), ref.MinHashLSH(**kw)
-    for key, row in zip(keys, sig):
-        one.insert(key, ref.MinHash(num_perm=64, seed=1, hashvalues=row))
+    bulk = _DictIndex(64, gold["b"], gold["r"], prepickle, LB.fnv1a_64 if use_hashfunc else None)
     LB.insert_bulk(bulk, keys, sig, gpu_mode="disable")
-    assert one.b == bulk.b and one.r == bulk.r
-    for t1, t2 in zip(one.hashtables, bulk.hashtables):
-        assert dict(t1._dict) == dict(t2._dict)
-    assert dict(one.keys._dict) == dict(bulk.keys._dict)
-    probe = ref.MinHash(num_perm=64, seed=1, hashvalues=sig[0])
-    assert sorted(one.query(probe)) == sorted(bulk.query(probe)) and len(one.query(probe)) > 1
+    assert index_digest(bulk) == gold["index_sha256"]
+    got = LB.query_bulk(bulk, sig[:1], gpu_mode="disable")
+    assert results_digest(got) == gold["query_sha256"] and len(got[0]) > 1
     with pytest.raises(ValueError):
         LB.insert_bulk(bulk, keys[:1], sig[:1], gpu_mode="disable")  # duplicate key
     with pytest.raises(ValueError):
         LB.insert_bulk(bulk, ["x"], sig[:1, :32], gpu_mode="disable")  # wrong length
     if use_hashfunc:  # the digests are what the index stores
-        dig = LB.band_digests(sig, one.b, one.r, gpu_mode="disable")
-        assert set(one.hashtables[0]._dict) == set(int(x) for x in dig[:, 0])
+        dig = LB.band_digests(sig, bulk.b, bulk.r, gpu_mode="disable")
+        assert set(bulk.hashtables[0]._dict) == set(int(x) for x in dig[:, 0])
 
 
 def _weighted_signatures(n=60, dim=32, s=16):
@@ -127,42 +161,21 @@ def test_weighted_signatures_go_through_the_same_helpers():
         LB.band_keys(sig, 5, 4, gpu_mode="disable")  # 5 * 4 > 16 samples
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference repository not mounted")
 def test_insert_bulk_of_weighted_signatures_matches_the_reference_index():
-    sys.path.insert(0, REFERENCE)
-    try:
-        import datasketch as ref
-    finally:
-        sys.path.remove(REFERENCE)
+    """Weighted signatures under integer keys: the reference's index of ref.WeightedMinHash(3, hashvalues) per key."""
+    gold = lsh_golden("weighted")
     wm, sig = _weighted_signatures()
-    one, bulk = ref.MinHashLSH(threshold=0.5, num_perm=16), ref.MinHashLSH(threshold=0.5, num_perm=16)
-    for i, w in enumerate(wm):
-        one.insert(i, ref.WeightedMinHash(3, w.hashvalues))
+    bulk = _DictIndex(16, gold["b"], gold["r"])
     LB.insert_bulk(bulk, list(range(len(wm))), sig, gpu_mode="disable")
-    for t1, t2 in zip(one.hashtables, bulk.hashtables):
-        assert dict(t1._dict) == dict(t2._dict)
-    probe = ref.WeightedMinHash(3, wm[3].hashvalues)
-    assert sorted(one.query(probe)) == sorted(bulk.query(probe)) and 7 in bulk.query(probe)
+    assert index_digest(bulk) == gold["index_sha256"]
+    got = LB.query_bulk(bulk, sig[3:4], gpu_mode="disable")
+    assert results_digest(got) == gold["query_sha256"] and 7 in got[0]
     with pytest.raises(ValueError):
         LB.insert_bulk(bulk, ["x"], sig[:1, :8], gpu_mode="disable")  # wrong sample count
 
 
-def _reference():
-    sys.path.insert(0, REFERENCE)
-    try:
-        import datasketch as ref
-    finally:
-        sys.path.remove(REFERENCE)
-    return ref
-
-
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference repository not mounted")
-@pytest.mark.parametrize("prepickle", [True, False])
-def test_insert_bulk_in_batches_and_query_bulk_equal_the_per_key_calls(prepickle):
-    """Two bulk batches (the second onto a non-empty index, with band keys shared inside the batch and with the
-    first batch) leave every dictionary as the per-key loop does; query_bulk == [lsh.query(m) for m in probes]
-    for 1000 probes (ref: datasketch/lsh.py:326-347, 370-431; storage.py:210-259)."""
-    ref = _reference()
+def batch_inputs(prepickle):
+    """Signatures (whole rows again across the batch boundary, a big bucket, a near duplicate), keys and 1000 probes."""
     rng = np.random.RandomState(3)
     n, k = 1500, 64
     sig = rng.randint(0, 2**32, (n, k)).astype(np.uint64)
@@ -170,23 +183,26 @@ def test_insert_bulk_in_batches_and_query_bulk_equal_the_per_key_calls(prepickle
     sig[900:940, :32] = sig[5, :32]     # a big bucket in the first bands
     sig[1200, 16:] = sig[1100, 16:]     # a near duplicate inside the second batch
     keys = [("doc", i) for i in range(n)] if prepickle else [b"doc-%d" % i for i in range(n)]
-    kw = dict(threshold=0.6, num_perm=k, prepickle=prepickle)
-    one, bulk = ref.MinHashLSH(**kw), ref.MinHashLSH(**kw)
-    for key, row in zip(keys, sig):
-        one.insert(key, ref.MinHash(num_perm=k, seed=1, hashvalues=row))
-    LB.insert_bulk(bulk, keys[:800], sig[:800], gpu_mode="disable")
-    LB.insert_bulk(bulk, keys[800:], sig[800:], gpu_mode="disable")
-    assert dict(one.keys._dict) == dict(bulk.keys._dict)
-    for t1, t2 in zip(one.hashtables, bulk.hashtables):
-        assert dict(t1._dict) == dict(t2._dict)
     probes = sig[rng.randint(0, n, 1000)].copy()
     probes[::3, rng.randint(0, k, 20)] = 7          # perturbed probes: some bands still match
     probes[1::50] = rng.randint(0, 2**32, (20, k))  # probes that match nothing
+    return sig, keys, probes
+
+
+@pytest.mark.parametrize("prepickle", [True, False])
+def test_insert_bulk_in_batches_and_query_bulk_equal_the_per_key_calls(prepickle):
+    """Two bulk batches (the second onto a non-empty index, with band keys shared inside the batch and with the
+    first batch) leave every dictionary as the reference's per-key loop does; query_bulk == [lsh.query(m) for m in
+    probes] for 1000 probes (ref: datasketch/lsh.py:326-347, 370-431; storage.py:210-259)."""
+    gold = lsh_golden(f"batches-{int(prepickle)}")
+    sig, keys, probes = batch_inputs(prepickle)
+    bulk = _DictIndex(64, gold["b"], gold["r"], prepickle)
+    LB.insert_bulk(bulk, keys[:800], sig[:800], gpu_mode="disable")
+    LB.insert_bulk(bulk, keys[800:], sig[800:], gpu_mode="disable")
+    assert index_digest(bulk) == gold["index_sha256"]
     got = LB.query_bulk(bulk, probes, gpu_mode="disable")
     assert len(got) == 1000
-    for row, res in zip(probes, got):
-        want = one.query(ref.MinHash(num_perm=k, seed=1, hashvalues=row))
-        assert sorted(map(repr, res)) == sorted(map(repr, want))
+    assert results_digest(got) == gold["query_sha256"]
     assert any(len(r) > 30 for r in got) and any(len(r) == 0 for r in got)
     with pytest.raises(ValueError):
         LB.query_bulk(bulk, probes[:, :32], gpu_mode="disable")

@@ -7,7 +7,7 @@ TAG="${1:-run}"
 OUT="gpurun_out/pmc_extra_${TAG}"
 mkdir -p "${OUT}"
 export TMPDIR=/tmp
-CMD=(python bench.py --steps 2 --warmup 1 --cpu-sample 0 --no-e2e --check-rows 0)
+CMD=(python bench.py --full --steps 2 --warmup 1 --cpu-sample 0 --no-e2e --check-rows 0)
 pass() { local name="$1"; shift
   timeout 120 rocprofv3 --pmc "$@" -d "${OUT}/${name}" -o pmc -- "${CMD[@]}" > "${OUT}/${name}.log" 2>&1
   echo "${name} rc=$?"; }

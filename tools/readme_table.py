@@ -33,7 +33,7 @@ def main():
     c4v = e["c4"].get("kernel_device_log") or e["c4"]["kernel"]
     c4l = e["c4"].get("kernel_logs_in") or e["c4"]["kernel"]
     lines = [BEGIN,
-             f"Measured on one MI355X (`profiles/r06_bench.json`: `python bench.py`, every launch timed with HIP events behind a clock warm-up; "
+             f"Measured on one MI355X (`profiles/r06_bench.json`: `python bench.py --full`, every launch timed with HIP events behind a clock warm-up; "
              f"`frac` = algorithmic bytes / time against 8 TB/s).  Headline: **{d['value']:.3g} signatures/s** ({d['ms_per_step']:.2f} ms per 10^6 sets, "
              
              + (f"traffic {r['traffic'] / r['algorithmic_bytes_per_launch']:.2f}x algorithmic, VALU issue {r['valu_issue_frac']:.2f}" if r.get("traffic") else

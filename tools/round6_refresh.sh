@@ -19,13 +19,13 @@ if [[ ${rc} -ne 0 ]]; then echo "smoke failed: not profiling on this box"; tail 
 timeout 400 bash tools/traffic.sh "${TAG}" > "${OUT}/traffic.log" 2>&1; echo "traffic rc=$?"
 python tools/traffic_summary.py "gpurun_out/traffic_${TAG}" > "${OUT}/traffic.json" 2> "${OUT}/traffic.err" || true
 [[ -s "${OUT}/traffic.json" ]] && cp "${OUT}/traffic.json" profiles/r06_traffic_minhash_bulk.json
-timeout 900 python bench.py > "${OUT}/bench.log" 2>&1; echo "bench rc=$?"; tail -1 "${OUT}/bench.log" > "${OUT}/bench.json"; cut -c1-260 "${OUT}/bench.json"
+timeout 900 python bench.py --full > "${OUT}/bench.log" 2>&1; echo "bench rc=$?"; tail -1 "${OUT}/bench.log" > "${OUT}/bench.json"; cut -c1-260 "${OUT}/bench.json"
 PROFILE_ONLY=trace timeout 600 bash tools/profile.sh "${TAG}" > "${OUT}/profile.log" 2>&1; echo "profile rc=$?"
 python tools/rocpd_summary.py "gpurun_out/prof_${TAG}" > "${OUT}/rocprof_summary.txt" 2>&1 || true
 timeout 400 bash tools/r5_passes.sh "${TAG}" > "${OUT}/r5_passes.log" 2>&1; echo "r5_passes rc=$?"
 timeout 300 bash tools/pmc_weighted.sh "${TAG}_sparse001" --csr --density 0.01 --rows 100000 --variants "path=0" > "${OUT}/pmc_sparse001.log" 2>&1; echo "pmc sparse rc=$?"
 for n in 2 8; do
-  timeout 900 python bench.py --gpus ${n} --share-devices --allgather-transport host --check-rows 1024 > "${OUT}/bench_n${n}_host.log" 2>&1; echo "bench n=${n} rc=$?"
+  timeout 900 python bench.py --gpus ${n} --share-devices --allgather-transport host --check-rows 1024 --full > "${OUT}/bench_n${n}_host.log" 2>&1; echo "bench n=${n} rc=$?"
   grep "^{" "${OUT}/bench_n${n}_host.log" | tail -1 > "${OUT}/bench_n${n}_host.json"; cut -c1-200 "${OUT}/bench_n${n}_host.json"
 done
 timeout 400 python tools/bench_extra.py > "${OUT}/bench_extra.jsonl" 2> "${OUT}/bench_extra.err"; echo "bench_extra rc=$?"
