@@ -109,6 +109,14 @@ _PROTOTYPES = {
     "mhx_lean_deserialize": [_vp, _vp, _i64, _i32, _int, _vp, _vp],
     "mhx_bbit_unpack_dev": [_vp, _vp, _i64, _i32, _i32, _vp],
     "mhx_bbit_unpack": [_vp, _vp, _i64, _i32, _i32, _vp],
+    "mhx_jaccard_matrix_dev": [_vp, _vp, _i64, _vp, _i64, _int, _i32, _vp, _i64],
+    "mhx_jaccard_matrix": [_vp, _vp, _i64, _vp, _i64, _i32, _vp],
+    "mhx_jaccard_threshold_pairs_dev": [_vp, _vp, _i64, _vp, _i64, _int, _i32, _i32, _vp, _vp, _i64, ctypes.POINTER(_i64)],
+    "mhx_jaccard_threshold_pairs": [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _i64, ctypes.POINTER(_i64)],
+    "mhx_bbit_jaccard_matrix_dev": [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64],
+    "mhx_bbit_jaccard_matrix": [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp],
+    "mhx_bbit_jaccard_threshold_pairs_dev": [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _i64, ctypes.POINTER(_i64)],
+    "mhx_bbit_jaccard_threshold_pairs": [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _i64, ctypes.POINTER(_i64)],
     "mhx_comm_unique_id": [_vp],
     "mhx_comm_create": [_vp, _vp, _int, _int, ctypes.POINTER(_vp)],
     "mhx_comm_destroy": [_vp],
@@ -814,6 +822,97 @@ class Context:
         out = np.empty((blocks.shape[0], int(num_perm)), dtype=np.uint32)
         check(self.lib.mhx_bbit_unpack(self.handle, _ptr(blocks), blocks.shape[0], int(num_perm), int(b), _ptr(out)))
         return out
+
+    # -- all-pairs Jaccard: A [n_a, K] against B [n_b, K] (b=None: A against itself) -------------
+    def _all_pairs_args(self, a: np.ndarray, b: Optional[np.ndarray], width: int):
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        if a.ndim != 2 or a.shape[1] != width:
+            raise ValueError("rows must be [n, %d]" % width)
+        if b is not None:
+            b = np.ascontiguousarray(b, dtype=np.uint64)
+            if b.ndim != 2 or b.shape[1] != width:
+                raise ValueError("rows must be [n, %d]" % width)
+        return a, b
+
+    def _bbit_width(self, num_perm: int, b: int) -> int:
+        nb = _i32(0)
+        check(self.lib.mhx_bbit_num_blocks(int(num_perm), int(b), ctypes.byref(nb)))
+        return nb.value
+
+    def _threshold_retry(self, call, capacity: int):
+        cap = int(capacity)
+        while True:
+            pairs = np.empty((cap, 2), dtype=np.int64)
+            counts = np.empty(cap, dtype=np.int32)
+            found = _i64(0)
+            check(call(_ptr(pairs), _ptr(counts), cap, ctypes.byref(found)))
+            if found.value <= cap:
+                return pairs[: found.value], counts[: found.value]
+            cap = int(found.value)
+
+    def jaccard_matrix(self, a: np.ndarray, b: Optional[np.ndarray] = None) -> np.ndarray:
+        """int32 [n_a, n_b]: equal positions of every row of A against every row of B (mhx_jaccard_matrix)."""
+        a, b = self._all_pairs_args(a, b, np.shape(a)[-1])
+        n_b = a.shape[0] if b is None else b.shape[0]
+        out = np.empty((a.shape[0], n_b), dtype=np.int32)
+        check(self.lib.mhx_jaccard_matrix(self.handle, _ptr(a), a.shape[0], _ptr(b), n_b, a.shape[1], _ptr(out)))
+        return out
+
+    def jaccard_threshold_pairs(self, a: np.ndarray, b: Optional[np.ndarray], min_count: int, capacity: Optional[int] = None):
+        """(pairs int64 [P, 2] ascending, counts int32 [P]): every pair whose equal positions reach ``min_count``
+        (mhx_jaccard_threshold_pairs); b=None: pairs i < j of A.  ``capacity`` is the first guess of P."""
+        a, b = self._all_pairs_args(a, b, np.shape(a)[-1])
+        n_b = a.shape[0] if b is None else b.shape[0]
+        k = a.shape[1]
+        return self._threshold_retry(lambda p, c, cap, found: self.lib.mhx_jaccard_threshold_pairs(
+            self.handle, _ptr(a), a.shape[0], _ptr(b), n_b, k, int(min_count), p, c, cap, found),
+            capacity if capacity is not None else max(a.shape[0], 1 << 12))
+
+    def bbit_jaccard_matrix(self, a: np.ndarray, b: Optional[np.ndarray], num_perm: int, bits: int) -> np.ndarray:
+        """int32 [n_a, n_b]: agreeing b-bit positions of every packed row of A against every packed row of B
+        (mhx_bbit_jaccard_matrix)."""
+        a, b = self._all_pairs_args(a, b, self._bbit_width(num_perm, bits))
+        n_b = a.shape[0] if b is None else b.shape[0]
+        out = np.empty((a.shape[0], n_b), dtype=np.int32)
+        check(self.lib.mhx_bbit_jaccard_matrix(self.handle, _ptr(a), a.shape[0], _ptr(b), n_b, int(num_perm), int(bits), _ptr(out)))
+        return out
+
+    def bbit_jaccard_threshold_pairs(self, a: np.ndarray, b: Optional[np.ndarray], num_perm: int, bits: int, min_count: int,
+                                     capacity: Optional[int] = None):
+        """(pairs, counts) of the packed rows whose agreeing b-bit positions reach ``min_count``
+        (mhx_bbit_jaccard_threshold_pairs); b=None: pairs i < j of A."""
+        a, b = self._all_pairs_args(a, b, self._bbit_width(num_perm, bits))
+        n_b = a.shape[0] if b is None else b.shape[0]
+        return self._threshold_retry(lambda p, c, cap, found: self.lib.mhx_bbit_jaccard_threshold_pairs(
+            self.handle, _ptr(a), a.shape[0], _ptr(b), n_b, int(num_perm), int(bits), int(min_count), p, c, cap, found),
+            capacity if capacity is not None else max(a.shape[0], 1 << 12))
+
+    def jaccard_matrix_dev(self, d_a: int, n_a: int, d_b: Optional[int], n_b: int, sig_dtype: int, num_perm: int, d_counts: int,
+                           ldc: int) -> None:
+        check(self.lib.mhx_jaccard_matrix_dev(self.handle, _vp(d_a), int(n_a), _vp(d_b), int(n_b), int(sig_dtype), int(num_perm),
+                                              _vp(d_counts), int(ldc)))
+
+    def jaccard_threshold_pairs_dev(self, d_a: int, n_a: int, d_b: Optional[int], n_b: int, sig_dtype: int, num_perm: int,
+                                    min_count: int, d_pairs: Optional[int], d_counts: Optional[int], capacity: int) -> int:
+        """Total number of qualifying pairs (written to d_pairs / d_counts when it is <= capacity)."""
+        found = _i64(0)
+        check(self.lib.mhx_jaccard_threshold_pairs_dev(self.handle, _vp(d_a), int(n_a), _vp(d_b), int(n_b), int(sig_dtype),
+                                                       int(num_perm), int(min_count), _vp(d_pairs), _vp(d_counts), int(capacity),
+                                                       ctypes.byref(found)))
+        return int(found.value)
+
+    def bbit_jaccard_matrix_dev(self, d_a: int, n_a: int, d_b: Optional[int], n_b: int, num_perm: int, bits: int, d_counts: int,
+                                ldc: int) -> None:
+        check(self.lib.mhx_bbit_jaccard_matrix_dev(self.handle, _vp(d_a), int(n_a), _vp(d_b), int(n_b), int(num_perm), int(bits),
+                                                   _vp(d_counts), int(ldc)))
+
+    def bbit_jaccard_threshold_pairs_dev(self, d_a: int, n_a: int, d_b: Optional[int], n_b: int, num_perm: int, bits: int,
+                                         min_count: int, d_pairs: Optional[int], d_counts: Optional[int], capacity: int) -> int:
+        found = _i64(0)
+        check(self.lib.mhx_bbit_jaccard_threshold_pairs_dev(self.handle, _vp(d_a), int(n_a), _vp(d_b), int(n_b), int(num_perm),
+                                                            int(bits), int(min_count), _vp(d_pairs), _vp(d_counts), int(capacity),
+                                                            ctypes.byref(found)))
+        return int(found.value)
 
     # -- device-resident entry points (pointers are DeviceBuffer.ptr + byte offsets) -----------
     def minhash_bulk_dev(self, permutations, d_hv: int, hv_dtype: int, d_offsets: Optional[int], fixed_len: int, n_sets: int,

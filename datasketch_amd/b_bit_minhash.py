@@ -3,7 +3,9 @@
 Keeps the lowest ``b`` bits of every hash value.  The packed state is the reference's:
 header ``<qBdi`` (seed, b, r, num_perm) followed by uint64 blocks holding ``64/slot`` values
 each, value ``j`` of a block at bit ``(n-1-j)*slot``.  :func:`pack_matrix` packs a whole
-signature matrix on the device in the same bit order.
+signature matrix on the device in the same bit order; :func:`jaccard_pairs`, :func:`jaccard_matrix` and
+:func:`similar_pairs` estimate ``bBitMinHash.jaccard`` on packed rows for a list of pairs, for all pairs, and for
+the pairs at or above a threshold.
 """
 from __future__ import annotations
 
@@ -188,3 +190,94 @@ def jaccard_pairs(blocks: np.ndarray, pairs, num_perm: int, b: int, r: float = 0
     a = proto._calc_a(float(r), b)
     c1, c2 = proto._calc_c(a, a, float(r), float(r))
     return (same.astype(np.float64) / float(num_perm) - c1) / (1 - c2)
+
+
+def _packed_rows(blocks, nb: int, name: str) -> np.ndarray:
+    blocks = np.ascontiguousarray(blocks, dtype=np.uint64)
+    if blocks.ndim != 2 or blocks.shape[1] != nb:
+        raise ValueError("%s must be [n, %d] packed blocks" % (name, nb))
+    return blocks
+
+
+def _all_pairs_setup(blocks_a, blocks_b, num_perm: int, b: int, r: float, r_b):
+    """Checked inputs and the reference's estimate of every count 0..num_perm (ref: b_bit_minhash.py:53-72): row i of A
+    holds a bBitMinHash of ``r``, row j of B one of ``r_b`` (default ``r``)."""
+    b = int(b)
+    if b > 32 or b < 0:
+        raise ValueError("b must be an integer in [0, 32]")
+    r = float(r)
+    r_b = r if r_b is None else float(r_b)
+    if r > 1.0 or r_b > 1.0:
+        raise ValueError("r must be a float in [0.0, 1.0]")
+    num_perm = int(num_perm)
+    if num_perm <= 0:
+        raise ValueError("num_perm must be positive")
+    slot = _slot_size(b)
+    nb = -(-num_perm // (64 // slot))
+    a = _packed_rows(blocks_a, nb, "blocks_a")
+    bb = None if blocks_b is None else _packed_rows(blocks_b, nb, "blocks_b")
+    proto = object.__new__(bBitMinHash)
+    c1, c2 = proto._calc_c(proto._calc_a(r, b), proto._calc_a(r_b, b), r, r_b)
+    denom = 1 - c2
+    if denom == 0:
+        raise ZeroDivisionError("float division by zero")
+    return a, bb, b, num_perm, slot, c1, denom
+
+
+def _estimate(counts: np.ndarray, num_perm: int, c1: float, denom: float) -> np.ndarray:
+    return (counts.astype(np.float64) / float(num_perm) - c1) / denom
+
+
+def _agree_blocks(a: np.ndarray, bb, slot: int, num_perm: int):
+    """numpy fallback: agreeing b-bit positions, block of A rows by block (the rows unpacked once)."""
+    from datasketch_amd.lsh_bulk import _equal_counts_blocks
+
+    va = _unpack_rows(a, slot, num_perm)
+    vb = None if bb is None else _unpack_rows(bb, slot, num_perm)
+    return _equal_counts_blocks(va, vb)
+
+
+def _use_device(gpu_mode: str) -> bool:
+    return gpu_mode != "disable" and (gpu_mode == "always" or _native.gpu_detected())
+
+
+def jaccard_matrix(blocks_a, blocks_b, num_perm: int, b: int, r: float = 0.0, r_b=None, gpu_mode: str = "always") -> np.ndarray:
+    """``bBitMinHash.jaccard`` (ref: datasketch/b_bit_minhash.py:53-72) of every packed row of ``blocks_a`` against every
+    packed row of ``blocks_b`` (:func:`pack_matrix` output; ``None``: ``blocks_a`` against itself): float64 ``[M, N]``
+    estimates ``(agreeing / num_perm - C1) / (1 - C2)``, C1 and C2 from ``r`` (the rows of A) and ``r_b`` (the rows of B,
+    default ``r``) as the reference takes them from each side's own ``r``."""
+    a, bb, b, num_perm, slot, c1, denom = _all_pairs_setup(blocks_a, blocks_b, num_perm, b, r, r_b)
+    n_b = a.shape[0] if bb is None else bb.shape[0]
+    if a.shape[0] == 0 or n_b == 0:
+        return np.zeros((a.shape[0], n_b), dtype=np.float64)
+    if _use_device(gpu_mode):
+        counts = _native.context().bbit_jaccard_matrix(a, bb, num_perm, b)
+    else:
+        from datasketch_amd.lsh_bulk import _matrix_from_blocks
+
+        counts = _matrix_from_blocks(_agree_blocks(a, bb, slot, num_perm), a.shape[0], n_b)
+    return _estimate(counts, num_perm, c1, denom)
+
+
+def similar_pairs(blocks_a, blocks_b, num_perm: int, b: int, threshold: float = 0.5, r: float = 0.0, r_b=None,
+                  gpu_mode: str = "always"):
+    """Every pair of packed rows whose ``bBitMinHash.jaccard`` estimate is ``>= threshold``: ``(pairs int64 [P, 2],
+    estimates float64 [P])``, ascending by ``(i, j)``; ``blocks_b=None``: the pairs ``i < j`` of ``blocks_a``.  The
+    threshold becomes the first count whose estimate -- the exact float formula, evaluated for every count 0..num_perm --
+    reaches it.  ``b = 1`` makes a cheap exhaustive prefilter whose survivors are then verified on full signatures."""
+    a, bb, b, num_perm, slot, c1, denom = _all_pairs_setup(blocks_a, blocks_b, num_perm, b, r, r_b)
+    n_b = a.shape[0] if bb is None else bb.shape[0]
+    empty = (np.empty((0, 2), dtype=np.int64), np.empty(0, dtype=np.float64))
+    if a.shape[0] == 0 or n_b == 0:
+        return empty
+    from datasketch_amd.lsh_bulk import _min_count, _pairs_from_blocks
+
+    est = _estimate(np.arange(num_perm + 1), num_perm, c1, denom)
+    c = _min_count(est, float(threshold))
+    if c > num_perm:
+        return empty
+    if _use_device(gpu_mode):
+        pairs, counts = _native.context().bbit_jaccard_threshold_pairs(a, bb, num_perm, b, c)
+    else:
+        pairs, counts = _pairs_from_blocks(_agree_blocks(a, bb, slot, num_perm), c, bb is None)
+    return pairs, _estimate(counts, num_perm, c1, denom)

@@ -1842,4 +1842,166 @@ int mhx_weighted_minhash_many_dense(mhx_wgen *gen, const float *x, int values_ar
     return MHX_OK;
 }
 
+// ---- all-pairs Jaccard (jaccard_kernels.hip) -------------------------------------------------
+// Shared argument checks.  b < 0: dense rows of sig_dtype, else b-bit blocks.
+static int check_all_pairs(int64_t n_a, int64_t n_b, int sig_dtype, int32_t k, int32_t b) {
+    MHX_REQUIRE(sig_dtype == MHX_U64 || sig_dtype == MHX_U32, "bad sig_dtype %d", sig_dtype);
+    MHX_REQUIRE(b < 0 || b <= 32, "b must be an integer in [0, 32]");
+    MHX_REQUIRE(k > 0, "num_perm must be positive");
+    MHX_REQUIRE(n_a >= 0 && n_b >= 0, "bad shape");
+    MHX_REQUIRE(n_a < ((int64_t)1 << 32) && n_b < ((int64_t)1 << 32), "more than 2^32-1 rows per call");
+    return MHX_OK;
+}
+
+static int all_pairs_matrix_dev(mhx_ctx *ctx, const void *d_a, int64_t n_a, const void *d_b, int64_t n_b, int sig_dtype,
+                                int32_t k, int32_t b, int32_t *d_counts, int64_t ldc) {
+    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
+    MHX_GUARD(ctx);
+    if (int rc = check_all_pairs(n_a, n_b, sig_dtype, k, b)) return rc;
+    if (!d_b) n_b = n_a;
+    MHX_REQUIRE(ldc >= n_b, "ldc must be >= n_b");
+    if (n_a == 0 || n_b == 0) return MHX_OK;
+    MHX_REQUIRE(d_a && d_counts, "NULL device pointer");
+    if (int rc = ctx->activate()) return rc;
+    return mhx::launch_jaccard_matrix(ctx, d_a, n_a, d_b ? d_b : d_a, n_b, sig_dtype, k, b, d_counts, ldc);
+}
+
+static int all_pairs_threshold_dev(mhx_ctx *ctx, const void *d_a, int64_t n_a, const void *d_b, int64_t n_b, int sig_dtype,
+                                   int32_t k, int32_t b, int32_t min_count, int64_t *d_pairs, int32_t *d_counts, int64_t capacity,
+                                   int64_t *n_pairs) {
+    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
+    MHX_GUARD(ctx);
+    MHX_REQUIRE(n_pairs, "n_pairs is NULL");
+    *n_pairs = 0;
+    if (int rc = check_all_pairs(n_a, n_b, sig_dtype, k, b)) return rc;
+    MHX_REQUIRE(capacity >= 0, "bad capacity");
+    if (!d_b) n_b = n_a;
+    if (n_a == 0 || n_b == 0 || min_count > k) return MHX_OK;
+    MHX_REQUIRE(d_a && ((d_pairs && d_counts) || capacity == 0), "NULL device pointer");
+    if (int rc = ctx->activate()) return rc;
+    return mhx::launch_jaccard_threshold(ctx, d_a, n_a, d_b, n_b, sig_dtype, k, b, min_count, d_pairs, d_counts, capacity,
+                                         n_pairs);
+}
+
+// host form of the matrix: B staged once (scratch[1]); A and the counts go through scratch[0] / scratch[2] in row blocks
+static int all_pairs_matrix_host(mhx_ctx *ctx, const uint64_t *a, int64_t n_a, const uint64_t *b, int64_t n_b, int32_t k, int32_t bb,
+                                 int32_t *counts) {
+    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
+    MHX_GUARD(ctx);
+    if (int rc = check_all_pairs(n_a, n_b, MHX_U64, k, bb)) return rc;
+    if (!b) {
+        b = a;
+        n_b = n_a;
+    }
+    if (n_a == 0 || n_b == 0) return MHX_OK;
+    MHX_REQUIRE(a && counts, "NULL host pointer");
+    int32_t words = k;  // uint64 per row
+    if (bb >= 0 && mhx_bbit_num_blocks(k, bb, &words)) return MHX_ERR_INVALID;
+    if (int rc = ctx->activate()) return rc;
+    const size_t row_bytes = sizeof(uint64_t) * (size_t)words;
+    const size_t out_row = sizeof(int32_t) * (size_t)n_b;
+    const int64_t block = std::max<int64_t>(1, std::min<int64_t>(n_a, (int64_t)((256ull << 20) / out_row)));
+    if (int rc = ctx->ensure_scratch(1, row_bytes * (size_t)n_b)) return rc;
+    if (int rc = ctx->ensure_scratch(0, row_bytes * (size_t)block)) return rc;
+    if (int rc = ctx->ensure_scratch(2, out_row * (size_t)block)) return rc;
+    MHX_HIP_CHECK(hipMemcpyAsync(ctx->scratch[1], b, row_bytes * (size_t)n_b, hipMemcpyHostToDevice, ctx->stream));
+    for (int64_t i0 = 0; i0 < n_a; i0 += block) {
+        const int64_t m = std::min<int64_t>(block, n_a - i0);
+        MHX_HIP_CHECK(hipMemcpyAsync(ctx->scratch[0], a + i0 * words, row_bytes * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
+        if (int rc = mhx::launch_jaccard_matrix(ctx, ctx->scratch[0], m, ctx->scratch[1], n_b, MHX_U64, k, bb,
+                                                (int32_t *)ctx->scratch[2], n_b))
+            return rc;
+        MHX_HIP_CHECK(hipMemcpyAsync(counts + i0 * n_b, ctx->scratch[2], out_row * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
+        MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    }
+    return MHX_OK;
+}
+
+// host form of the threshold query: A in scratch[0], B in scratch[1], pairs | counts in scratch[2]
+static int all_pairs_threshold_host(mhx_ctx *ctx, const uint64_t *a, int64_t n_a, const uint64_t *b, int64_t n_b, int32_t k,
+                                    int32_t bb, int32_t min_count, int64_t *pairs, int32_t *counts, int64_t capacity,
+                                    int64_t *n_pairs) {
+    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
+    MHX_GUARD(ctx);
+    MHX_REQUIRE(n_pairs, "n_pairs is NULL");
+    *n_pairs = 0;
+    if (int rc = check_all_pairs(n_a, n_b, MHX_U64, k, bb)) return rc;
+    MHX_REQUIRE(capacity >= 0, "bad capacity");
+    if (!b) n_b = n_a;
+    if (n_a == 0 || n_b == 0 || min_count > k) return MHX_OK;
+    MHX_REQUIRE(a && ((pairs && counts) || capacity == 0), "NULL host pointer");
+    int32_t words = k;
+    if (bb >= 0 && mhx_bbit_num_blocks(k, bb, &words)) return MHX_ERR_INVALID;
+    if (int rc = ctx->activate()) return rc;
+    const size_t row_bytes = sizeof(uint64_t) * (size_t)words;
+    const size_t pair_bytes = ((sizeof(int64_t) * 2 * (size_t)capacity) + 255) & ~(size_t)255;
+    if (int rc = ctx->ensure_scratch(0, row_bytes * (size_t)n_a)) return rc;
+    if (b) {
+        if (int rc = ctx->ensure_scratch(1, row_bytes * (size_t)n_b)) return rc;
+    }
+    if (int rc = ctx->ensure_scratch(2, pair_bytes + sizeof(int32_t) * (size_t)capacity + 256)) return rc;
+    MHX_HIP_CHECK(hipMemcpyAsync(ctx->scratch[0], a, row_bytes * (size_t)n_a, hipMemcpyHostToDevice, ctx->stream));
+    if (b) MHX_HIP_CHECK(hipMemcpyAsync(ctx->scratch[1], b, row_bytes * (size_t)n_b, hipMemcpyHostToDevice, ctx->stream));
+    int64_t *d_pairs = capacity ? (int64_t *)ctx->scratch[2] : nullptr;
+    int32_t *d_counts = capacity ? (int32_t *)((char *)ctx->scratch[2] + pair_bytes) : nullptr;
+    if (int rc = mhx::launch_jaccard_threshold(ctx, ctx->scratch[0], n_a, b ? ctx->scratch[1] : nullptr, n_b, MHX_U64, k, bb,
+                                               min_count, d_pairs, d_counts, capacity, n_pairs))
+        return rc;
+    if (*n_pairs > 0 && *n_pairs <= capacity) {
+        MHX_HIP_CHECK(hipMemcpyAsync(pairs, d_pairs, sizeof(int64_t) * 2 * (size_t)*n_pairs, hipMemcpyDeviceToHost, ctx->stream));
+        MHX_HIP_CHECK(hipMemcpyAsync(counts, d_counts, sizeof(int32_t) * (size_t)*n_pairs, hipMemcpyDeviceToHost, ctx->stream));
+    }
+    MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    return MHX_OK;
+}
+
+int mhx_jaccard_matrix_dev(mhx_ctx *ctx, const void *d_a, int64_t n_a, const void *d_b, int64_t n_b, int sig_dtype, int32_t num_perm,
+                           int32_t *d_counts, int64_t ldc) {
+    return all_pairs_matrix_dev(ctx, d_a, n_a, d_b, n_b, sig_dtype, num_perm, -1, d_counts, ldc);
+}
+
+int mhx_jaccard_matrix(mhx_ctx *ctx, const uint64_t *a, int64_t n_a, const uint64_t *b, int64_t n_b, int32_t num_perm,
+                       int32_t *counts) {
+    return all_pairs_matrix_host(ctx, a, n_a, b, n_b, num_perm, -1, counts);
+}
+
+int mhx_jaccard_threshold_pairs_dev(mhx_ctx *ctx, const void *d_a, int64_t n_a, const void *d_b, int64_t n_b, int sig_dtype,
+                                    int32_t num_perm, int32_t min_count, int64_t *d_pairs, int32_t *d_counts, int64_t capacity,
+                                    int64_t *n_pairs) {
+    return all_pairs_threshold_dev(ctx, d_a, n_a, d_b, n_b, sig_dtype, num_perm, -1, min_count, d_pairs, d_counts, capacity, n_pairs);
+}
+
+int mhx_jaccard_threshold_pairs(mhx_ctx *ctx, const uint64_t *a, int64_t n_a, const uint64_t *b, int64_t n_b, int32_t num_perm,
+                                int32_t min_count, int64_t *pairs, int32_t *counts, int64_t capacity, int64_t *n_pairs) {
+    return all_pairs_threshold_host(ctx, a, n_a, b, n_b, num_perm, -1, min_count, pairs, counts, capacity, n_pairs);
+}
+
+int mhx_bbit_jaccard_matrix_dev(mhx_ctx *ctx, const uint64_t *d_a, int64_t n_a, const uint64_t *d_b, int64_t n_b, int32_t num_perm,
+                                int32_t b, int32_t *d_counts, int64_t ldc) {
+    MHX_REQUIRE(b >= 0 && b <= 32, "b must be an integer in [0, 32]");
+    return all_pairs_matrix_dev(ctx, d_a, n_a, d_b, n_b, MHX_U64, num_perm, b, d_counts, ldc);
+}
+
+int mhx_bbit_jaccard_matrix(mhx_ctx *ctx, const uint64_t *a, int64_t n_a, const uint64_t *b_blocks, int64_t n_b, int32_t num_perm,
+                            int32_t b, int32_t *counts) {
+    MHX_REQUIRE(b >= 0 && b <= 32, "b must be an integer in [0, 32]");
+    return all_pairs_matrix_host(ctx, a, n_a, b_blocks, n_b, num_perm, b, counts);
+}
+
+int mhx_bbit_jaccard_threshold_pairs_dev(mhx_ctx *ctx, const uint64_t *d_a, int64_t n_a, const uint64_t *d_b, int64_t n_b,
+                                         int32_t num_perm, int32_t b, int32_t min_count, int64_t *d_pairs, int32_t *d_counts,
+                                         int64_t capacity, int64_t *n_pairs) {
+    if (n_pairs) *n_pairs = 0;
+    MHX_REQUIRE(b >= 0 && b <= 32, "b must be an integer in [0, 32]");
+    return all_pairs_threshold_dev(ctx, d_a, n_a, d_b, n_b, MHX_U64, num_perm, b, min_count, d_pairs, d_counts, capacity, n_pairs);
+}
+
+int mhx_bbit_jaccard_threshold_pairs(mhx_ctx *ctx, const uint64_t *a, int64_t n_a, const uint64_t *b_blocks, int64_t n_b,
+                                     int32_t num_perm, int32_t b, int32_t min_count, int64_t *pairs, int32_t *counts,
+                                     int64_t capacity, int64_t *n_pairs) {
+    if (n_pairs) *n_pairs = 0;
+    MHX_REQUIRE(b >= 0 && b <= 32, "b must be an integer in [0, 32]");
+    return all_pairs_threshold_host(ctx, a, n_a, b_blocks, n_b, num_perm, b, min_count, pairs, counts, capacity, n_pairs);
+}
+
 }  // extern "C"

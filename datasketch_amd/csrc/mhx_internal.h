@@ -198,6 +198,14 @@ int launch_lean_deserialize(mhx_ctx *ctx, const uint8_t *d_records, int64_t n, i
                             int64_t *d_seeds, unsigned int *d_bad);
 int launch_bbit_unpack(mhx_ctx *ctx, const uint64_t *d_blocks, int64_t n, int32_t k, int32_t b, uint32_t *d_out);
 
+// jaccard_kernels.hip: all-pairs counts.  b < 0: dense rows of sig_dtype; b in [0, 32]: b-bit blocks (mhx_bbit_pack*).
+int launch_jaccard_matrix(mhx_ctx *ctx, const void *d_a, int64_t n_a, const void *d_b, int64_t n_b, int sig_dtype, int32_t k,
+                          int32_t b, int32_t *d_counts, int64_t ldc);
+// d_b == nullptr: self-join of A (pairs i < j).  Blocking: *n_pairs comes back to the host.
+int launch_jaccard_threshold(mhx_ctx *ctx, const void *d_a, int64_t n_a, const void *d_b, int64_t n_b, int sig_dtype, int32_t k,
+                             int32_t b, int32_t min_count, int64_t *d_pairs, int32_t *d_counts, int64_t capacity,
+                             int64_t *n_pairs);
+
 int bbit_slot_size(int b);
 
 }  // namespace mhx

@@ -18,7 +18,10 @@ Python round trips:
   ascending order with their rows (device radix sort), and from that the pairs of rows that share at
   least one band (what ``query`` would find), without probing dictionaries -- on the device the
   whole chain (digests, sorts, run detection, pair emission, sort + unique) is one call;
-* :func:`jaccard_pairs` -- ``MinHash.jaccard`` for a list of pairs (ref: datasketch/minhash.py:299-324).
+* :func:`jaccard_pairs` -- ``MinHash.jaccard`` for a list of pairs (ref: datasketch/minhash.py:299-324);
+* :func:`jaccard_matrix` / :func:`similar_pairs` -- ``MinHash.jaccard`` of every row of A against every row of B
+  (or of A against itself), as a dense matrix or as the pairs at or above a threshold: exhaustive near-duplicate
+  search with no LSH banding in front, so no pair is missed by design.
 
 Every helper except :func:`jaccard_pairs` also takes a WeightedMinHash matrix ``[N, S, 2]`` int64
 (``WeightedMinHashGenerator.minhash_many_arrays``): its band keys are the reference's too
@@ -449,3 +452,110 @@ def weighted_jaccard_pairs(signatures, pairs) -> np.ndarray:
         raise ValueError("pair index out of range")
     same = np.all(sig[pairs[:, 0]] == sig[pairs[:, 1]], axis=2)
     return np.count_nonzero(same, axis=1).astype(np.float64) / float(sig.shape[1])
+
+
+# rows of A per numpy block of the all-pairs fallback: about 2^24 compared elements at a time
+_FALLBACK_ELEMS = 1 << 24
+
+
+def _hashvalue_rows(x, name: str):
+    """(uint64 [N, K] matrix, seed or None) of a signature matrix or a sequence of MinHash / LeanMinHash objects."""
+    if isinstance(x, np.ndarray) or (not hasattr(x, "__len__") or not len(x) or not hasattr(x[0], "hashvalues")):
+        sig = np.asarray(x)
+        if sig.ndim == 3:
+            raise ValueError("%s: all-pairs Jaccard takes [N, K] matrices, not WeightedMinHash [N, S, 2] ones" % name)
+        if sig.ndim != 2:
+            raise ValueError("%s must be an [N, K] matrix or a sequence of MinHash" % name)
+        return np.ascontiguousarray(sig, dtype=np.uint64), None
+    seed, k = x[0].seed, len(x[0].hashvalues)
+    for m in x:
+        if m.seed != seed:
+            raise ValueError("Cannot compute Jaccard given MinHash with different seeds")
+        if len(m.hashvalues) != k:
+            raise ValueError("Cannot compute Jaccard given MinHash with different numbers of permutation functions")
+    return np.ascontiguousarray(np.stack([np.asarray(m.hashvalues) for m in x]), dtype=np.uint64), seed
+
+
+def _all_pairs_inputs(a, b):
+    sa, seed_a = _hashvalue_rows(a, "a")
+    if b is None:
+        return sa, None
+    sb, seed_b = _hashvalue_rows(b, "b")
+    if seed_a is not None and seed_b is not None and seed_a != seed_b:
+        raise ValueError("Cannot compute Jaccard given MinHash with different seeds")
+    if sa.shape[1] != sb.shape[1]:
+        raise ValueError("Cannot compute Jaccard given MinHash with different numbers of permutation functions")
+    return sa, sb
+
+
+def _equal_counts_blocks(va: np.ndarray, vb: Optional[np.ndarray]):
+    """numpy all-pairs equal-position counts, block of A rows by block: yields (first row, int64 [rows, n_b])."""
+    other = va if vb is None else vb
+    n_b, k = other.shape
+    step = max(1, _FALLBACK_ELEMS // max(1, n_b * k))
+    for i0 in range(0, va.shape[0], step):
+        yield i0, np.count_nonzero(va[i0 : i0 + step, None, :] == other[None, :, :], axis=2)
+
+
+def _matrix_from_blocks(blocks, n_a: int, n_b: int) -> np.ndarray:
+    out = np.empty((n_a, n_b), dtype=np.int64)
+    for i0, c in blocks:
+        out[i0 : i0 + c.shape[0]] = c
+    return out
+
+
+def _pairs_from_blocks(blocks, min_count: int, self_join: bool):
+    found, counts = [], []
+    for i0, c in blocks:
+        keep = c >= min_count
+        if self_join:
+            keep &= np.arange(c.shape[1])[None, :] > (i0 + np.arange(c.shape[0]))[:, None]
+        ij = np.argwhere(keep)
+        counts.append(c[ij[:, 0], ij[:, 1]])
+        ij[:, 0] += i0
+        found.append(ij)
+    if not found:
+        return np.empty((0, 2), dtype=np.int64), np.empty(0, dtype=np.int64)
+    return np.concatenate(found).astype(np.int64), np.concatenate(counts)
+
+
+def _min_count(estimates: np.ndarray, threshold: float) -> int:
+    """The smallest count whose estimate (estimates[c], c = 0..K, monotone in c) is >= threshold; K + 1 when none is."""
+    hit = np.flatnonzero(estimates >= threshold)
+    return int(hit[0]) if hit.size else len(estimates)
+
+
+def jaccard_matrix(a, b=None, gpu_mode: str = "detect") -> np.ndarray:
+    """``MinHash.jaccard`` (ref: datasketch/minhash.py:299-324) of every row of ``a`` against every row of ``b``: float64
+    ``[M, N]``, equal positions / K.  ``a`` / ``b``: ``[N, K]`` uint32 or uint64 signature matrices or sequences of MinHash /
+    LeanMinHash (seeds and ``num_perm`` must agree, as the reference requires).  ``b=None``: ``a`` against itself."""
+    sa, sb = _all_pairs_inputs(a, b)
+    k = sa.shape[1]
+    n_b = sa.shape[0] if sb is None else sb.shape[0]
+    if sa.shape[0] == 0 or n_b == 0 or k == 0:
+        return np.zeros((sa.shape[0], n_b), dtype=np.float64)
+    if _use_gpu(gpu_mode):
+        counts = _native.context().jaccard_matrix(sa, sb)
+    else:
+        counts = _matrix_from_blocks(_equal_counts_blocks(sa, sb), sa.shape[0], n_b)
+    return counts.astype(np.float64) / float(k)
+
+
+def similar_pairs(a, b=None, threshold: float = 0.5, gpu_mode: str = "detect"):
+    """Every pair whose ``MinHash.jaccard`` is ``>= threshold``: ``(pairs int64 [P, 2], jaccard float64 [P])``, ascending by
+    ``(i, j)`` -- row ``i`` of ``a``, row ``j`` of ``b``; with ``b=None`` the pairs ``i < j`` of ``a``.  Exhaustive: every
+    pair is compared (on the device, all-pairs tiles; no LSH banding, so no false negatives).  The threshold becomes the
+    smallest count ``c`` with ``float(c) / float(K) >= threshold``, the reference's own float comparison."""
+    sa, sb = _all_pairs_inputs(a, b)
+    k = sa.shape[1]
+    n_b = sa.shape[0] if sb is None else sb.shape[0]
+    if sa.shape[0] == 0 or n_b == 0 or k == 0:
+        return np.empty((0, 2), dtype=np.int64), np.empty(0, dtype=np.float64)
+    c = _min_count(np.arange(k + 1, dtype=np.float64) / float(k), float(threshold))
+    if c > k:
+        return np.empty((0, 2), dtype=np.int64), np.empty(0, dtype=np.float64)
+    if _use_gpu(gpu_mode):
+        pairs, counts = _native.context().jaccard_threshold_pairs(sa, sb, c)
+    else:
+        pairs, counts = _pairs_from_blocks(_equal_counts_blocks(sa, sb), c, sb is None)
+    return pairs, counts.astype(np.float64) / float(k)

@@ -456,6 +456,44 @@ MHX_API int mhx_bbit_unpack_dev(mhx_ctx *ctx, const uint64_t *d_blocks, int64_t 
                                 uint32_t *d_out);
 MHX_API int mhx_bbit_unpack(mhx_ctx *ctx, const uint64_t *blocks, int64_t n_sigs, int32_t num_perm, int32_t b, uint32_t *out);
 
+/* ---- All-pairs Jaccard --------------------------------------------------------------------- */
+/* Every pair of rows of two signature matrices A [n_a, num_perm] and B [n_b, num_perm] of sig_dtype, with no LSH banding in
+ * front (no false negatives): counts[i*ldc + j] = the number of positions k where A[i][k] == B[j][k] -- the numerator of
+ * MinHash.jaccard (ref: datasketch/minhash.py:299-324), exact on the full element width (uint64 values that differ only in
+ * bits 32..63 are not equal).  d_b == NULL compares A with itself (n_b is then n_a).  ldc >= n_b.  Enqueued on the ctx stream.
+ * Rows: fewer than 2^32 per matrix. */
+MHX_API int mhx_jaccard_matrix_dev(mhx_ctx *ctx, const void *d_a, int64_t n_a, const void *d_b, int64_t n_b, int sig_dtype,
+                                   int32_t num_perm, int32_t *d_counts, int64_t ldc);
+/* Host form (uint64 rows, b == NULL: A with itself): counts int32[n_a, n_b]; B is staged once, A and the counts stream
+ * through the device in row blocks.  Blocking. */
+MHX_API int mhx_jaccard_matrix(mhx_ctx *ctx, const uint64_t *a, int64_t n_a, const uint64_t *b, int64_t n_b, int32_t num_perm,
+                               int32_t *counts);
+/* Thresholded form: every pair (i, j) whose count is >= min_count, ascending by (i, j), each once -- pairs int64[capacity, 2],
+ * counts int32[capacity].  d_b == NULL: self-join of A, pairs i < j only.  *n_pairs always receives the exact total; when it
+ * exceeds capacity the buffers' contents are unspecified (nothing is written at or past capacity entries) and the caller
+ * calls again with a larger buffer.  min_count <= 0 keeps every pair, min_count > num_perm none (nothing is launched).  Keeps a
+ * sort's worth of scratch (about 12 bytes per pair found) in the context until mhx_ctx_release_scratch.  Blocking. */
+MHX_API int mhx_jaccard_threshold_pairs_dev(mhx_ctx *ctx, const void *d_a, int64_t n_a, const void *d_b, int64_t n_b, int sig_dtype,
+                                            int32_t num_perm, int32_t min_count, int64_t *d_pairs, int32_t *d_counts,
+                                            int64_t capacity, int64_t *n_pairs);
+MHX_API int mhx_jaccard_threshold_pairs(mhx_ctx *ctx, const uint64_t *a, int64_t n_a, const uint64_t *b, int64_t n_b,
+                                        int32_t num_perm, int32_t min_count, int64_t *pairs, int32_t *counts, int64_t capacity,
+                                        int64_t *n_pairs);
+/* The b-bit twins on packed rows (mhx_bbit_pack*: [n, num_blocks] uint64, num_blocks as mhx_bbit_num_blocks): counts = the
+ * positions of num_perm whose b-bit values agree, the `intersection` of bBitMinHash.jaccard (ref:
+ * datasketch/b_bit_minhash.py:53-72), counted as num_perm minus the slots that differ (XOR, fold, popcount).  The estimate
+ * is (counts / num_perm - C1) / (1 - C2) with the reference's C1, C2.  Arguments otherwise as above; b in [0, 32]. */
+MHX_API int mhx_bbit_jaccard_matrix_dev(mhx_ctx *ctx, const uint64_t *d_a, int64_t n_a, const uint64_t *d_b, int64_t n_b,
+                                        int32_t num_perm, int32_t b, int32_t *d_counts, int64_t ldc);
+MHX_API int mhx_bbit_jaccard_matrix(mhx_ctx *ctx, const uint64_t *a, int64_t n_a, const uint64_t *b_blocks, int64_t n_b,
+                                    int32_t num_perm, int32_t b, int32_t *counts);
+MHX_API int mhx_bbit_jaccard_threshold_pairs_dev(mhx_ctx *ctx, const uint64_t *d_a, int64_t n_a, const uint64_t *d_b, int64_t n_b,
+                                                 int32_t num_perm, int32_t b, int32_t min_count, int64_t *d_pairs,
+                                                 int32_t *d_counts, int64_t capacity, int64_t *n_pairs);
+MHX_API int mhx_bbit_jaccard_threshold_pairs(mhx_ctx *ctx, const uint64_t *a, int64_t n_a, const uint64_t *b_blocks, int64_t n_b,
+                                             int32_t num_perm, int32_t b, int32_t min_count, int64_t *pairs, int32_t *counts,
+                                             int64_t capacity, int64_t *n_pairs);
+
 /* ---- Multi-GPU: assemble the signature matrix (RCCL over xGMI) ----------------------------- */
 /* 128-byte RCCL unique id, created on rank 0 and distributed by the caller (env, file, socket). */
 #define MHX_COMM_ID_BYTES 128
