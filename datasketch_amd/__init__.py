@@ -9,6 +9,7 @@ from datasketch_amd.b_bit_minhash import bBitMinHash
 from datasketch_amd import lsh_bulk
 from datasketch_amd.hashfunc import prehashed, sha1_hash32, sha1_hash64, sha1_hash_many
 from datasketch_amd.lean_minhash import LeanMinHash
+from datasketch_amd.lsh import MinHashLSH
 from datasketch_amd.minhash import MinHash
 from datasketch_amd.weighted_minhash import WeightedMinHash, WeightedMinHashGenerator
 
@@ -17,6 +18,7 @@ __version__ = "0.1.0"
 __all__ = [
     "LeanMinHash",
     "MinHash",
+    "MinHashLSH",
     "WeightedMinHash",
     "WeightedMinHashGenerator",
     "bBitMinHash",

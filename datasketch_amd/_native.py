@@ -117,6 +117,9 @@ _PROTOTYPES = {
     "mhx_bbit_jaccard_matrix": [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp],
     "mhx_bbit_jaccard_threshold_pairs_dev": [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _i64, ctypes.POINTER(_i64)],
     "mhx_bbit_jaccard_threshold_pairs": [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _i64, ctypes.POINTER(_i64)],
+    "mhx_lsh_bands_merge_dev": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, ctypes.c_uint32, _i32, _vp, _vp],
+    "mhx_lsh_bands_compact_dev": [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp],
+    "mhx_rows_compact_dev": [_vp, _vp, _i64, _i64, _vp, _vp, ctypes.POINTER(_i64)],
     "mhx_comm_unique_id": [_vp],
     "mhx_comm_create": [_vp, _vp, _int, _int, ctypes.POINTER(_vp)],
     "mhx_comm_destroy": [_vp],
@@ -915,6 +918,25 @@ class Context:
         return int(found.value)
 
     # -- device-resident entry points (pointers are DeviceBuffer.ptr + byte offsets) -----------
+    def lsh_bands_merge_dev(self, d_dig_a: int, d_rows_a: int, n_a: int, d_dig_b: int, d_rows_b: int, n_b: int, row_offset_b: int,
+                            bands: int, d_dig_out: int, d_rows_out: int) -> None:
+        """mhx_lsh_bands_merge_dev: per band, the stable merge by digest of two sorted runs (B's rows + row_offset_b); enqueued."""
+        check(self.lib.mhx_lsh_bands_merge_dev(self.handle, _vp(d_dig_a), _vp(d_rows_a), int(n_a), _vp(d_dig_b), _vp(d_rows_b), int(n_b),
+                                               int(row_offset_b), int(bands), _vp(d_dig_out), _vp(d_rows_out)))
+
+    def lsh_bands_compact_dev(self, d_dig: int, d_rows: int, n: int, bands: int, d_live_bits: int, n_live: int, d_dig_out: int,
+                              d_rows_out: int) -> None:
+        """mhx_lsh_bands_compact_dev: the live entries of sorted bands with remapped rows (blocking)."""
+        check(self.lib.mhx_lsh_bands_compact_dev(self.handle, _vp(d_dig), _vp(d_rows), int(n), int(bands), _vp(d_live_bits), int(n_live),
+                                                 _vp(d_dig_out), _vp(d_rows_out)))
+
+    def rows_compact_dev(self, d_src: int, row_bytes: int, n_rows: int, d_live_bits: int, d_dst: int) -> int:
+        """mhx_rows_compact_dev: the live rows gathered in slot order; returns how many (blocking)."""
+        kept = _i64(0)
+        check(self.lib.mhx_rows_compact_dev(self.handle, _vp(d_src), int(row_bytes), int(n_rows), _vp(d_live_bits), _vp(d_dst),
+                                            ctypes.byref(kept)))
+        return int(kept.value)
+
     def minhash_bulk_dev(self, permutations, d_hv: int, hv_dtype: int, d_offsets: Optional[int], fixed_len: int, n_sets: int,
                          total_tokens: int, d_init: Optional[int], init_stride: int, d_out: int, out_dtype: int) -> None:
         perm = self.perm_handle(permutations)

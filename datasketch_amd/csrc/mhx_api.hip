@@ -390,6 +390,10 @@ int mhx_ctx_set_option(mhx_ctx *ctx, const char *key, int64_t value) {
     else if (!strcmp(key, "pack.fused")) ctx->opt_pack_fused = value;
     else if (!strcmp(key, "weighted.refill")) ctx->opt_weighted_refill = value;
     else if (!strcmp(key, "lsh.prehash")) ctx->opt_lsh_prehash = value;
+    else if (!strcmp(key, "lsh.merge_items")) {
+        if (value != 0 && value != 8 && value != 16) return fail(MHX_ERR_INVALID, "lsh.merge_items must be 0, 8 or 16");
+        ctx->opt_lsh_merge_items = value;
+    }
     else return fail(MHX_ERR_INVALID, "unknown option '%s'", key);
     return MHX_OK;
 }
@@ -2002,6 +2006,49 @@ int mhx_bbit_jaccard_threshold_pairs(mhx_ctx *ctx, const uint64_t *a, int64_t n_
     if (n_pairs) *n_pairs = 0;
     MHX_REQUIRE(b >= 0 && b <= 32, "b must be an integer in [0, 32]");
     return all_pairs_threshold_host(ctx, a, n_a, b_blocks, n_b, num_perm, b, min_count, pairs, counts, capacity, n_pairs);
+}
+
+int mhx_lsh_bands_merge_dev(mhx_ctx *ctx, const uint64_t *d_dig_a, const uint32_t *d_rows_a, int64_t n_a, const uint64_t *d_dig_b,
+                            const uint32_t *d_rows_b, int64_t n_b, uint32_t row_offset_b, int32_t bands, uint64_t *d_dig_out,
+                            uint32_t *d_rows_out) {
+    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
+    MHX_GUARD(ctx);
+    MHX_REQUIRE(bands > 0, "bands must be positive");
+    MHX_REQUIRE(n_a >= 0 && n_b >= 0, "bad shape");
+    MHX_REQUIRE(n_a + n_b < ((int64_t)1 << 32), "more than 2^32-1 entries per band");
+    if (n_a + n_b == 0) return MHX_OK;
+    MHX_REQUIRE((n_a == 0 || (d_dig_a && d_rows_a)) && (n_b == 0 || (d_dig_b && d_rows_b)) && d_dig_out && d_rows_out,
+                "NULL device pointer");
+    if (int rc = ctx->activate()) return rc;
+    return mhx::launch_lsh_bands_merge(ctx, d_dig_a, d_rows_a, n_a, d_dig_b, d_rows_b, n_b, row_offset_b, bands, d_dig_out, d_rows_out);
+}
+
+int mhx_lsh_bands_compact_dev(mhx_ctx *ctx, const uint64_t *d_dig, const uint32_t *d_rows, int64_t n, int32_t bands,
+                              const uint32_t *d_live_bits, int64_t n_live, uint64_t *d_dig_out, uint32_t *d_rows_out) {
+    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
+    MHX_GUARD(ctx);
+    MHX_REQUIRE(bands > 0, "bands must be positive");
+    MHX_REQUIRE(n >= 0 && n_live >= 0 && n_live <= n, "bad shape");
+    MHX_REQUIRE(n < ((int64_t)1 << 32), "more than 2^32-1 rows per call");
+    if (n == 0) return MHX_OK;
+    MHX_REQUIRE(d_dig && d_rows && d_live_bits && ((d_dig_out && d_rows_out) || n_live == 0), "NULL device pointer");
+    if (int rc = ctx->activate()) return rc;
+    return mhx::launch_lsh_bands_compact(ctx, d_dig, d_rows, n, bands, d_live_bits, n_live, d_dig_out, d_rows_out);
+}
+
+int mhx_rows_compact_dev(mhx_ctx *ctx, const void *d_src, int64_t row_bytes, int64_t n_rows, const uint32_t *d_live_bits, void *d_dst,
+                         int64_t *n_kept) {
+    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
+    MHX_GUARD(ctx);
+    MHX_REQUIRE(n_kept, "n_kept is NULL");
+    *n_kept = 0;
+    MHX_REQUIRE(row_bytes > 0 && n_rows >= 0, "bad shape");
+    MHX_REQUIRE(n_rows < ((int64_t)1 << 32), "more than 2^32-1 rows per call");
+    MHX_REQUIRE(n_rows == 0 || row_bytes <= INT64_MAX / n_rows, "row_bytes * n_rows overflows");
+    if (n_rows == 0) return MHX_OK;
+    MHX_REQUIRE(d_src && d_live_bits && d_dst, "NULL device pointer");
+    if (int rc = ctx->activate()) return rc;
+    return mhx::launch_rows_compact(ctx, d_src, row_bytes, n_rows, d_live_bits, d_dst, n_kept);
 }
 
 }  // extern "C"

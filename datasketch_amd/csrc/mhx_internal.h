@@ -94,6 +94,7 @@ struct mhx_ctx {
     int64_t opt_lsh_chunk = 0;      // bucketing: rows per thread of a scatter pass over a unit-stride source: 0 auto (16), 8 = eight (A/B)
     int64_t opt_lsh_bigbins = 0;    // bucketing: 0 auto (2.56M .. 10.2M rows: one scatter level into 1024 big bins + the big bin pass), 1 never, 2 whenever there are at least 4 bins (tests)
     int64_t opt_lsh_team = 0;       // bucketing, unit-stride sources: 0 auto (one team of 1024 threads x 8 rows per workgroup), 256 = teams of 256 x 16 (until round 6; A/B, tests)
+    int64_t opt_lsh_merge_items = 0; // mhx_lsh_bands_merge_dev: outputs per thread of the merge tile, 0 auto (8), 8 or 16 (A/B)
     int64_t opt_lsh_levels = 0;     // bucketing: 0 auto (two scatter levels beyond 2^10 bins per band), 2 = two levels whenever there are at least 4 bins
     int64_t opt_pack_fused = 0;     // mhx_bbit_pack_band_digests_dev: 0 auto (one read of the matrix where the shape allows), 1 = always the two kernels
     int64_t opt_weighted_refill = 0; // one-wave-per-row walk, 4096-column rows: 0 auto (non-temporal row loads; values in: also the refill right after staging, chunk after chunk), 1 = round 4 (plain loads, refill behind the walk), 2 / 3 = force non-temporal / + early refill
@@ -205,6 +206,16 @@ int launch_jaccard_matrix(mhx_ctx *ctx, const void *d_a, int64_t n_a, const void
 int launch_jaccard_threshold(mhx_ctx *ctx, const void *d_a, int64_t n_a, const void *d_b, int64_t n_b, int sig_dtype, int32_t k,
                              int32_t b, int32_t min_count, int64_t *d_pairs, int32_t *d_counts, int64_t capacity,
                              int64_t *n_pairs);
+
+// lsh_index_kernels.hip: the update path of a live index held as sorted bands (mhx_lsh_bands_merge_dev, mhx_lsh_bands_compact_dev,
+// mhx_rows_compact_dev).  The compactions are blocking: they read their totals back.
+int launch_lsh_bands_merge(mhx_ctx *ctx, const uint64_t *d_dig_a, const uint32_t *d_rows_a, int64_t n_a, const uint64_t *d_dig_b,
+                           const uint32_t *d_rows_b, int64_t n_b, uint32_t row_offset_b, int32_t bands, uint64_t *d_dig_out,
+                           uint32_t *d_rows_out);
+int launch_lsh_bands_compact(mhx_ctx *ctx, const uint64_t *d_dig, const uint32_t *d_rows, int64_t n, int32_t bands,
+                             const uint32_t *d_live_bits, int64_t n_live, uint64_t *d_dig_out, uint32_t *d_rows_out);
+int launch_rows_compact(mhx_ctx *ctx, const void *d_src, int64_t row_bytes, int64_t n_rows, const uint32_t *d_live_bits, void *d_dst,
+                        int64_t *n_kept);
 
 int bbit_slot_size(int b);
 

@@ -146,6 +146,10 @@ def insert_bulk(lsh, keys: Iterable[Hashable], signatures, check_duplication: bo
     ``gc.freeze()`` instead (no walk now or ever, process-wide effect); ``"leave"`` does neither."""
     if settle not in ("collect", "freeze", "leave"):
         raise ValueError("settle must be 'collect', 'freeze' or 'leave'")
+    from datasketch_amd.lsh import MinHashLSH
+
+    if isinstance(lsh, MinHashLSH):  # our own index: its bulk path (the index's gpu_mode decides where it lives)
+        return lsh.insert_bulk(keys, signatures, check_duplication=check_duplication)
     sig, words = _matrix(signatures), _words(signatures)
     n, k = sig.shape
     if k != lsh.h * words:
@@ -245,6 +249,10 @@ def query_bulk(lsh, signatures, gpu_mode: str = "detect") -> List[list]:
     keys of all probes taken in one pass and, for the in-memory storage, the ``b`` dictionary probes per
     signature done by C-level ``map(dict.get, ...)``.  Returns one list of keys per row (order within a list
     is unspecified, as in the reference)."""
+    from datasketch_amd.lsh import MinHashLSH
+
+    if isinstance(lsh, MinHashLSH):
+        return lsh.query_bulk(signatures)
     sig, words = _matrix(signatures), _words(signatures)
     n, k = sig.shape
     if k != lsh.h * words:

@@ -107,7 +107,8 @@ MHX_API int mhx_ctx_device_info(mhx_ctx *ctx, char *name, int name_len, int *cus
  * ("weighted.min_dim", dense rows at least this wide -- a multiple of 4, up to 4096 columns -- go to the one-wave-per-row / fetcher-walker kernels:
  * 0 auto = 4, 1024 = the rule until round 6),
  * ("lsh.sort", 0 auto: mhx_lsh_sort_bands buckets the bands in two passes (three beyond 10.2M rows) and falls back to the radix sort when a bin
- * overflows or n > 41M, 1 = radix sort always). */
+ * overflows or n > 41M, 1 = radix sort always),
+ * ("lsh.merge_items", mhx_lsh_bands_merge_dev: outputs per thread of a 256-thread merge tile, 0 auto = 8, or 8 / 16; results unaffected). */
 MHX_API int mhx_ctx_set_option(mhx_ctx *ctx, const char *key, int64_t value);
 /* Kernel event counters since the last call (synchronises the stream, then resets them):
  *   out[0] sets the sieve launch left to the full launch (failed proof, or skipped by the back-off),
@@ -493,6 +494,32 @@ MHX_API int mhx_bbit_jaccard_threshold_pairs_dev(mhx_ctx *ctx, const uint64_t *d
 MHX_API int mhx_bbit_jaccard_threshold_pairs(mhx_ctx *ctx, const uint64_t *a, int64_t n_a, const uint64_t *b_blocks, int64_t n_b,
                                              int32_t num_perm, int32_t b, int32_t min_count, int64_t *pairs, int32_t *counts,
                                              int64_t capacity, int64_t *n_pairs);
+
+/* ---- Live LSH index: the update path of sorted bands ------------------------------------- */
+/* The index of datasketch_amd.MinHashLSH (ref: datasketch/lsh.py:326-347 insert, :509-528 remove) is the layout of
+ * mhx_lsh_sort_bands*: per band the digests uint64[bands][n] ascending by (digest, row) with their rows uint32[bands][n] (rows are
+ * slot numbers of the signature matrix), which mhx_lsh_query_dev and mhx_lsh_candidate_pairs_dev read.  A batch is merged in and
+ * removed slots are compacted out; nothing is sorted twice.  Rows and entries per band: fewer than 2^32.
+ *
+ * Merge, per band, two runs sorted by (digest, row) -- A [bands][n_a] and B [bands][n_b] -- into d_dig_out / d_rows_out
+ * [bands][n_a + n_b] (caller-owned, not overlapping the inputs); B's rows get row_offset_b added.  The caller guarantees that every
+ * B row after the offset is greater than every A row: ties then go to A and the output is the stable sort of A||B by digest,
+ * what mhx_lsh_sort_bands* gives for the union.  Either side may be empty.  Enqueued on the ctx stream. */
+MHX_API int mhx_lsh_bands_merge_dev(mhx_ctx *ctx, const uint64_t *d_dig_a, const uint32_t *d_rows_a, int64_t n_a,
+                                    const uint64_t *d_dig_b, const uint32_t *d_rows_b, int64_t n_b, uint32_t row_offset_b,
+                                    int32_t bands, uint64_t *d_dig_out, uint32_t *d_rows_out);
+/* Compact sorted bands [bands][n] whose rows are the slots 0 .. n-1 (each once per band): the entries whose slot is dead in
+ * d_live_bits (bit (row & 31) of word row >> 5 set = live; ceil(n / 32) words) are dropped and every other row becomes
+ * remap[row], the number of live slots below it, so the order is kept.  d_dig_out / d_rows_out: [bands][n_live], band j from
+ * j * n_live.  MHX_ERR_INVALID when the bitmap does not hold n_live live slots or the bands do not hold bands * n_live live
+ * entries; nothing is ever written at or past bands * n_live entries.  Blocking. */
+MHX_API int mhx_lsh_bands_compact_dev(mhx_ctx *ctx, const uint64_t *d_dig, const uint32_t *d_rows, int64_t n, int32_t bands,
+                                      const uint32_t *d_live_bits, int64_t n_live, uint64_t *d_dig_out, uint32_t *d_rows_out);
+/* The matrix side of compaction: the live rows (d_live_bits as above, ceil(n_rows / 32) words) of d_src [n_rows][row_bytes]
+ * gathered in slot order into d_dst (room for the live rows; not overlapping d_src); *n_kept receives their number.  16-byte
+ * loads and stores where both pointers and row_bytes allow them.  Blocking. */
+MHX_API int mhx_rows_compact_dev(mhx_ctx *ctx, const void *d_src, int64_t row_bytes, int64_t n_rows, const uint32_t *d_live_bits,
+                                 void *d_dst, int64_t *n_kept);
 
 /* ---- Multi-GPU: assemble the signature matrix (RCCL over xGMI) ----------------------------- */
 /* 128-byte RCCL unique id, created on rank 0 and distributed by the caller (env, file, socket). */
