@@ -17,6 +17,7 @@ import scipy.sparse as sp
 
 from datasketch_amd import WeightedMinHashGenerator, _native
 from oracle import oracle as O
+from tests.weighted_dispatch import dense_walk_launch
 
 pytestmark = pytest.mark.gpu
 
@@ -78,8 +79,10 @@ _SAMPLES = [1, 65, 129, 300, 513]
 
 
 def _case_id(dim, s):
-    ahead = dim % 4 == 0 and 4 <= dim <= 4096
-    kernel = "walk_wave" if dim % 4 == 0 and 1024 <= dim <= 4096 else "walk_dense"
+    """The kernel launch_weighted_dense_walk takes and the AHEAD instantiation of the workgroup-per-row kernel the case runs
+    (tests/weighted_dispatch.py)."""
+    kernel = dense_walk_launch(dim, s, True).kernel
+    ahead = dense_walk_launch(dim, s, True, options={"weighted.kernel": 1}).ahead
     return f"{kernel}_AHEAD_{str(ahead).lower()}-dim{dim}-S{s}-chunks{(s + 63) // 64}"
 
 
@@ -92,8 +95,16 @@ _CASES = [(d, s) for d in _DIMS for s in _SAMPLES] + [(1024, 300), (1024, 513), 
                                                        (4096, 192), (4096, 256), (2048, 384), (1024, 200)]
 
 
-def _wave_kernel_takes(dim):
-    return dim % 4 == 0 and 1024 <= dim <= 4096
+def _wave_kernel_takes(dim, s):
+    return dense_walk_launch(dim, s, True).kernel == "walk_wave" and dense_walk_launch(dim, s, False).kernel == "walk_wave"
+
+
+def _dense_rows_per_turn(dim, s, cus):
+    """The most rows one turn of the grid takes, over the dense launches of a case: logs and values in, and the workgroup-per-row
+    kernel the wave kernel's rows are checked against -- at least 256 x 8, the count round 4 assumed for the wave kernel."""
+    launches = [dense_walk_launch(dim, s, logs, options=o, cus=cus) for logs in (True, False) for o in ({}, {"weighted.kernel": 1})]
+    floor = 256 * 8 if _wave_kernel_takes(dim, s) else 0
+    return max([floor] + [launch.rows_per_turn for launch in launches])
 
 
 @pytest.mark.parametrize("dim,s", _CASES, ids=[_case_id(d, s) for d, s in _CASES])
@@ -102,7 +113,7 @@ def test_weighted_kernels_with_several_rows_per_workgroup(ctx, dim, s):
     values (device log), weighted.split 0 / 1: a sample of rows against the C oracle (all rows of small shapes), EVERY
     row against the evaluate-every-element kernels (weighted.path = 2)."""
     rng = np.random.RandomState(zlib.crc32(f"{dim}/{s}".encode()))
-    dense_blocks, csr_blocks = _walk_dense_blocks(dim, s)
+    _, csr_blocks = _walk_dense_blocks(dim, s)
     heavy = (dim + s) % 2 == 1
     g = WeightedMinHashGenerator(dim, s, seed=11, gpu_mode="always")
     gv = WeightedMinHashGenerator(dim, s, seed=11, gpu_mode="always", device_log=True)
@@ -138,10 +149,10 @@ def test_weighted_kernels_with_several_rows_per_workgroup(ctx, dim, s):
         assert np.array_equal(ne_v, ne_v2) and np.array_equal(out_v[ne_v.astype(bool)], every_v[ne_v.astype(bool)])
         return out, ne
 
-    n_dense = 3 * (2048 if _wave_kernel_takes(dim) else dense_blocks) + 37  # (256 workgroups of eight waves: one row per wave and turn)
+    n_dense = 3 * _dense_rows_per_turn(dim, s, ctx.info()["compute_units"]) + 37  # (three turns of every dense launch's grid and a ragged one)
     x = _fuzz_matrix(rng, n_dense, dim, heavy)
     out0, ne0 = check(x, False)
-    if _wave_kernel_takes(dim):  # the workgroup-per-row kernel on the same rows (its AHEAD instantiation)
+    if _wave_kernel_takes(dim, s):  # the workgroup-per-row kernel on the same rows (its AHEAD instantiation)
         wctx.set_option("weighted.kernel", 1)
         try:
             out_w, ne_w = g.minhash_many_arrays(x)
