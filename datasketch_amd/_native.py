@@ -120,6 +120,8 @@ _PROTOTYPES = {
     "mhx_lsh_bands_merge_dev": [_vp, _vp, _vp, _i64, _vp, _vp, _i64, ctypes.c_uint32, _i32, _vp, _vp],
     "mhx_lsh_bands_compact_dev": [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _vp, _vp],
     "mhx_rows_compact_dev": [_vp, _vp, _i64, _i64, _vp, _vp, ctypes.POINTER(_i64)],
+    "mhx_lsh_forest_build_dev_typed": [_vp, _vp, _int, _i64, _i32, _i32, _i32, _vp],
+    "mhx_lsh_forest_query_dev_typed": [_vp, _vp, _int, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i64, _i32, _vp, _vp],
     "mhx_comm_unique_id": [_vp],
     "mhx_comm_create": [_vp, _vp, _int, _int, ctypes.POINTER(_vp)],
     "mhx_comm_destroy": [_vp],
@@ -936,6 +938,18 @@ class Context:
         check(self.lib.mhx_rows_compact_dev(self.handle, _vp(d_src), int(row_bytes), int(n_rows), _vp(d_live_bits), _vp(d_dst),
                                             ctypes.byref(kept)))
         return int(kept.value)
+
+    def lsh_forest_build_dev(self, d_sig: int, sig_dtype: int, n: int, row_words: int, l: int, tree_words: int, d_order: int) -> None:
+        """mhx_lsh_forest_build_dev_typed: per tree, the rows ascending by (the tree's words, row) into order u32[l][n]; enqueued."""
+        check(self.lib.mhx_lsh_forest_build_dev_typed(self.handle, _vp(d_sig), int(sig_dtype), int(n), int(row_words), int(l),
+                                                      int(tree_words), _vp(d_order)))
+
+    def lsh_forest_query_dev(self, d_sig: int, sig_dtype: int, n: int, row_words: int, l: int, tree_words: int, w: int, d_order: int,
+                             d_probes: int, m: int, k: int, d_slots: int, d_counts: int) -> None:
+        """mhx_lsh_forest_query_dev_typed: the top-k walk of m probes into slots u32[m][k] and counts i32[m]; enqueued."""
+        check(self.lib.mhx_lsh_forest_query_dev_typed(self.handle, _vp(d_sig), int(sig_dtype), int(n), int(row_words), int(l),
+                                                      int(tree_words), int(w), _vp(d_order), _vp(d_probes), int(m), int(k), _vp(d_slots),
+                                                      _vp(d_counts)))
 
     def minhash_bulk_dev(self, permutations, d_hv: int, hv_dtype: int, d_offsets: Optional[int], fixed_len: int, n_sets: int,
                          total_tokens: int, d_init: Optional[int], init_stride: int, d_out: int, out_dtype: int) -> None:

@@ -2051,4 +2051,41 @@ int mhx_rows_compact_dev(mhx_ctx *ctx, const void *d_src, int64_t row_bytes, int
     return mhx::launch_rows_compact(ctx, d_src, row_bytes, n_rows, d_live_bits, d_dst, n_kept);
 }
 
+int mhx_lsh_forest_build_dev_typed(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n, int32_t row_words, int32_t l,
+                                   int32_t tree_words, uint32_t *d_order) {
+    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
+    MHX_GUARD(ctx);
+    MHX_REQUIRE(sig_dtype == MHX_U32 || sig_dtype == MHX_U64, "sig_dtype must be MHX_U32 or MHX_U64");
+    MHX_REQUIRE(l > 0 && l < 65536, "l must be in [1, 65535]");
+    MHX_REQUIRE(tree_words > 0 && row_words > 0 && (int64_t)l * tree_words <= row_words, "l * tree_words must be in [1, row_words]");
+    MHX_REQUIRE(n >= 0 && n < ((int64_t)1 << 32), "n_sigs must be in [0, 2^32)");
+    if (n == 0) return MHX_OK;
+    MHX_REQUIRE(d_sig && d_order, "NULL device pointer");
+    if (int rc = ctx->activate()) return rc;
+    return mhx::launch_lsh_forest_build(ctx, d_sig, sig_dtype, n, row_words, l, tree_words, d_order);
+}
+
+int mhx_lsh_forest_query_dev_typed(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n, int32_t row_words, int32_t l,
+                                   int32_t tree_words, int32_t w, const uint32_t *d_order, const void *d_probes, int64_t m, int32_t k,
+                                   uint32_t *d_slots, int32_t *d_counts) {
+    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
+    MHX_GUARD(ctx);
+    MHX_REQUIRE(sig_dtype == MHX_U32 || sig_dtype == MHX_U64, "sig_dtype must be MHX_U32 or MHX_U64");
+    MHX_REQUIRE(l > 0 && l < 65536, "l must be in [1, 65535]");
+    MHX_REQUIRE(tree_words > 0 && row_words > 0 && (int64_t)l * tree_words <= row_words, "l * tree_words must be in [1, row_words]");
+    MHX_REQUIRE((w == 1 || w == 2) && tree_words % w == 0 && tree_words / w < 65536, "w must be 1 or 2 and divide tree_words");
+    MHX_REQUIRE(k > 0, "k must be positive");
+    MHX_REQUIRE(n >= 0 && n < ((int64_t)1 << 32), "n_sigs must be in [0, 2^32)");
+    MHX_REQUIRE(m >= 0 && m < ((int64_t)1 << 31), "m must be in [0, 2^31)");
+    if (m == 0) return MHX_OK;
+    MHX_REQUIRE(d_counts, "NULL device pointer");
+    if (int rc = ctx->activate()) return rc;
+    if (n == 0) {
+        MHX_HIP_CHECK(hipMemsetAsync(d_counts, 0, sizeof(int32_t) * (size_t)m, ctx->stream));
+        return MHX_OK;
+    }
+    MHX_REQUIRE(d_sig && d_order && d_probes && d_slots, "NULL device pointer");
+    return mhx::launch_lsh_forest_query(ctx, d_sig, sig_dtype, n, row_words, l, tree_words, w, d_order, d_probes, m, k, d_slots, d_counts);
+}
+
 }  // extern "C"

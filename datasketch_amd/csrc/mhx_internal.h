@@ -217,6 +217,13 @@ int launch_lsh_bands_compact(mhx_ctx *ctx, const uint64_t *d_dig, const uint32_t
 int launch_rows_compact(mhx_ctx *ctx, const void *d_src, int64_t row_bytes, int64_t n_rows, const uint32_t *d_live_bits, void *d_dst,
                         int64_t *n_kept);
 
+// lsh_forest_kernels.hip: the LSH Forest (mhx_lsh_forest_build_dev_typed, mhx_lsh_forest_query_dev_typed); both enqueue only
+int launch_lsh_forest_build(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n, int32_t row_words, int32_t l, int32_t tree_words,
+                            uint32_t *d_order);
+int launch_lsh_forest_query(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n, int32_t row_words, int32_t l, int32_t tree_words,
+                            int32_t w, const uint32_t *d_order, const void *d_probes, int64_t m, int32_t k, uint32_t *d_slots,
+                            int32_t *d_counts);
+
 int bbit_slot_size(int b);
 
 }  // namespace mhx

@@ -1,0 +1,450 @@
+"""``MinHashLSHForest`` with the reference's public surface (ref: datasketch/lshforest.py), held as sorted trees.
+
+The reference keeps, per tree, a dictionary tree key -> keys and the sorted list of the tree keys, a tree key being the
+big-endian bytes of the tree's ``D = num_perm // l`` hash values; a query binary-searches prefixes of the probe's tree keys in
+those lists, longest prefix first.  Here the index is a signature matrix of *slots* (a key's rank in insertion order; only the
+``l * D`` hash values the trees cover are stored) and, per tree, ``order[t]``: the slots ascending by (the tree's words compared
+lexicographically as unsigned integers, slot).  That is the order of the reference's byte keys with the keys of one bucket in
+insertion order, so the slots matching a probe on their first ``r`` hash values are one contiguous range of ``order[t]``.
+
+``query(minhash, k)`` is the reference's walk (ref: lshforest.py:92-128): for ``r = D .. 1``, for ``t = 0 .. l-1``, through the
+positions of tree ``t``'s level-``r`` range ascending, take the slot if it was not taken before; stop at ``k``.  The reference
+returns the taken keys as ``list(set)``; :meth:`MinHashLSHForest.query` and :meth:`MinHashLSHForest.query_bulk` return them in
+the order the walk takes them.
+
+``gpu_mode`` is the seam of ``MinHashLSH``: ``'always'`` / ``'detect'`` keep the matrix and ``order`` on an MI355X
+(``mhx_lsh_forest_build_dev_typed``, ``mhx_lsh_forest_query_dev_typed``), ``'disable'`` (or ``'detect'`` without a device) keeps
+the same arrays in numpy (``np.lexsort``, a vectorised search of the level ranges and a plain walk).  Both back ends hold the same
+``order``, element for element, and give the same answers in the same order.
+
+Differences from the reference: a key added after :meth:`MinHashLSHForest.index` is not searchable until the
+next ``index()`` (the reference finds it early when its tree key equals an indexed one); ``keys``, ``hashtables`` and
+``sorted_hashtables`` are read-only views materialised on access; one kind of signature per index.
+"""
+from __future__ import annotations
+
+from typing import Hashable, List, Optional
+
+import numpy as np
+
+from datasketch_amd import _native, lsh_bulk
+from datasketch_amd.lsh import _words_of
+
+__all__ = ["MinHashLSHForest"]
+
+_U32_MAX = 0xFFFFFFFF
+MAX_CANDIDATES = 16384  # MHX_LSH_FOREST_MAX_CANDIDATES: l * min(2k - 1, n) candidates per probe the query kernel stages in LDS
+
+
+def tree_order(sig: np.ndarray, l: int, tree_words: int) -> np.ndarray:
+    """``order u32[l][n]``: per tree the rows of ``sig`` ascending by (the tree's words, row)."""
+    n = sig.shape[0]
+    order = np.empty((l, n), dtype=np.uint32)
+    for t in range(l if n else 0):
+        cols = sig[:, t * tree_words : (t + 1) * tree_words]
+        order[t] = np.lexsort(cols.T[::-1])  # the last key is the primary one; a stable sort, so equal keys keep row order
+    return order
+
+
+def _bound(sig, order_t, q, col0: int, lo: np.ndarray, hi: np.ndarray, upper: bool) -> np.ndarray:
+    """Per probe row of ``q`` ``[m, nw]``: the first position in ``[lo, hi)`` of ``order_t`` whose row's words ``col0 .. col0+nw``
+    are not below (``upper``: are above) the probe's, the rows being ascending there -- a bisection of all probes at once."""
+    lo, hi = lo.copy(), hi.copy()
+    cols = np.arange(col0, col0 + q.shape[1])[None, :]
+    while True:
+        idx = np.flatnonzero(lo < hi)
+        if idx.size == 0:
+            return lo
+        mid = (lo[idx] + hi[idx]) >> 1
+        rows = sig[order_t[mid][:, None], cols]
+        probe = q[idx]
+        differ = rows != probe
+        first = differ.argmax(axis=1)
+        at = np.arange(idx.size)
+        right = np.where(differ.any(axis=1), rows[at, first] < probe[at, first], upper)
+        lo[idx[right]] = mid[right] + 1
+        hi[idx[~right]] = mid[~right]
+
+
+def level_ranges(sig, order, probes, l: int, depth: int, w: int):
+    """``lo, hi int64[l][depth + 2][m]``: ``[lo[t][r], hi[t][r])`` is the range of ``order[t]`` matching probe ``i`` on its first
+    ``r`` hash values; level 0 is everything, level ``depth + 1`` the empty range at ``lo[t][depth]``."""
+    m, n = probes.shape[0], sig.shape[0]
+    lo = np.zeros((l, depth + 2, m), dtype=np.int64)
+    hi = np.full((l, depth + 2, m), n, dtype=np.int64)
+    if probes.dtype != sig.dtype:
+        probes = probes.astype(np.result_type(probes.dtype, sig.dtype))
+    for t in range(l):
+        col0 = t * depth * w
+        for r in range(1, depth + 1):
+            q = probes[:, col0 : col0 + r * w]
+            lo[t, r] = _bound(sig, order[t], q, col0, lo[t, r - 1], hi[t, r - 1], upper=False)
+            hi[t, r] = _bound(sig, order[t], q, col0, lo[t, r], hi[t, r - 1], upper=True)
+        lo[t, depth + 1] = hi[t, depth + 1] = lo[t, depth]
+    return lo, hi
+
+
+def _walk(order, lo, hi, l: int, depth: int, k: int) -> list:
+    """The reference's walk for one probe (``lo``, ``hi``: ``[l][depth + 2]`` lists): level by level, tree by tree, the positions
+    a level adds to the one above it, left part then right part."""
+    out, seen = [], set()
+    for r in range(depth, 0, -1):
+        for t in range(l):
+            for a, b in ((lo[t][r], lo[t][r + 1]), (hi[t][r + 1], hi[t][r])):
+                while a < b:
+                    chunk = order[t][a : min(b, a + k + 64)].tolist()
+                    for s in chunk:
+                        if s not in seen:
+                            seen.add(s)
+                            out.append(s)
+                            if len(out) == k:
+                                return out
+                    a += len(chunk)
+    return out
+
+
+def host_query(sig, order, probes, l: int, depth: int, w: int, k: int):
+    """(slots uint32[m][k], counts int32[m]) of the walk on numpy arrays; cells past the count are zero."""
+    m = probes.shape[0]
+    slots = np.zeros((m, k), dtype=np.uint32)
+    counts = np.zeros(m, dtype=np.int32)
+    if m == 0 or sig.shape[0] == 0:
+        return slots, counts
+    lo, hi = level_ranges(sig, order, probes, l, depth, w)
+    lo, hi = lo.transpose(2, 0, 1).tolist(), hi.transpose(2, 0, 1).tolist()
+    for i in range(m):
+        got = _walk(order, lo[i], hi[i], l, depth, k)
+        slots[i, : len(got)] = got
+        counts[i] = len(got)
+    return slots, counts
+
+
+class _HostForest:
+    """The numpy back end: the signature slots and ``order`` in host memory."""
+
+    def __init__(self, kw: int, l: int, depth: int, w: int, dtype):
+        self.kw, self.l, self.depth, self.w = kw, l, depth, w
+        self.dtype = np.dtype(dtype)
+        self.sig = np.empty((0, kw), dtype=self.dtype)
+        self._order = np.empty((l, 0), dtype=np.uint32)
+
+    @property
+    def n(self) -> int:
+        return self.sig.shape[0]
+
+    def widen(self) -> None:
+        self.sig, self.dtype = self.sig.astype(np.uint64), np.dtype(np.uint64)
+
+    def append(self, rows: np.ndarray) -> None:
+        self.sig = np.concatenate([self.sig, rows])
+
+    def build(self) -> None:
+        self._order = tree_order(self.sig, self.l, self.depth * self.w)
+
+    def query(self, probes: np.ndarray, k: int):
+        return host_query(self.sig, self._order, probes, self.l, self.depth, self.w, k)
+
+    def matrix(self) -> np.ndarray:
+        return self.sig
+
+    def row(self, slot: int) -> np.ndarray:
+        return self.sig[slot]
+
+    def order(self) -> np.ndarray:
+        return self._order
+
+
+class _DeviceForest:
+    """The device back end: a ``[capacity, kw]`` signature matrix that grows by doubling and ``order u32[l][n]``, resident on one
+    MI355X.  ``order`` costs ``4 * l * n`` bytes; no copy of the leading words is kept beside it."""
+
+    def __init__(self, ctx, kw: int, l: int, depth: int, w: int, dtype):
+        self.ctx, self.kw, self.l, self.depth, self.w = ctx, kw, l, depth, w
+        self.dtype = np.dtype(dtype)
+        self.n = 0
+        self.capacity = 0
+        self.d_sig = self.d_order = None
+
+    @property
+    def code(self) -> int:
+        return _native.MHX_U32 if self.dtype == np.uint32 else _native.MHX_U64
+
+    @property
+    def row_bytes(self) -> int:
+        return self.kw * self.dtype.itemsize
+
+    def widen(self) -> None:
+        """uint32 -> uint64 once; ``order`` stays valid (widening does not change how rows compare)."""
+        host = self.matrix().astype(np.uint64)
+        grown = self.ctx.alloc(max(self.capacity, 1) * self.kw * 8)
+        if self.n:
+            grown.upload(host)
+        self.ctx.synchronize()
+        self.d_sig, self.dtype = grown, np.dtype(np.uint64)
+
+    def append(self, rows: np.ndarray) -> None:
+        m = rows.shape[0]
+        if (self.n + m) >> 32:
+            raise ValueError("an index holds fewer than 2^32 rows")
+        if self.n + m > self.capacity:
+            cap = max(self.n + m, 2 * self.capacity, 1024)
+            grown = self.ctx.alloc(cap * self.row_bytes)
+            if self.n:
+                self.ctx.copy_dev(grown.ptr, self.d_sig.ptr, self.n * self.row_bytes)
+            self.ctx.synchronize()
+            self.d_sig, self.capacity = grown, cap
+        self.d_sig.upload(rows, offset=self.n * self.row_bytes)
+        self.n += m
+
+    def build(self) -> None:
+        order = self.ctx.alloc(max(1, self.l * self.n * 4))
+        if self.n:
+            self.ctx.lsh_forest_build_dev(self.d_sig.ptr, self.code, self.n, self.kw, self.l, self.depth * self.w, order.ptr)
+        self.ctx.synchronize()
+        self.d_order = order
+
+    def query(self, probes: np.ndarray, k: int):
+        m = probes.shape[0]
+        if m == 0 or self.n == 0:
+            return np.zeros((m, k), dtype=np.uint32), np.zeros(m, dtype=np.int32)
+        if self.l * min(2 * k - 1, self.n) > MAX_CANDIDATES:  # more candidates per probe than the kernel stages: the host walk
+            return host_query(self.matrix(), self.order(), probes, self.l, self.depth, self.w, k)
+        d_q = self.ctx.to_device(np.ascontiguousarray(probes, dtype=self.dtype))
+        d_slots = self.ctx.alloc(m * k * 4)
+        d_counts = self.ctx.alloc(m * 4)
+        self.ctx.lsh_forest_query_dev(self.d_sig.ptr, self.code, self.n, self.kw, self.l, self.depth * self.w, self.w, self.d_order.ptr,
+                                      d_q.ptr, m, k, d_slots.ptr, d_counts.ptr)
+        self.ctx.synchronize()
+        return d_slots.download((m, k), np.uint32), d_counts.download((m,), np.int32)
+
+    def matrix(self) -> np.ndarray:
+        if self.n == 0:
+            return np.empty((0, self.kw), dtype=self.dtype)
+        return self.d_sig.download((self.n, self.kw), self.dtype)
+
+    def row(self, slot: int) -> np.ndarray:
+        return self.d_sig.download((self.kw,), self.dtype, offset=slot * self.row_bytes)
+
+    def order(self) -> np.ndarray:
+        if self.n == 0 or self.d_order is None:
+            return np.empty((self.l, 0), dtype=np.uint32)
+        return self.d_order.download((self.l, self.n), np.uint32)
+
+
+class MinHashLSHForest:
+    """The LSH Forest for MinHash, LeanMinHash and WeightedMinHash signatures (ref: datasketch/lshforest.py ``MinHashLSHForest``):
+    approximate top-``k`` queries in Jaccard similarity.  ``num_perm`` and ``l`` mean what they mean there (``l`` trees of depth
+    ``num_perm // l``, the attribute ``k``); ``gpu_mode`` (``'always'`` | ``'detect'`` | ``'disable'``) and ``device`` choose where
+    the index lives.  Added keys are searchable after the next :meth:`index`.  Beyond the reference: :meth:`add_bulk` and
+    :meth:`query_bulk`; answers come in the order the reference's walk takes them."""
+
+    def __init__(self, num_perm: int = 128, l: int = 8, gpu_mode: str = "detect", device: Optional[int] = None) -> None:
+        if l <= 0 or num_perm <= 0:
+            raise ValueError("num_perm and l must be positive")
+        if l > num_perm:
+            raise ValueError("l cannot be greater than num_perm")
+        if gpu_mode not in ("always", "detect", "disable"):
+            raise ValueError("gpu_mode must be 'always', 'detect' or 'disable'")
+        self.l = l
+        self.k = int(num_perm / l)
+        self.hashranges = [(i * self.k, (i + 1) * self.k) for i in range(self.l)]
+        self.gpu_mode, self.device = gpu_mode, device
+        if gpu_mode == "always" and not _native.gpu_available():
+            raise RuntimeError("GPU mode 'always' requested but no MI355X / libmhx.so is available.")
+        self._reset()
+
+    def _reset(self) -> None:
+        self._words = None     # uint64 words per hash value: 1 MinHash, 2 WeightedMinHash (set by the first add)
+        self._backend = None
+        self._slot = {}        # key -> slot
+        self._keys = []        # slot -> key
+        self._pending = []     # rows staged for the next index() (1-D or 2-D arrays of words)
+        self._n_indexed = 0
+
+    # ---------------------------------------------------------------- bookkeeping
+    def _ensure_backend(self, words: int) -> None:
+        if self._words is None:
+            self._words = words
+        elif words != self._words:
+            raise ValueError("Cannot index MinHash and WeightedMinHash signatures together")
+        if self._backend is None:
+            kw = self.l * self.k * words
+            dtype = np.uint32 if words == 1 else np.uint64
+            if lsh_bulk._use_gpu(self.gpu_mode):
+                self._backend = _DeviceForest(_native.context(self.device), kw, self.l, self.k, words, dtype)
+            else:
+                self._backend = _HostForest(kw, self.l, self.k, words, dtype)
+
+    def _bulk_matrix(self, signatures):
+        """(words matrix cut to the columns the trees cover, words per hash value) of an ``[N, K]`` / ``[N, S, 2]`` matrix."""
+        sig = np.asarray(signatures)
+        words = lsh_bulk._words(sig)
+        mat = sig if sig.ndim == 2 and sig.dtype == np.uint32 else lsh_bulk._matrix(sig)
+        if mat.shape[1] < self.k * self.l * words:
+            raise ValueError("The num_perm of MinHash out of range")
+        return mat[:, : self.k * self.l * words], words
+
+    def _pending_matrix(self) -> Optional[np.ndarray]:
+        if not self._pending:
+            return None
+        if len(self._pending) > 1 or self._pending[0].ndim != 2:
+            self._pending = [np.vstack(self._pending)]
+        return self._pending[0]
+
+    def _all_rows(self) -> np.ndarray:
+        """uint64 words of every added key, indexed or not, in slot order."""
+        kw = self.l * self.k * (self._words or 1)
+        parts = [np.empty((0, kw), dtype=np.uint64)]
+        if self._backend is not None:
+            parts.append(self._backend.matrix().astype(np.uint64))
+        if self._pending:
+            parts.append(self._pending_matrix().astype(np.uint64))
+        return np.concatenate(parts)
+
+    # ---------------------------------------------------------------- adding and indexing
+    def add(self, key: Hashable, minhash) -> None:
+        """Add a unique key with the MinHash (or WeightedMinHash, LeanMinHash) of its set; searchable after :meth:`index`."""
+        if len(minhash) < self.k * self.l:
+            raise ValueError("The num_perm of MinHash out of range")
+        if key in self._slot:
+            raise ValueError("The given key has already been added")
+        row, words = _words_of(minhash.hashvalues)
+        self._ensure_backend(words)
+        self._slot[key] = len(self._keys)
+        self._keys.append(key)
+        self._pending.append(row[: self.k * self.l * words])
+
+    def add_bulk(self, keys, signatures) -> None:
+        """``add(key, MinHash(hashvalues=row))`` for every row: ``signatures`` ``[N, K]`` uint32 / uint64, or a WeightedMinHash
+        matrix ``[N, S, 2]`` int64.  A key present already, or twice in ``keys``, raises ``ValueError`` and nothing is added.
+        The values are taken at call time."""
+        mat, words = self._bulk_matrix(signatures)
+        keys = list(keys)
+        if len(keys) != mat.shape[0]:
+            raise ValueError("keys and signatures must have the same length")
+        if len(set(keys)) != len(keys) or not self._slot.keys().isdisjoint(keys):
+            raise ValueError("The given key has already been added")
+        if not keys:
+            return
+        self._ensure_backend(words)
+        self._slot.update(zip(keys, range(len(self._keys), len(self._keys) + len(keys))))
+        self._keys.extend(keys)
+        self._pending.append(np.array(mat))
+
+    def index(self) -> None:
+        """Index all the keys added so far and make them searchable: the staged rows join the signature matrix and every tree's
+        order is rebuilt from all rows."""
+        rows = self._pending_matrix()
+        if rows is None:
+            return
+        backend = self._backend
+        if backend.dtype == np.uint32 and rows.dtype != np.uint32 and rows.size and int(rows.max()) > _U32_MAX:
+            backend.widen()
+        backend.append(np.ascontiguousarray(rows, dtype=backend.dtype))
+        backend.build()
+        self._pending = []
+        self._n_indexed = len(self._keys)
+
+    # ---------------------------------------------------------------- queries
+    def _answers(self, probes: np.ndarray, k: int) -> List[list]:
+        m = probes.shape[0]
+        if self._n_indexed == 0 or m == 0:
+            return [[] for _ in range(m)]
+        backend = self._backend
+        if backend.dtype == np.uint32 and probes.dtype != np.uint32 and probes.size and int(probes.max()) > _U32_MAX:
+            backend.widen()  # a probe value no uint32 row can hold: compare on the full width
+        slots, counts = backend.query(np.ascontiguousarray(probes, dtype=backend.dtype), min(int(k), self._n_indexed))
+        keys = self._keys
+        return [[keys[s] for s in row[:c]] for row, c in zip(slots.tolist(), counts.tolist())]
+
+    def query(self, minhash, k: int) -> list:
+        """The approximate top-``k`` keys (ref: lshforest.py:92-128): at most ``k`` keys, in the order the walk takes them."""
+        if k <= 0:
+            raise ValueError("k must be positive")
+        if len(minhash) < self.k * self.l:
+            raise ValueError("The num_perm of MinHash out of range")
+        row, words = _words_of(minhash.hashvalues)
+        if self._words is not None and words != self._words:
+            return []
+        return self._answers(row[None, : self.k * self.l * words], k)[0]
+
+    def query_bulk(self, signatures, k: int) -> List[list]:
+        """``[query(MinHash(hashvalues=row), k) for row in signatures]`` for an ``[M, K]`` (or ``[M, S, 2]``) matrix."""
+        if k <= 0:
+            raise ValueError("k must be positive")
+        mat, words = self._bulk_matrix(signatures)
+        if self._words is not None and words != self._words:
+            return [[] for _ in range(mat.shape[0])]
+        return self._answers(mat, k)
+
+    def get_minhash_hashvalues(self, key: Hashable) -> np.ndarray:
+        """The hash values the trees hold for ``key`` -- the first ``l * (num_perm // l)`` of its MinHash, as uint64 words."""
+        slot = self._slot.get(key, None)
+        if slot is None:
+            raise KeyError(f"The provided key does not exist in the LSHForest: {key}")
+        if slot < self._n_indexed:
+            return self._backend.row(slot).astype(np.uint64)
+        return np.array(self._pending_matrix()[slot - self._n_indexed], dtype=np.uint64)
+
+    def is_empty(self) -> bool:
+        """True until :meth:`index` has made at least one key searchable."""
+        return self._n_indexed == 0
+
+    def __contains__(self, key: Hashable) -> bool:
+        return key in self._slot
+
+    # ---------------------------------------------------------------- the reference's containers, as views
+    def _tree_keys(self) -> list:
+        """slot -> the ``l`` tree keys (big-endian bytes) of every added key."""
+        tw = self.k * (self._words or 1)
+        big = self._all_rows().astype(">u8")
+        return [[big[s, t * tw : (t + 1) * tw].tobytes() for t in range(self.l)] for s in range(big.shape[0])]
+
+    @property
+    def keys(self) -> dict:
+        """key -> its ``l`` tree keys, for every added key (a copy built on access)."""
+        return dict(zip(self._keys, self._tree_keys()))
+
+    @property
+    def hashtables(self) -> list:
+        """Per tree, tree key -> the keys with it in insertion order, for every added key (a copy built on access)."""
+        tables = [dict() for _ in range(self.l)]
+        for key, hs in zip(self._keys, self._tree_keys()):
+            for table, h in zip(tables, hs):
+                table.setdefault(h, []).append(key)
+        return tables
+
+    @property
+    def sorted_hashtables(self) -> list:
+        """Per tree, the sorted distinct tree keys of the keys the last :meth:`index` made searchable."""
+        indexed = self._tree_keys()[: self._n_indexed]
+        return [sorted({hs[t] for hs in indexed}) for t in range(self.l)]
+
+    # ---------------------------------------------------------------- pickling
+    def __getstate__(self):
+        state = {k: v for k, v in self.__dict__.items() if not k.startswith("_")}
+        state["_words"] = self._words
+        state["_stored"] = list(self._keys)
+        state["_n_indexed"] = self._n_indexed
+        state["_matrix"] = self._all_rows() if self._backend is not None else None
+        state["_dtype"] = self._backend.dtype.str if self._backend is not None else None
+        return state
+
+    def __setstate__(self, state) -> None:
+        stored, mat, words = state.pop("_stored"), state.pop("_matrix"), state.pop("_words")
+        n_indexed, dtype = state.pop("_n_indexed"), state.pop("_dtype")
+        self.__dict__.update(state)
+        self._reset()
+        if words is None:
+            return
+        self._ensure_backend(words)
+        if np.dtype(dtype) == np.uint64 and self._backend.dtype == np.uint32:
+            self._backend.widen()
+        self._slot = dict(zip(stored, range(len(stored))))
+        self._keys = list(stored)
+        if n_indexed:
+            self._pending = [mat[:n_indexed]]
+            self.index()
+            self._n_indexed = n_indexed
+        if n_indexed < len(stored):
+            self._pending = [mat[n_indexed:]]

@@ -521,6 +521,30 @@ MHX_API int mhx_lsh_bands_compact_dev(mhx_ctx *ctx, const uint64_t *d_dig, const
 MHX_API int mhx_rows_compact_dev(mhx_ctx *ctx, const void *d_src, int64_t row_bytes, int64_t n_rows, const uint32_t *d_live_bits,
                                  void *d_dst, int64_t *n_kept);
 
+/* ---- LSH Forest: top-k queries over sorted trees ------------------------------------------ */
+/* The index of datasketch_amd.MinHashLSHForest (ref: datasketch/lshforest.py).  d_sig is a signature matrix [n_sigs][row_words]
+ * of sig_dtype words (a WeightedMinHash row: its (k, t) int64 pairs as 2 words per hash value).  Tree t of l owns the words
+ * [t * tree_words, (t + 1) * tree_words) of a row, tree_words = depth * words per hash value; l * tree_words <= row_words, the
+ * words past that belong to no tree.  l and the depth are below 65536.
+ *
+ * Build: d_order uint32[l][n_sigs] (caller-owned) receives, per tree, the rows ascending by (the tree's words compared
+ * lexicographically as unsigned integers, row) -- the order of the reference's big-endian byte keys, equal keys in row order.
+ * tree_words (uint32) or 2 * tree_words (uint64) stable radix passes over l * n_sigs pairs, whatever the data: rows that are all
+ * identical cost what distinct ones do.  l * n_sigs < 2^32.  n_sigs == 0 writes nothing.  Enqueued on the ctx stream. */
+MHX_API int mhx_lsh_forest_build_dev_typed(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n_sigs, int32_t row_words,
+                                           int32_t l, int32_t tree_words, uint32_t *d_order);
+/* Query: for each of the m rows of d_probes [m][row_words] (same sig_dtype), the reference's walk -- level r = depth .. 1, tree
+ * t = 0 .. l-1, the positions of d_order[t] whose first r hash values (r * w words) equal the probe's, ascending; a row is taken
+ * the first time it is met; stop at k rows.  d_slots uint32[m][k] receives the rows of probe i in that order from i * k on and
+ * d_counts int32[m] how many (<= k); the cells of d_slots past the count are not written.  w: words per hash value (1 or 2),
+ * tree_words a multiple of it.  A probe stages l * min(2k - 1, n_sigs) candidates in LDS: MHX_ERR_INVALID when that exceeds
+ * MHX_LSH_FOREST_MAX_CANDIDATES (k = 1024 at l = 8 fits).  m == 0 writes nothing; n_sigs == 0 writes m zero counts.  Enqueued on
+ * the ctx stream. */
+#define MHX_LSH_FOREST_MAX_CANDIDATES 16384
+MHX_API int mhx_lsh_forest_query_dev_typed(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n_sigs, int32_t row_words,
+                                           int32_t l, int32_t tree_words, int32_t w, const uint32_t *d_order, const void *d_probes,
+                                           int64_t m, int32_t k, uint32_t *d_slots, int32_t *d_counts);
+
 /* ---- Multi-GPU: assemble the signature matrix (RCCL over xGMI) ----------------------------- */
 /* 128-byte RCCL unique id, created on rank 0 and distributed by the caller (env, file, socket). */
 #define MHX_COMM_ID_BYTES 128
