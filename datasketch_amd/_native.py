@@ -939,6 +939,35 @@ class Context:
                                             ctypes.byref(kept)))
         return int(kept.value)
 
+    def lsh_sort_bands_dev(self, d_sig: int, code: int, n: int, k: int, b: int, r: int, d_dig: int, d_rows: int) -> None:
+        """mhx_lsh_sort_bands_dev_typed: the band digests of a resident [n, k] matrix, per band ascending by (digest, row), into
+        digests u64[b][n] and rows u32[b][n]."""
+        check(self.lib.mhx_lsh_sort_bands_dev_typed(self.handle, _vp(d_sig), int(code), int(n), int(k), int(b), int(r), _vp(d_dig),
+                                                    _vp(d_rows)))
+
+    def lsh_query_dev(self, d_dig: int, d_rows: int, n: int, b: int, r: int, d_sig: int, code: int, k: int, probes: np.ndarray,
+                      capacity: Optional[int] = None):
+        """mhx_lsh_query_dev for a host matrix of probes (of the index's dtype) against resident sorted bands and their [n, k]
+        matrix: (offsets int64[m + 1], rows int64[...]), the index rows sharing a band with probe i being
+        rows[offsets[i]:offsets[i + 1]], ascending.  ``capacity`` is the first guess of the number of (probe, row) pairs; a
+        larger answer costs one more call."""
+        m = probes.shape[0]
+        d_q = self.to_device(probes)
+        cap = int(capacity) if capacity is not None else max(4 * m, 1 << 16)
+        while True:
+            d_pairs = self.alloc(cap * 16)
+            found = _i64(0)
+            check(self.lib.mhx_lsh_query_dev(self.handle, _vp(d_dig), _vp(d_rows), int(n), int(b), int(r), _vp(d_q.ptr), _vp(d_sig),
+                                             int(code), int(k), m, _vp(d_pairs.ptr), cap, ctypes.byref(found)))
+            if found.value <= cap:
+                break
+            cap = int(found.value)
+        self.synchronize()
+        pairs = d_pairs.download((found.value, 2), np.int64) if found.value else np.empty((0, 2), dtype=np.int64)
+        offsets = np.zeros(m + 1, dtype=np.int64)
+        np.cumsum(np.bincount(pairs[:, 0], minlength=m), out=offsets[1:])
+        return offsets, np.ascontiguousarray(pairs[:, 1])
+
     def lsh_forest_build_dev(self, d_sig: int, sig_dtype: int, n: int, row_words: int, l: int, tree_words: int, d_order: int) -> None:
         """mhx_lsh_forest_build_dev_typed: per tree, the rows ascending by (the tree's words, row) into order u32[l][n]; enqueued."""
         check(self.lib.mhx_lsh_forest_build_dev_typed(self.handle, _vp(d_sig), int(sig_dtype), int(n), int(row_words), int(l),

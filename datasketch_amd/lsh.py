@@ -35,11 +35,9 @@ import numpy as np
 from scipy.integrate import quad
 
 from datasketch_amd import _native, lsh_bulk
+from datasketch_amd._index_rows import DeviceRows, HostRows
 
 __all__ = ["MinHashLSH", "MinHashLSHInsertionSession", "MinHashLSHDeletionSession"]
-
-_U32_MAX = 0xFFFFFFFF
-
 
 def _weighted_error(threshold: float, b: int, r: int, fp_weight: float, fn_weight: float) -> float:
     """Weighted false positive + false negative probability of ``b`` bands of ``r`` rows at ``threshold``: a pair of
@@ -63,54 +61,38 @@ def _optimal_param(threshold: float, num_perm: int, fp_weight: float, fn_weight:
     return opt
 
 
-def _words_of(hashvalues):
-    """(uint64 words of one signature, words per hash value): a MinHash's ``[h]`` values, or a WeightedMinHash's ``[h, 2]``
-    int64 ``(k, t)`` pairs viewed as ``2h`` words -- the reference's band key bytes are the big-endian bytes of those words."""
-    a = np.asarray(hashvalues)
-    if a.ndim == 2:
-        return np.ascontiguousarray(a, dtype=np.int64).view(np.uint64).reshape(-1).copy(), 2
-    return np.array(a, dtype=np.uint64), 1
-
-
 def _starts(counts: np.ndarray) -> np.ndarray:
     out = np.zeros(counts.size + 1, dtype=np.int64)
     np.cumsum(counts, out=out[1:])
     return out
 
 
-class _HostBands:
+class _HostBands(HostRows):
     """The numpy back end: the signature slots and the sorted bands in host memory.  A merge is a stable ``argsort`` by digest
     of A||B, compaction a mask plus a remap, a query ``searchsorted`` per band with the band's words compared."""
 
     def __init__(self, k: int, b: int, r: int, dtype):
-        self.k, self.b, self.r = k, b, r
-        self.dtype = np.dtype(dtype)
-        self.sig = np.empty((0, k), dtype=self.dtype)
+        super().__init__(k, dtype)
+        self.b, self.r = b, r
         self.dig = np.empty((b, 0), dtype=np.uint64)
         self.rows = np.empty((b, 0), dtype=np.uint32)
 
-    @property
-    def n(self) -> int:
-        return self.sig.shape[0]
-
-    def widen(self) -> None:
-        self.sig, self.dtype = self.sig.astype(np.uint64), np.dtype(np.uint64)
-
-    def _merge(self, sig: np.ndarray, dig_b: np.ndarray, rows_b: np.ndarray) -> None:
+    def _merge_bands(self, dig_b: np.ndarray, rows_b: np.ndarray) -> None:
+        """Merge in the sorted bands of rows that take the slots after the last used one."""
         dig = np.concatenate([self.dig, dig_b], axis=1)
         order = np.argsort(dig, axis=1, kind="stable")
         rows = np.concatenate([self.rows, rows_b + np.uint32(self.n)], axis=1)
         self.dig = np.take_along_axis(dig, order, axis=1)
         self.rows = np.take_along_axis(rows, order, axis=1)
-        self.sig = np.concatenate([self.sig, sig])
 
     def append(self, sig: np.ndarray) -> None:
         dig = lsh_bulk.band_digests(sig, self.b, self.r, gpu_mode="disable").T
-        rows = np.broadcast_to(np.arange(sig.shape[0], dtype=np.uint32), dig.shape)
-        self._merge(sig, dig, rows)
+        self._merge_bands(dig, np.broadcast_to(np.arange(sig.shape[0], dtype=np.uint32), dig.shape))
+        self.upload(sig)
 
     def merge_from(self, other: "_HostBands") -> None:
-        self._merge(other.sig.astype(self.dtype), other.dig, other.rows)
+        self._merge_bands(other.dig, other.rows)
+        self.copy_from(other)
 
     def compact(self, live: np.ndarray) -> None:
         n_live = int(np.count_nonzero(live))
@@ -138,9 +120,6 @@ class _HostBands:
             found_s.append(slot[same])
         return _pairs_to_lists(found_p, found_s, m, self.n)
 
-    def matrix(self) -> np.ndarray:
-        return self.sig
-
     def bands(self):
         return self.dig, self.rows
 
@@ -155,45 +134,14 @@ def _pairs_to_lists(found_p, found_s, m: int, n: int):
     return offsets, code % max(n, 1)
 
 
-class _DeviceBands:
-    """The device back end: a ``[capacity, K]`` signature matrix that grows by doubling and the sorted bands
-    ``digests u64[b][n]`` / ``rows u32[b][n]`` (the layout of ``mhx_lsh_sort_bands_dev_typed``), all resident on one MI355X."""
+class _DeviceBands(DeviceRows):
+    """The device back end: the ``[capacity, K]`` signature matrix and the sorted bands ``digests u64[b][n]`` / ``rows u32[b][n]``
+    (the layout of ``mhx_lsh_sort_bands_dev_typed``), all resident on one MI355X."""
 
     def __init__(self, ctx, k: int, b: int, r: int, dtype):
-        self.ctx, self.k, self.b, self.r = ctx, k, b, r
-        self.dtype = np.dtype(dtype)
-        self.n = 0
-        self.capacity = 0
-        self.d_sig = None
+        super().__init__(ctx, k, dtype)
+        self.b, self.r = b, r
         self.d_dig = self.d_rows = None
-
-    @property
-    def code(self) -> int:
-        return _native.MHX_U32 if self.dtype == np.uint32 else _native.MHX_U64
-
-    @property
-    def row_bytes(self) -> int:
-        return self.k * self.dtype.itemsize
-
-    def _grow(self, need: int) -> None:
-        if need <= self.capacity:
-            return
-        cap = max(need, 2 * self.capacity, 1024)
-        grown = self.ctx.alloc(cap * self.row_bytes)
-        if self.n:
-            self.ctx.copy_dev(grown.ptr, self.d_sig.ptr, self.n * self.row_bytes)
-        self.ctx.synchronize()
-        self.d_sig, self.capacity = grown, cap
-
-    def widen(self) -> None:
-        """uint32 -> uint64 once (the bands stay valid: a uint32 matrix's band digests are those of the widened one).  The wider
-        matrix is allocated and filled before anything is reassigned, so a failure leaves the uint32 index as it was."""
-        host = self.matrix().astype(np.uint64)
-        grown = self.ctx.alloc(max(self.capacity, 1) * self.k * 8)
-        if self.n:
-            grown.upload(host)
-        self.ctx.synchronize()
-        self.d_sig, self.dtype = grown, np.dtype(np.uint64)
 
     def _merge_bands(self, d_dig_b: int, d_rows_b: int, m: int):
         """New buffers holding this index's bands merged with the sorted bands of m rows that take slots n .. n+m-1."""
@@ -207,30 +155,24 @@ class _DeviceBands:
         return dig, rows
 
     def append(self, sig: np.ndarray) -> None:
-        m = sig.shape[0]
-        if (self.n + m) >> 32:
-            raise ValueError("an index holds fewer than 2^32 rows")
-        self._grow(self.n + m)
-        at = self.n * self.row_bytes
-        self.d_sig.upload(sig, offset=at)
+        first, m = self.n, sig.shape[0]
+        self.upload(sig)
+        self.n = first  # the rows count once their bands are merged in: a failure below leaves the index as it was
         d_dig = self.ctx.alloc(m * self.b * 8)
         d_rows = self.ctx.alloc(m * self.b * 4)
-        _native.check(self.ctx.lib.mhx_lsh_sort_bands_dev_typed(self.ctx.handle, self.d_sig.ptr + at, self.code, m, self.k, self.b,
-                                                                self.r, d_dig.ptr, d_rows.ptr))
-        dig, rows = self._merge_bands(d_dig.ptr, d_rows.ptr, m) if self.n else (d_dig, d_rows)
+        self.ctx.lsh_sort_bands_dev(self.d_sig.ptr + first * self.row_bytes, self.code, m, self.kw, self.b, self.r, d_dig.ptr, d_rows.ptr)
+        dig, rows = self._merge_bands(d_dig.ptr, d_rows.ptr, m) if first else (d_dig, d_rows)
         self.ctx.synchronize()
-        self.d_dig, self.d_rows, self.n = dig, rows, self.n + m
+        self.d_dig, self.d_rows, self.n = dig, rows, first + m
 
     def merge_from(self, other: "_DeviceBands") -> None:
         """The other index's rows copied device to device after this one's, its bands merged in with that row offset."""
-        m = other.n
-        if (self.n + m) >> 32:
-            raise ValueError("an index holds fewer than 2^32 rows")
-        self._grow(self.n + m)
-        self.ctx.copy_dev(self.d_sig.ptr + self.n * self.row_bytes, other.d_sig.ptr, m * self.row_bytes)
+        first, m = self.n, other.n
+        self.copy_from(other)
+        self.n = first  # as in append
         dig, rows = self._merge_bands(other.d_dig.ptr, other.d_rows.ptr, m)
         self.ctx.synchronize()
-        self.d_dig, self.d_rows, self.n = dig, rows, self.n + m
+        self.d_dig, self.d_rows, self.n = dig, rows, first + m
 
     def compact(self, live: np.ndarray) -> None:
         n_live = int(np.count_nonzero(live))
@@ -249,33 +191,12 @@ class _DeviceBands:
         self.d_sig, self.capacity, self.d_dig, self.d_rows, self.n = sig, cap, dig, rows, n_live
 
     def query(self, probes: np.ndarray, capacity: Optional[int] = None):
-        import ctypes
-
-        m = probes.shape[0]
-        offsets = np.zeros(m + 1, dtype=np.int64)
-        if m == 0 or self.n == 0:
-            return offsets, np.empty(0, dtype=np.int64)
-        if self.dtype == np.uint32 and probes.dtype != np.uint32 and probes.size and int(probes.max()) > _U32_MAX:
+        if probes.shape[0] == 0 or self.n == 0:
+            return np.zeros(probes.shape[0] + 1, dtype=np.int64), np.empty(0, dtype=np.int64)
+        if lsh_bulk.needs_widening(self.dtype, probes):
             self.widen()  # a probe value no uint32 row can hold: compare on the full width
-        d_q = self.ctx.to_device(np.ascontiguousarray(probes, dtype=self.dtype))
-        cap = int(capacity) if capacity is not None else max(4 * m, 1 << 16)
-        while True:
-            d_pairs = self.ctx.alloc(cap * 16)
-            found = ctypes.c_int64(0)
-            _native.check(self.ctx.lib.mhx_lsh_query_dev(self.ctx.handle, self.d_dig.ptr, self.d_rows.ptr, self.n, self.b, self.r, d_q.ptr,
-                                                         self.d_sig.ptr, self.code, self.k, m, d_pairs.ptr, cap, ctypes.byref(found)))
-            if found.value <= cap:
-                break
-            cap = int(found.value)
-        self.ctx.synchronize()
-        pairs = d_pairs.download((found.value, 2), np.int64) if found.value else np.empty((0, 2), dtype=np.int64)
-        np.cumsum(np.bincount(pairs[:, 0], minlength=m), out=offsets[1:])
-        return offsets, np.ascontiguousarray(pairs[:, 1])
-
-    def matrix(self) -> np.ndarray:
-        if self.n == 0:
-            return np.empty((0, self.k), dtype=self.dtype)
-        return self.d_sig.download((self.n, self.k), self.dtype)
+        return self.ctx.lsh_query_dev(self.d_dig.ptr, self.d_rows.ptr, self.n, self.b, self.r, self.d_sig.ptr, self.code, self.kw,
+                                      np.ascontiguousarray(probes, dtype=self.dtype), capacity)
 
     def bands(self):
         if self.n == 0:
@@ -299,8 +220,7 @@ class MinHashLSH:
         storage_config = storage_config if storage_config else {"type": "dict"}
         if storage_config.get("type") != "dict":
             raise ValueError("datasketch_amd.MinHashLSH supports only the in-memory storage: storage_config None or {'type': 'dict'}")
-        if gpu_mode not in ("always", "detect", "disable"):
-            raise ValueError("gpu_mode must be 'always', 'detect' or 'disable'")
+        lsh_bulk._check_gpu_mode(gpu_mode)
         self._buffer_size = 50000
         if threshold > 1.0 or threshold < 0.0:
             raise ValueError("threshold must be in [0.0, 1.0]")
@@ -361,10 +281,7 @@ class MinHashLSH:
         return lsh_bulk._use_gpu(self.gpu_mode)
 
     def _ensure_backend(self, words: int) -> None:
-        if self._words is None:
-            self._words = words
-        elif words != self._words:
-            raise ValueError("Cannot index MinHash and WeightedMinHash signatures together")
+        self._words = lsh_bulk._same_words(self._words, words)
         if self._backend is None:
             k, r = self.h * words, self.r * words
             dtype = np.uint32 if words == 1 else np.uint64
@@ -422,11 +339,10 @@ class MinHashLSH:
     def _upload_pending(self) -> None:
         if not self._pending:
             return
-        rows = self._pending[0] if len(self._pending) == 1 and self._pending[0].ndim == 2 else np.vstack(self._pending)
+        rows = lsh_bulk._stacked(self._pending)
         backend = self._backend
-        if backend.dtype == np.uint32 and rows.dtype != np.uint32:
-            if rows.size and int(rows.max()) > _U32_MAX:
-                backend.widen()
+        if lsh_bulk.needs_widening(backend.dtype, rows):
+            backend.widen()
         backend.append(np.ascontiguousarray(rows, dtype=backend.dtype))
         self._pending = []
         self._n_flushed = self._n_slots
@@ -504,7 +420,7 @@ class MinHashLSH:
             key = pickle.dumps(key)
         if check_duplication and key in self._kid:
             raise ValueError("The given key already exists")
-        row, words = _words_of(minhash.hashvalues)
+        row, words = lsh_bulk._words_of(minhash.hashvalues)
         self._ensure_backend(words)
         self._stage([key], row, fresh=key not in self._kid)
 
@@ -512,9 +428,7 @@ class MinHashLSH:
         """``insert(key, MinHash(hashvalues=row))`` for every row: ``signatures`` ``[N, K]`` uint32 / uint64, or a
         WeightedMinHash matrix ``[N, S, 2]`` int64.  With ``check_duplication`` a key present already, or twice in ``keys``,
         raises ``ValueError`` and nothing is inserted."""
-        sig = np.asarray(signatures)
-        words = lsh_bulk._words(sig)
-        mat = np.ascontiguousarray(sig) if sig.ndim == 2 and sig.dtype == np.uint32 else lsh_bulk._matrix(sig)
+        mat, words = lsh_bulk._words_matrix(signatures)
         n, k = mat.shape
         if k != self.h * words:
             raise ValueError("Expecting minhash with length %d, got %d" % (self.h, k // words))
@@ -530,7 +444,7 @@ class MinHashLSH:
         if n == 0:
             return
         self._ensure_backend(words)
-        self._stage(keys, mat, fresh, borrowed=np.shares_memory(mat, sig))
+        self._stage(keys, mat, fresh, borrowed=np.shares_memory(mat, np.asarray(signatures)))
 
     def _stage_stored(self, stored_keys: list, mat: np.ndarray, words: int) -> None:
         """Rows whose keys are stored keys already (pickled where prepickle is on): unpickling, merging through the host."""
@@ -572,7 +486,7 @@ class MinHashLSH:
         for m in minhashes:
             if len(m) != self.h:
                 raise ValueError("Expecting minhash with length %d, got %d" % (self.h, len(m)))
-            row, words = _words_of(m.hashvalues)
+            row, words = lsh_bulk._words_of(m.hashvalues)
             if self._words is not None and words != self._words:
                 return None
             rows.append(row)
@@ -604,9 +518,7 @@ class MinHashLSH:
 
     def query_bulk(self, signatures) -> List[list]:
         """``[query(MinHash(hashvalues=row)) for row in signatures]`` for an ``[M, K]`` (or ``[M, S, 2]``) matrix."""
-        sig = np.asarray(signatures)
-        words = lsh_bulk._words(sig)
-        mat = np.ascontiguousarray(sig) if sig.ndim == 2 and sig.dtype == np.uint32 else lsh_bulk._matrix(sig)
+        mat, words = lsh_bulk._words_matrix(signatures)
         m, k = mat.shape
         if k != self.h * words:
             raise ValueError("Expecting minhash with length %d, got %d" % (self.h, k // words))

@@ -35,6 +35,7 @@ from typing import Hashable, Iterable, List, Optional, Sequence
 import numpy as np
 
 from datasketch_amd import _native
+from datasketch_amd._index_rows import DeviceRows
 
 _FNV_OFFSET = np.uint64(0xCBF29CE484222325)
 _FNV_PRIME = np.uint64(0x100000001B3)
@@ -74,6 +75,46 @@ def _matrix(signatures) -> np.ndarray:
 def _words(signatures) -> int:
     """uint64 words per hash value: 2 for a WeightedMinHash matrix ``[N, S, 2]``, else 1."""
     return 2 if np.ndim(signatures) == 3 else 1
+
+
+def _words_of(hashvalues):
+    """(uint64 words of one signature, words per hash value): a MinHash's ``[h]`` values, or a WeightedMinHash's ``[h, 2]``
+    int64 ``(k, t)`` pairs viewed as ``2h`` words -- the reference's band key bytes are the big-endian bytes of those words."""
+    a = np.asarray(hashvalues)
+    if a.ndim == 2:
+        return np.ascontiguousarray(a, dtype=np.int64).view(np.uint64).reshape(-1).copy(), 2
+    return np.array(a, dtype=np.uint64), 1
+
+
+def _words_matrix(signatures):
+    """(words matrix, words per hash value) of a bulk argument ``[N, K]`` / ``[N, S, 2]``: :func:`_matrix`, except that a uint32
+    matrix is kept as it is (the indexes hold uint32 rows while every value fits)."""
+    sig = np.asarray(signatures)
+    mat = np.ascontiguousarray(sig) if sig.ndim == 2 and sig.dtype == np.uint32 else _matrix(sig)
+    return mat, _words(sig)
+
+
+def needs_widening(dtype, rows: np.ndarray) -> bool:
+    """Whether an index holding rows of ``dtype`` has to become uint64 before it stores ``rows`` or is compared with them: it is
+    uint32 and some value of ``rows`` is one no uint32 row can hold."""
+    return dtype == np.uint32 and rows.dtype != np.uint32 and rows.size > 0 and int(rows.max()) > 0xFFFFFFFF
+
+
+def _check_gpu_mode(gpu_mode: str) -> None:
+    if gpu_mode not in ("always", "detect", "disable"):
+        raise ValueError("gpu_mode must be 'always', 'detect' or 'disable'")
+
+
+def _same_words(have: Optional[int], words: int) -> int:
+    """The words per hash value of an index that holds ``have`` (``None``: nothing yet) and now takes rows of ``words``."""
+    if have is not None and words != have:
+        raise ValueError("Cannot index MinHash and WeightedMinHash signatures together")
+    return words
+
+
+def _stacked(pending: list) -> np.ndarray:
+    """The staged rows (1-D or 2-D arrays of words) as one matrix; a single staged matrix is returned as it is."""
+    return pending[0] if len(pending) == 1 and pending[0].ndim == 2 else np.vstack(pending)
 
 
 def _check_params(k: int, b: int, r: int) -> None:
@@ -312,19 +353,23 @@ class SortedBandsIndex:
         if not _native.gpu_available():
             raise RuntimeError("SortedBandsIndex needs an MI355X / libmhx.so")
         self.ctx = _native.context(device)
-        self.n, self.k = sig.shape
+        self.k = sig.shape[1]
         self.b, self.r = int(b), int(r)
         self.dtype = sig.dtype
-        self._code = _native.MHX_U32 if sig.dtype == np.uint32 else _native.MHX_U64
-        self._d_sig = self.ctx.to_device(sig)
+        self._rows = DeviceRows(self.ctx, self.k, sig.dtype)
+        self._rows.upload(sig)
         self._sort()
+
+    @property
+    def n(self) -> int:
+        return self._rows.n
 
     def _sort(self) -> None:
         self._d_dig = self.ctx.alloc(max(1, self.n * self.b * 8))
         self._d_rows = self.ctx.alloc(max(1, self.n * self.b * 4))
         if self.n:
-            _native.check(self.ctx.lib.mhx_lsh_sort_bands_dev_typed(self.ctx.handle, self._d_sig.ptr, self._code, self.n, self.k,
-                                                                    self.b, self.r, self._d_dig.ptr, self._d_rows.ptr))
+            self.ctx.lsh_sort_bands_dev(self._rows.d_sig.ptr, self._rows.code, self.n, self.k, self.b, self.r, self._d_dig.ptr,
+                                        self._d_rows.ptr)
 
     def _as_index_dtype(self, sig: np.ndarray) -> np.ndarray:
         """``sig`` in the index's signature type; a wider matrix must fit (a wrapped value would match band keys the
@@ -340,7 +385,8 @@ class SortedBandsIndex:
     def extend(self, signatures) -> range:
         """Add rows (what ``MinHashLSH.insert`` does key by key, ref: datasketch/lsh.py:326-347) and return their row
         numbers ``range(old N, new N)``.  The matrix grows on the device (the rows already there are not uploaded
-        again) and the bands are sorted afresh -- 40 ms per 10^6 rows, so add in batches."""
+        again; the first build allocates room for its own rows, 1024 at least, and the capacity at least doubles whenever it runs
+        out, so most calls copy nothing) and the bands are sorted afresh -- 40 ms per 10^6 rows, so add in batches."""
         more = np.asarray(signatures)
         if more.ndim != 2 or more.shape[1] != self.k:
             raise ValueError("Expecting minhash with length %d, got %d" % (self.k, more.shape[-1]))
@@ -348,46 +394,22 @@ class SortedBandsIndex:
         first, m = self.n, more.shape[0]
         if m == 0:
             return range(first, first)
-        if (first + m) >> 32:
-            raise ValueError("a SortedBandsIndex holds fewer than 2^32 rows")
-        row_bytes = self.k * self.dtype.itemsize
-        grown = self.ctx.alloc((first + m) * row_bytes)
-        if first:
-            self.ctx.copy_dev(grown.ptr, self._d_sig.ptr, first * row_bytes)
-        grown.upload(more, offset=first * row_bytes)
+        self._rows.upload(more)
         self.ctx.synchronize()
-        self._d_sig, self.n = grown, first + m
         self._sort()
         return range(first, first + m)
 
     def query(self, signatures, capacity: Optional[int] = None):
         """``(offsets int64[M+1], rows int64[...])``: the index rows sharing at least one band key with probe
         ``i`` are ``rows[offsets[i]:offsets[i+1]]``, ascending."""
-        import ctypes
-
         q = np.asarray(signatures)
         if q.ndim != 2 or q.shape[1] != self.k:
             raise ValueError("Expecting minhash with length %d, got %d" % (self.k, q.shape[-1]))
         q = self._as_index_dtype(q)
-        m = q.shape[0]
-        offsets = np.zeros(m + 1, dtype=np.int64)
-        if m == 0 or self.n == 0:
-            return offsets, np.empty(0, dtype=np.int64)
-        d_q = self.ctx.to_device(q)
-        cap = int(capacity) if capacity is not None else max(4 * m, 1 << 16)
-        while True:
-            d_pairs = self.ctx.alloc(cap * 16)
-            found = ctypes.c_int64(0)
-            _native.check(self.ctx.lib.mhx_lsh_query_dev(self.ctx.handle, self._d_dig.ptr, self._d_rows.ptr, self.n, self.b, self.r,
-                                                         d_q.ptr, self._d_sig.ptr, self._code, self.k, m, d_pairs.ptr, cap,
-                                                         ctypes.byref(found)))
-            if found.value <= cap:
-                break
-            cap = int(found.value)
-        self.ctx.synchronize()
-        pairs = d_pairs.download((found.value, 2), np.int64) if found.value else np.empty((0, 2), dtype=np.int64)
-        np.cumsum(np.bincount(pairs[:, 0], minlength=m), out=offsets[1:])
-        return offsets, np.ascontiguousarray(pairs[:, 1])
+        if q.shape[0] == 0 or self.n == 0:
+            return np.zeros(q.shape[0] + 1, dtype=np.int64), np.empty(0, dtype=np.int64)
+        return self.ctx.lsh_query_dev(self._d_dig.ptr, self._d_rows.ptr, self.n, self.b, self.r, self._rows.d_sig.ptr, self._rows.code,
+                                      self.k, q, capacity)
 
 
 def sorted_bands(signatures, b: int, r: int, gpu_mode: str = "detect"):

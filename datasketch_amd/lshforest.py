@@ -28,11 +28,10 @@ from typing import Hashable, List, Optional
 import numpy as np
 
 from datasketch_amd import _native, lsh_bulk
-from datasketch_amd.lsh import _words_of
+from datasketch_amd._index_rows import DeviceRows, HostRows
 
 __all__ = ["MinHashLSHForest"]
 
-_U32_MAX = 0xFFFFFFFF
 MAX_CANDIDATES = 16384  # MHX_LSH_FOREST_MAX_CANDIDATES: l * min(2k - 1, n) candidates per probe the query kernel stages in LDS
 
 
@@ -119,24 +118,13 @@ def host_query(sig, order, probes, l: int, depth: int, w: int, k: int):
     return slots, counts
 
 
-class _HostForest:
+class _HostForest(HostRows):
     """The numpy back end: the signature slots and ``order`` in host memory."""
 
     def __init__(self, kw: int, l: int, depth: int, w: int, dtype):
-        self.kw, self.l, self.depth, self.w = kw, l, depth, w
-        self.dtype = np.dtype(dtype)
-        self.sig = np.empty((0, kw), dtype=self.dtype)
+        super().__init__(kw, dtype)
+        self.l, self.depth, self.w = l, depth, w
         self._order = np.empty((l, 0), dtype=np.uint32)
-
-    @property
-    def n(self) -> int:
-        return self.sig.shape[0]
-
-    def widen(self) -> None:
-        self.sig, self.dtype = self.sig.astype(np.uint64), np.dtype(np.uint64)
-
-    def append(self, rows: np.ndarray) -> None:
-        self.sig = np.concatenate([self.sig, rows])
 
     def build(self) -> None:
         self._order = tree_order(self.sig, self.l, self.depth * self.w)
@@ -144,57 +132,18 @@ class _HostForest:
     def query(self, probes: np.ndarray, k: int):
         return host_query(self.sig, self._order, probes, self.l, self.depth, self.w, k)
 
-    def matrix(self) -> np.ndarray:
-        return self.sig
-
-    def row(self, slot: int) -> np.ndarray:
-        return self.sig[slot]
-
     def order(self) -> np.ndarray:
         return self._order
 
 
-class _DeviceForest:
-    """The device back end: a ``[capacity, kw]`` signature matrix that grows by doubling and ``order u32[l][n]``, resident on one
-    MI355X.  ``order`` costs ``4 * l * n`` bytes; no copy of the leading words is kept beside it."""
+class _DeviceForest(DeviceRows):
+    """The device back end: the ``[capacity, kw]`` signature matrix and ``order u32[l][n]``, resident on one MI355X.  ``order``
+    costs ``4 * l * n`` bytes; no copy of the leading words is kept beside it."""
 
     def __init__(self, ctx, kw: int, l: int, depth: int, w: int, dtype):
-        self.ctx, self.kw, self.l, self.depth, self.w = ctx, kw, l, depth, w
-        self.dtype = np.dtype(dtype)
-        self.n = 0
-        self.capacity = 0
-        self.d_sig = self.d_order = None
-
-    @property
-    def code(self) -> int:
-        return _native.MHX_U32 if self.dtype == np.uint32 else _native.MHX_U64
-
-    @property
-    def row_bytes(self) -> int:
-        return self.kw * self.dtype.itemsize
-
-    def widen(self) -> None:
-        """uint32 -> uint64 once; ``order`` stays valid (widening does not change how rows compare)."""
-        host = self.matrix().astype(np.uint64)
-        grown = self.ctx.alloc(max(self.capacity, 1) * self.kw * 8)
-        if self.n:
-            grown.upload(host)
-        self.ctx.synchronize()
-        self.d_sig, self.dtype = grown, np.dtype(np.uint64)
-
-    def append(self, rows: np.ndarray) -> None:
-        m = rows.shape[0]
-        if (self.n + m) >> 32:
-            raise ValueError("an index holds fewer than 2^32 rows")
-        if self.n + m > self.capacity:
-            cap = max(self.n + m, 2 * self.capacity, 1024)
-            grown = self.ctx.alloc(cap * self.row_bytes)
-            if self.n:
-                self.ctx.copy_dev(grown.ptr, self.d_sig.ptr, self.n * self.row_bytes)
-            self.ctx.synchronize()
-            self.d_sig, self.capacity = grown, cap
-        self.d_sig.upload(rows, offset=self.n * self.row_bytes)
-        self.n += m
+        super().__init__(ctx, kw, dtype)
+        self.l, self.depth, self.w = l, depth, w
+        self.d_order = None
 
     def build(self) -> None:
         order = self.ctx.alloc(max(1, self.l * self.n * 4))
@@ -217,14 +166,6 @@ class _DeviceForest:
         self.ctx.synchronize()
         return d_slots.download((m, k), np.uint32), d_counts.download((m,), np.int32)
 
-    def matrix(self) -> np.ndarray:
-        if self.n == 0:
-            return np.empty((0, self.kw), dtype=self.dtype)
-        return self.d_sig.download((self.n, self.kw), self.dtype)
-
-    def row(self, slot: int) -> np.ndarray:
-        return self.d_sig.download((self.kw,), self.dtype, offset=slot * self.row_bytes)
-
     def order(self) -> np.ndarray:
         if self.n == 0 or self.d_order is None:
             return np.empty((self.l, 0), dtype=np.uint32)
@@ -243,8 +184,7 @@ class MinHashLSHForest:
             raise ValueError("num_perm and l must be positive")
         if l > num_perm:
             raise ValueError("l cannot be greater than num_perm")
-        if gpu_mode not in ("always", "detect", "disable"):
-            raise ValueError("gpu_mode must be 'always', 'detect' or 'disable'")
+        lsh_bulk._check_gpu_mode(gpu_mode)
         self.l = l
         self.k = int(num_perm / l)
         self.hashranges = [(i * self.k, (i + 1) * self.k) for i in range(self.l)]
@@ -263,10 +203,7 @@ class MinHashLSHForest:
 
     # ---------------------------------------------------------------- bookkeeping
     def _ensure_backend(self, words: int) -> None:
-        if self._words is None:
-            self._words = words
-        elif words != self._words:
-            raise ValueError("Cannot index MinHash and WeightedMinHash signatures together")
+        self._words = lsh_bulk._same_words(self._words, words)
         if self._backend is None:
             kw = self.l * self.k * words
             dtype = np.uint32 if words == 1 else np.uint64
@@ -277,9 +214,7 @@ class MinHashLSHForest:
 
     def _bulk_matrix(self, signatures):
         """(words matrix cut to the columns the trees cover, words per hash value) of an ``[N, K]`` / ``[N, S, 2]`` matrix."""
-        sig = np.asarray(signatures)
-        words = lsh_bulk._words(sig)
-        mat = sig if sig.ndim == 2 and sig.dtype == np.uint32 else lsh_bulk._matrix(sig)
+        mat, words = lsh_bulk._words_matrix(signatures)
         if mat.shape[1] < self.k * self.l * words:
             raise ValueError("The num_perm of MinHash out of range")
         return mat[:, : self.k * self.l * words], words
@@ -287,8 +222,7 @@ class MinHashLSHForest:
     def _pending_matrix(self) -> Optional[np.ndarray]:
         if not self._pending:
             return None
-        if len(self._pending) > 1 or self._pending[0].ndim != 2:
-            self._pending = [np.vstack(self._pending)]
+        self._pending = [lsh_bulk._stacked(self._pending)]
         return self._pending[0]
 
     def _all_rows(self) -> np.ndarray:
@@ -308,7 +242,7 @@ class MinHashLSHForest:
             raise ValueError("The num_perm of MinHash out of range")
         if key in self._slot:
             raise ValueError("The given key has already been added")
-        row, words = _words_of(minhash.hashvalues)
+        row, words = lsh_bulk._words_of(minhash.hashvalues)
         self._ensure_backend(words)
         self._slot[key] = len(self._keys)
         self._keys.append(key)
@@ -338,9 +272,9 @@ class MinHashLSHForest:
         if rows is None:
             return
         backend = self._backend
-        if backend.dtype == np.uint32 and rows.dtype != np.uint32 and rows.size and int(rows.max()) > _U32_MAX:
+        if lsh_bulk.needs_widening(backend.dtype, rows):
             backend.widen()
-        backend.append(np.ascontiguousarray(rows, dtype=backend.dtype))
+        backend.upload(np.ascontiguousarray(rows, dtype=backend.dtype))
         backend.build()
         self._pending = []
         self._n_indexed = len(self._keys)
@@ -351,7 +285,7 @@ class MinHashLSHForest:
         if self._n_indexed == 0 or m == 0:
             return [[] for _ in range(m)]
         backend = self._backend
-        if backend.dtype == np.uint32 and probes.dtype != np.uint32 and probes.size and int(probes.max()) > _U32_MAX:
+        if lsh_bulk.needs_widening(backend.dtype, probes):
             backend.widen()  # a probe value no uint32 row can hold: compare on the full width
         slots, counts = backend.query(np.ascontiguousarray(probes, dtype=backend.dtype), min(int(k), self._n_indexed))
         keys = self._keys
@@ -363,7 +297,7 @@ class MinHashLSHForest:
             raise ValueError("k must be positive")
         if len(minhash) < self.k * self.l:
             raise ValueError("The num_perm of MinHash out of range")
-        row, words = _words_of(minhash.hashvalues)
+        row, words = lsh_bulk._words_of(minhash.hashvalues)
         if self._words is not None and words != self._words:
             return []
         return self._answers(row[None, : self.k * self.l * words], k)[0]

@@ -107,7 +107,7 @@ class DictModel:
 
 
 def _words(sig_obj_or_row):
-    return L._words_of(sig_obj_or_row)[0]
+    return LB._words_of(sig_obj_or_row)[0]
 
 
 def run_differential(gpu_modes, variant, prepickle, seed=0, n_ops=2000, after_op=None):
