@@ -82,22 +82,22 @@ _PROTOTYPES = {
     "mhx_bbit_pack": [_vp, _vp, _i64, _i32, _i32, _vp],
     "mhx_band_keys_dev": [_vp, _vp, _i64, _i32, _i32, _i32, _vp],
     "mhx_band_keys": [_vp, _vp, _i64, _i32, _i32, _i32, _vp],
-    "mhx_band_digests_dev": [_vp, _vp, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp],
-    "mhx_band_digests": [_vp, _vp, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp],
-    "mhx_lsh_sort_bands_dev": [_vp, _vp, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp],
-    "mhx_lsh_sort_bands": [_vp, _vp, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _vp],
-    "mhx_lsh_sort_digests_dev": [_vp, _vp, _i64, ctypes.c_int32, _vp, _vp],
-    "mhx_lsh_candidate_pairs_dev": [_vp, _vp, _vp, _i64, ctypes.c_int32, _vp, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
-    "mhx_lsh_candidate_pairs": [_vp, _vp, _i64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, _vp, _i64,
+    "mhx_band_digests_dev": [_vp, _vp, _i64, _i32, _i32, _i32, _vp],
+    "mhx_band_digests": [_vp, _vp, _i64, _i32, _i32, _i32, _vp],
+    "mhx_lsh_sort_bands_dev": [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp],
+    "mhx_lsh_sort_bands": [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _vp],
+    "mhx_lsh_sort_digests_dev": [_vp, _vp, _i64, _i32, _vp, _vp],
+    "mhx_lsh_candidate_pairs_dev": [_vp, _vp, _vp, _i64, _i32, _vp, _i64, ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
+    "mhx_lsh_candidate_pairs": [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64,
                                 ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
     "mhx_lsh_query_dev": [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _int, _i32, _i64, _vp, _i64, ctypes.POINTER(_i64)],
-    "mhx_jaccard_pairs_dev": [_vp, _vp, _vp, ctypes.c_int32, _vp, _i64, _vp],
-    "mhx_jaccard_pairs": [_vp, _vp, _i64, ctypes.c_int32, _vp, _i64, _vp],
+    "mhx_jaccard_pairs_dev": [_vp, _vp, _vp, _i32, _vp, _i64, _vp],
+    "mhx_jaccard_pairs": [_vp, _vp, _i64, _i32, _vp, _i64, _vp],
     "mhx_bbit_pack_dev_typed": [_vp, _vp, _int, _i64, _i32, _i32, _vp],
     "mhx_band_digests_dev_typed": [_vp, _vp, _int, _i64, _i32, _i32, _i32, _vp],
     "mhx_bbit_pack_band_digests_dev": [_vp, _vp, _int, _i64, _i32, _i32, _i32, _i32, _int, _vp, _vp, ctypes.POINTER(_int)],
     "mhx_band_digests_layout_dev": [_vp, _vp, _int, _i64, _i32, _i32, _i32, _int, _vp],
-    "mhx_lsh_sort_digests_layout_dev": [_vp, _vp, _i64, ctypes.c_int32, _int, _vp, _vp],
+    "mhx_lsh_sort_digests_layout_dev": [_vp, _vp, _i64, _i32, _int, _vp, _vp],
     "mhx_lsh_sort_bands_dev_typed": [_vp, _vp, _int, _i64, _i32, _i32, _i32, _vp, _vp],
     "mhx_jaccard_pairs_dev_typed": [_vp, _vp, _vp, _int, _i32, _vp, _i64, _vp],
     "mhx_bbit_jaccard_pairs_dev": [_vp, _vp, _vp, _i32, _i32, _vp, _i64, _vp],

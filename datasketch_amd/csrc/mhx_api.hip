@@ -188,6 +188,105 @@ bool guard_mode() { return guard_align() != 0; }
 
 using mhx::fail;
 
+// ---- what the entry points share: the way in, the argument checks (one wording per condition), host staging ----------
+// Every entry starts here: the handle, then the lock of its context -- before any field of the context is read.
+#define MHX_ENTER(handle, ctxp)                                      \
+    if (!(handle)) return fail(MHX_ERR_INVALID, #handle " is NULL"); \
+    MHX_GUARD(ctxp)
+
+#define MHX_TRY(expr)                  \
+    do {                               \
+        if (int _rc = (expr)) return _rc; \
+    } while (0)
+
+namespace {
+
+// An operation has one checked core; `Where` says whether its data pointers are the caller's device buffers (the core only
+// enqueues) or host arrays (the core stages them through scratch and blocks until the results are back).
+enum Where { kDevice, kHost };
+#define MHX_REQUIRE_POINTERS(cond, where) MHX_REQUIRE(cond, "NULL %s pointer", (where) == kHost ? "host" : "device")
+
+// the argument checks that several entries share: one wording each
+#define MHX_CHECK_DTYPE(code) MHX_REQUIRE((code) == MHX_U64 || (code) == MHX_U32, "bad " #code " %d", code)
+#define MHX_CHECK_B(b) MHX_REQUIRE((b) >= 0 && (b) <= 32, "b must be an integer in [0, 32]")  // (the fused pack + digest entry alone asks for b >= 1)
+#define MHX_CHECK_BANDS(bands, r, k) MHX_REQUIRE((bands) > 0 && (r) > 0 && (int64_t)(bands) * (r) <= (k), "bands*r must be in (0, num_perm]")
+#define MHX_CHECK_LAYOUT(layout) MHX_REQUIRE((layout) == MHX_ROW_MAJOR || (layout) == MHX_BAND_MAJOR, "bad layout %d", layout)
+#define MHX_CHECK_BYTEORDER(order) MHX_REQUIRE((order) == MHX_LITTLE_ENDIAN || (order) == MHX_BIG_ENDIAN, "unknown byte order %d", order)
+#define MHX_CHECK_ROWS32(n) MHX_REQUIRE((n) < ((int64_t)1 << 32), "more than 2^32-1 rows per call")  // rows are numbered in 32 bits
+
+int32_t num_blocks(int32_t k, int32_t b) {  // uint64 blocks of a b-bit row
+    const int per = 64 / mhx::bbit_slot_size(b);
+    return (k + per - 1) / per;
+}
+
+// Host staging: a host entry names the pieces it wants in the context's scratch slots, commit() grows the slots, and
+// the pieces are addressed from then on.  Pieces of one slot start on 256-byte boundaries, in the order they were asked
+// for; a slot is asked to hold exactly the end of its last piece -- in guard mode that is the end of its mapping, so a
+// kernel that reads past a staged input faults -- unless ask() names another size.
+struct Stage {
+    enum Slot { In = 0, Aux = 1, Out = 2, Offsets = 3 };
+    struct Piece {
+        int slot;
+        size_t at, bytes;
+    };
+
+    explicit Stage(mhx_ctx *c) : ctx(c) {}
+
+    Piece piece(Slot slot, size_t bytes) {
+        const size_t at = (size[slot] + 255) & ~(size_t)255;
+        size[slot] = at + bytes;
+        asked[slot] = true;
+        return Piece{slot, at, bytes};
+    }
+    // the size the slot is grown to where that is not the end of its last piece: the slack some entries have always
+    // carried behind their inputs.  Nothing is known to need it; the sizes are kept as they were.
+    void ask(Slot slot, size_t bytes) { size[slot] = bytes; }
+
+    int commit() {
+        for (int slot = 0; slot < 5; ++slot)
+            if (asked[slot]) MHX_TRY(ctx->ensure_scratch(slot, size[slot]));
+        return MHX_OK;
+    }
+    template <class T>
+    T *at(const Piece &p) const { return reinterpret_cast<T *>(static_cast<char *>(ctx->scratch[p.slot]) + p.at); }
+
+    int upload(const Piece &p, const void *host, size_t bytes) const {
+        if (bytes) MHX_HIP_CHECK(hipMemcpyAsync(at<void>(p), host, bytes, hipMemcpyHostToDevice, ctx->stream));
+        return MHX_OK;
+    }
+    int upload(const Piece &p, const void *host) const { return upload(p, host, p.bytes); }
+    int download(void *host, const Piece &p, size_t bytes) const {
+        MHX_HIP_CHECK(hipMemcpyAsync(host, at<void>(p), bytes, hipMemcpyDeviceToHost, ctx->stream));
+        return MHX_OK;
+    }
+    int download(void *host, const Piece &p) const { return download(host, p, p.bytes); }
+    int synchronize() const {
+        MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        return MHX_OK;
+    }
+    int fetch(void *host, const Piece &p) const {  // the last piece of a call: down, then wait
+        MHX_TRY(download(host, p));
+        return synchronize();
+    }
+
+    mhx_ctx *ctx;
+    size_t size[5] = {0, 0, 0, 0, 0};
+    bool asked[5] = {false, false, false, false, false};
+};
+
+// the plainest host form: one array up (In), the launch, one array back (Out), then wait
+template <class Launch>
+int through_scratch(mhx_ctx *ctx, const void *in, size_t in_bytes, void *out, size_t out_bytes, Launch launch) {
+    Stage s(ctx);
+    const auto p_in = s.piece(Stage::In, in_bytes), p_out = s.piece(Stage::Out, out_bytes);
+    MHX_TRY(s.commit());
+    MHX_TRY(s.upload(p_in, in));
+    MHX_TRY(launch(s.at<void>(p_in), s.at<void>(p_out)));
+    return s.fetch(out, p_out);
+}
+
+}  // namespace
+
 int mhx_ctx::activate() const {
     MHX_HIP_CHECK(hipSetDevice(device));
     return MHX_OK;
@@ -321,16 +420,14 @@ int mhx_ctx_destroy(mhx_ctx *ctx) {
 }
 
 int mhx_ctx_synchronize(mhx_ctx *ctx) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
+    MHX_ENTER(ctx, ctx);
     MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return MHX_OK;
 }
 
 int mhx_ctx_release_scratch(mhx_ctx *ctx) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    if (int rc = ctx->activate()) return rc;
+    MHX_ENTER(ctx, ctx);
+    MHX_TRY(ctx->activate());
     MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     for (int i = 0; i < 5; ++i) {
         if (ctx->scratch[i]) MHX_HIP_CHECK(mhx::dev_free(ctx->scratch[i]));
@@ -346,8 +443,7 @@ int mhx_ctx_release_scratch(mhx_ctx *ctx) {
 }
 
 int mhx_ctx_device_info(mhx_ctx *ctx, char *name, int name_len, int *cus, int64_t *hbm_bytes) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
+    MHX_ENTER(ctx, ctx);
     if (name && name_len > 0) {
         strncpy(name, ctx->name, (size_t)name_len - 1);
         name[name_len - 1] = 0;
@@ -358,54 +454,46 @@ int mhx_ctx_device_info(mhx_ctx *ctx, char *name, int name_len, int *cus, int64_
 }
 
 int mhx_ctx_set_option(mhx_ctx *ctx, const char *key, int64_t value) {
+    static const struct {
+        const char *key;
+        int64_t mhx_ctx::*field;
+    } options[] = {
+        {"minhash.path", &mhx_ctx::opt_minhash_path},       {"minhash.split", &mhx_ctx::opt_minhash_split},
+        {"minhash.packed", &mhx_ctx::opt_minhash_packed},   {"minhash.ties", &mhx_ctx::opt_minhash_ties},
+        {"minhash.p3", &mhx_ctx::opt_minhash_p3},           {"minhash.share", &mhx_ctx::opt_minhash_share},
+        {"minhash.adapt", &mhx_ctx::opt_minhash_adapt},     {"blocks_per_cu", &mhx_ctx::opt_blocks_per_cu},
+        {"minhash.alias", &mhx_ctx::opt_minhash_alias},     {"minhash.prefetch", &mhx_ctx::opt_minhash_prefetch},
+        {"weighted.path", &mhx_ctx::opt_weighted_path},     {"weighted.direct", &mhx_ctx::opt_weighted_direct},
+        {"weighted.split", &mhx_ctx::opt_weighted_split},   {"weighted.tail", &mhx_ctx::opt_weighted_tail},
+        {"weighted.debug", &mhx_ctx::opt_weighted_debug},   {"weighted.kernel", &mhx_ctx::opt_weighted_kernel},
+        {"weighted.plan", &mhx_ctx::opt_weighted_plan},     {"weighted.rescue", &mhx_ctx::opt_weighted_rescue},
+        {"weighted.min_dim", &mhx_ctx::opt_weighted_min_dim}, {"host.chunk_bytes", &mhx_ctx::opt_host_chunk_bytes},
+        {"lsh.sort_bits", &mhx_ctx::opt_lsh_sort_bits},     {"lsh.gather", &mhx_ctx::opt_lsh_gather},
+        {"lsh.sort", &mhx_ctx::opt_lsh_sort},               {"lsh.levels", &mhx_ctx::opt_lsh_levels},
+        {"lsh.chunk", &mhx_ctx::opt_lsh_chunk},             {"lsh.team", &mhx_ctx::opt_lsh_team},
+        {"lsh.bigbins", &mhx_ctx::opt_lsh_bigbins},         {"pack.fused", &mhx_ctx::opt_pack_fused},
+        {"weighted.refill", &mhx_ctx::opt_weighted_refill}, {"lsh.prehash", &mhx_ctx::opt_lsh_prehash},
+        {"lsh.merge_items", &mhx_ctx::opt_lsh_merge_items},
+    };
     if (!ctx || !key) return fail(MHX_ERR_INVALID, "ctx/key is NULL");
     MHX_GUARD(ctx);
-    if (!strcmp(key, "minhash.path")) ctx->opt_minhash_path = value;
-    else if (!strcmp(key, "minhash.split")) ctx->opt_minhash_split = value;
-    else if (!strcmp(key, "minhash.packed")) ctx->opt_minhash_packed = value;
-    else if (!strcmp(key, "minhash.ties")) ctx->opt_minhash_ties = value;
-    else if (!strcmp(key, "minhash.p3")) ctx->opt_minhash_p3 = value;
-    else if (!strcmp(key, "minhash.share")) ctx->opt_minhash_share = value;
-    else if (!strcmp(key, "minhash.adapt")) ctx->opt_minhash_adapt = value;
-    else if (!strcmp(key, "blocks_per_cu")) ctx->opt_blocks_per_cu = value;
-    else if (!strcmp(key, "minhash.alias")) ctx->opt_minhash_alias = value;
-    else if (!strcmp(key, "minhash.prefetch")) ctx->opt_minhash_prefetch = value;
-    else if (!strcmp(key, "weighted.path")) ctx->opt_weighted_path = value;
-    else if (!strcmp(key, "weighted.direct")) ctx->opt_weighted_direct = value;
-    else if (!strcmp(key, "weighted.split")) ctx->opt_weighted_split = value;
-    else if (!strcmp(key, "weighted.tail")) ctx->opt_weighted_tail = value;
-    else if (!strcmp(key, "weighted.debug")) ctx->opt_weighted_debug = value;
-    else if (!strcmp(key, "weighted.kernel")) ctx->opt_weighted_kernel = value;
-    else if (!strcmp(key, "weighted.plan")) ctx->opt_weighted_plan = value;
-    else if (!strcmp(key, "weighted.rescue")) ctx->opt_weighted_rescue = value;
-    else if (!strcmp(key, "weighted.min_dim")) ctx->opt_weighted_min_dim = value;
-    else if (!strcmp(key, "host.chunk_bytes")) ctx->opt_host_chunk_bytes = value;
-    else if (!strcmp(key, "lsh.sort_bits")) ctx->opt_lsh_sort_bits = value;
-    else if (!strcmp(key, "lsh.gather")) ctx->opt_lsh_gather = value;
-    else if (!strcmp(key, "lsh.sort")) ctx->opt_lsh_sort = value;
-    else if (!strcmp(key, "lsh.levels")) ctx->opt_lsh_levels = value;
-    else if (!strcmp(key, "lsh.chunk")) ctx->opt_lsh_chunk = value;
-    else if (!strcmp(key, "lsh.team")) ctx->opt_lsh_team = value;
-    else if (!strcmp(key, "lsh.bigbins")) ctx->opt_lsh_bigbins = value;
-    else if (!strcmp(key, "pack.fused")) ctx->opt_pack_fused = value;
-    else if (!strcmp(key, "weighted.refill")) ctx->opt_weighted_refill = value;
-    else if (!strcmp(key, "lsh.prehash")) ctx->opt_lsh_prehash = value;
-    else if (!strcmp(key, "lsh.merge_items")) {
-        if (value != 0 && value != 8 && value != 16) return fail(MHX_ERR_INVALID, "lsh.merge_items must be 0, 8 or 16");
-        ctx->opt_lsh_merge_items = value;
+    for (const auto &o : options) {
+        if (strcmp(key, o.key)) continue;
+        if (o.field == &mhx_ctx::opt_lsh_merge_items)
+            MHX_REQUIRE(value == 0 || value == 8 || value == 16, "lsh.merge_items must be 0, 8 or 16");
+        ctx->*o.field = value;
+        return MHX_OK;
     }
-    else return fail(MHX_ERR_INVALID, "unknown option '%s'", key);
-    return MHX_OK;
+    return fail(MHX_ERR_INVALID, "unknown option '%s'", key);
 }
 
 // What the previous MinHash call on this context learned about the corpus (d_work word 8, written by the last launch of every
 // call and read by the first launch of the next one): 0 = one-candidate proof first, 1 = most sets defeat it (tie-tolerant proof
 // first), 2 = heavily repeated tokens.  Timings depend on it, results never; reset = 1 puts it back to 0 (a fresh context).
 int mhx_ctx_minhash_mode(mhx_ctx *ctx, int reset, int *mode) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    if (int rc = ctx->activate()) return rc;
-    if (int rc = ctx->ensure_work()) return rc;
+    MHX_ENTER(ctx, ctx);
+    MHX_TRY(ctx->activate());
+    MHX_TRY(ctx->ensure_work());
     unsigned int word = 0;
     MHX_HIP_CHECK(hipMemcpyAsync(&word, ctx->d_work + 8, sizeof(word), hipMemcpyDeviceToHost, ctx->stream));
     MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
@@ -417,9 +505,8 @@ int mhx_ctx_minhash_mode(mhx_ctx *ctx, int reset, int *mode) {
 // Which sets of the last MinHash call left the fast path (see mhx.h).  The flags are the launches' own hand-over bytes: the sieve
 // launch writes 0 / 1 for every set, the second launch turns the 1 of a set it could not certify either into 2.
 int mhx_ctx_minhash_flags(mhx_ctx *ctx, int64_t n_sets, uint8_t *flags) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    if (int rc = ctx->activate()) return rc;
+    MHX_ENTER(ctx, ctx);
+    MHX_TRY(ctx->activate());
     MHX_REQUIRE(n_sets >= 0 && (flags || n_sets == 0), "NULL flags");
     if (ctx->redo_sets != n_sets || (n_sets > 0 && !ctx->d_redo))
         return fail(MHX_ERR_INVALID, "the last MinHash call on this context kept flags for %lld sets, not %lld (one huge set split over waves and "
@@ -430,9 +517,8 @@ int mhx_ctx_minhash_flags(mhx_ctx *ctx, int64_t n_sets, uint8_t *flags) {
 }
 
 int mhx_ctx_counters(mhx_ctx *ctx, int enable, uint64_t out[MHX_NUM_COUNTERS]) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    if (int rc = ctx->activate()) return rc;
+    MHX_ENTER(ctx, ctx);
+    MHX_TRY(ctx->activate());
     MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     if (out) {
         for (int i = 0; i < MHX_NUM_COUNTERS; ++i) out[i] = 0;
@@ -500,7 +586,7 @@ int mhx_dev_alloc(mhx_ctx *ctx, size_t bytes, void **dptr) {
     if (!ctx || !dptr) return fail(MHX_ERR_INVALID, "ctx/dptr is NULL");
     MHX_GUARD(ctx);
     *dptr = nullptr;
-    if (int rc = ctx->activate()) return rc;
+    MHX_TRY(ctx->activate());
     hipError_t e = mhx::dev_malloc(dptr, bytes ? bytes : 1, true);
     if (e != hipSuccess) {
         (void)hipGetLastError();
@@ -510,10 +596,9 @@ int mhx_dev_alloc(mhx_ctx *ctx, size_t bytes, void **dptr) {
 }
 
 int mhx_dev_free(mhx_ctx *ctx, void *dptr) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
+    MHX_ENTER(ctx, ctx);
     if (!dptr) return MHX_OK;
-    if (int rc = ctx->activate()) return rc;
+    MHX_TRY(ctx->activate());
     MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     MHX_HIP_CHECK(mhx::dev_free(dptr));
     return MHX_OK;
@@ -523,7 +608,7 @@ int mhx_host_alloc(mhx_ctx *ctx, size_t bytes, void **ptr) {
     if (!ctx || !ptr) return fail(MHX_ERR_INVALID, "ctx/ptr is NULL");
     MHX_GUARD(ctx);
     *ptr = nullptr;
-    if (int rc = ctx->activate()) return rc;
+    MHX_TRY(ctx->activate());
     hipError_t e = hipHostMalloc(ptr, bytes ? bytes : 1, hipHostMallocDefault);
     if (e != hipSuccess) {
         (void)hipGetLastError();
@@ -539,7 +624,7 @@ int mhx_host_free(mhx_ctx *ctx, void *ptr) {
         return MHX_OK;
     }
     MHX_GUARD(ctx);
-    if (int rc = ctx->activate()) return rc;
+    MHX_TRY(ctx->activate());
     MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     if (ctx->copy_in) MHX_HIP_CHECK(hipStreamSynchronize(ctx->copy_in));
     MHX_HIP_CHECK(hipHostFree(ptr));
@@ -547,39 +632,35 @@ int mhx_host_free(mhx_ctx *ctx, void *ptr) {
 }
 
 int mhx_memcpy_h2d(mhx_ctx *ctx, void *dst, const void *src, size_t bytes) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
+    MHX_ENTER(ctx, ctx);
     if (!bytes) return MHX_OK;
-    if (int rc = ctx->activate()) return rc;
+    MHX_TRY(ctx->activate());
     MHX_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, ctx->stream));
     MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return MHX_OK;
 }
 
 int mhx_memcpy_d2h(mhx_ctx *ctx, void *dst, const void *src, size_t bytes) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
+    MHX_ENTER(ctx, ctx);
     if (!bytes) return MHX_OK;
-    if (int rc = ctx->activate()) return rc;
+    MHX_TRY(ctx->activate());
     MHX_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->stream));
     MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return MHX_OK;
 }
 
 int mhx_memcpy_d2d(mhx_ctx *ctx, void *dst, const void *src, size_t bytes) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
+    MHX_ENTER(ctx, ctx);
     if (!bytes) return MHX_OK;
-    if (int rc = ctx->activate()) return rc;
+    MHX_TRY(ctx->activate());
     MHX_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, ctx->stream));
     return MHX_OK;
 }
 
 int mhx_memset_dev(mhx_ctx *ctx, void *dst, int byte_value, size_t bytes) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
+    MHX_ENTER(ctx, ctx);
     if (!bytes) return MHX_OK;
-    if (int rc = ctx->activate()) return rc;
+    MHX_TRY(ctx->activate());
     MHX_HIP_CHECK(hipMemsetAsync(dst, byte_value, bytes, ctx->stream));
     return MHX_OK;
 }
@@ -588,7 +669,7 @@ int mhx_memset_dev(mhx_ctx *ctx, void *dst, int byte_value, size_t bytes) {
 int mhx_event_create(mhx_ctx *ctx, mhx_event **ev) {
     if (!ctx || !ev) return fail(MHX_ERR_INVALID, "ctx/ev is NULL");
     MHX_GUARD(ctx);
-    if (int rc = ctx->activate()) return rc;
+    MHX_TRY(ctx->activate());
     mhx_event *e = new mhx_event();
     e->ctx = ctx;
     hipError_t err = hipEventCreate(&e->ev);
@@ -632,7 +713,7 @@ int mhx_perm_create(mhx_ctx *ctx, const uint64_t *a, const uint64_t *b, int32_t 
     if (!ctx || !a || !b || !out) return fail(MHX_ERR_INVALID, "NULL argument");
     MHX_GUARD(ctx);
     MHX_REQUIRE(num_perm > 0, "num_perm must be positive, got %d", num_perm);
-    if (int rc = ctx->activate()) return rc;
+    MHX_TRY(ctx->activate());
     mhx_perm *p = new mhx_perm();
     p->ctx = ctx;
     p->num_perm = num_perm;
@@ -665,21 +746,24 @@ int mhx_perm_destroy(mhx_perm *perm) {
     return MHX_OK;
 }
 
-int mhx_minhash_bulk_dev(mhx_perm *perm, const void *d_hv, int hv_dtype, const int64_t *d_offsets,
-                         int64_t fixed_len, int64_t n_sets, int64_t total_tokens,
-                         const uint64_t *d_init, int64_t init_stride, void *d_out, int out_dtype) {
-    if (!perm) return fail(MHX_ERR_INVALID, "perm is NULL");
-    MHX_GUARD(perm->ctx);
+static int check_bulk(int64_t n_sets, int hv_dtype, int out_dtype) {
     MHX_REQUIRE(n_sets >= 0, "n_sets must be >= 0");
-    MHX_REQUIRE(hv_dtype == MHX_U64 || hv_dtype == MHX_U32, "bad hv_dtype %d", hv_dtype);
-    MHX_REQUIRE(out_dtype == MHX_U64 || out_dtype == MHX_U32, "bad out_dtype %d", out_dtype);
+    MHX_CHECK_DTYPE(hv_dtype);
+    MHX_CHECK_DTYPE(out_dtype);
+    return MHX_OK;
+}
+
+int mhx_minhash_bulk_dev(mhx_perm *perm, const void *d_hv, int hv_dtype, const int64_t *d_offsets, int64_t fixed_len, int64_t n_sets,
+                         int64_t total_tokens, const uint64_t *d_init, int64_t init_stride, void *d_out, int out_dtype) {
+    MHX_ENTER(perm, perm->ctx);
+    MHX_TRY(check_bulk(n_sets, hv_dtype, out_dtype));
     MHX_REQUIRE(d_offsets || fixed_len >= 0, "fixed_len must be >= 0 when offsets is NULL");
     MHX_REQUIRE(init_stride == 0 || init_stride >= perm->num_perm, "init_stride must be 0 or >= num_perm");
     MHX_REQUIRE(total_tokens >= 0, "total_tokens must be >= 0");
     if (n_sets == 0) return MHX_OK;
     MHX_REQUIRE(d_out, "d_out is NULL");
     MHX_REQUIRE(d_hv || total_tokens == 0, "d_hv is NULL");
-    if (int rc = perm->ctx->activate()) return rc;
+    MHX_TRY(perm->ctx->activate());
     return mhx::launch_minhash_bulk(perm, d_hv, hv_dtype, d_offsets, fixed_len, n_sets, total_tokens,
                                     d_init, init_stride, d_out, out_dtype);
 }
@@ -831,16 +915,13 @@ int bulk_pipelined(mhx_perm *perm, const char *hv, int hv_dtype, const int64_t *
 
 int mhx_minhash_bulk_typed(mhx_perm *perm, const void *hv, int hv_dtype, const int64_t *offsets, int64_t fixed_len,
                            int64_t n_sets, const uint64_t *init, int64_t init_stride, void *out, int out_dtype) {
-    if (!perm) return fail(MHX_ERR_INVALID, "perm is NULL");
-    MHX_GUARD(perm->ctx);
-    MHX_REQUIRE(n_sets >= 0, "n_sets must be >= 0");
-    MHX_REQUIRE(hv_dtype == MHX_U64 || hv_dtype == MHX_U32, "bad hv_dtype %d", hv_dtype);
-    MHX_REQUIRE(out_dtype == MHX_U64 || out_dtype == MHX_U32, "bad out_dtype %d", out_dtype);
+    MHX_ENTER(perm, perm->ctx);
+    MHX_TRY(check_bulk(n_sets, hv_dtype, out_dtype));
     if (n_sets == 0) return MHX_OK;
     MHX_REQUIRE(out, "out is NULL");
     MHX_REQUIRE(offsets || fixed_len >= 0, "fixed_len must be >= 0 when offsets is NULL");
     mhx_ctx *ctx = perm->ctx;
-    if (int rc = ctx->activate()) return rc;
+    MHX_TRY(ctx->activate());
     const int64_t k = perm->num_perm;
     const size_t ts = hv_dtype == MHX_U32 ? 4 : 8, os = out_dtype == MHX_U32 ? 4 : 8;
     int64_t total = 0;
@@ -853,43 +934,39 @@ int mhx_minhash_bulk_typed(mhx_perm *perm, const void *hv, int hv_dtype, const i
         total = n_sets * fixed_len;
     }
     MHX_REQUIRE(hv || total == 0, "hv is NULL");
-    const size_t hv_bytes = ts * (size_t)total;
-    const size_t off_bytes = offsets ? sizeof(int64_t) * (size_t)(n_sets + 1) : 0;
-    const size_t out_bytes = os * (size_t)(n_sets * k);
     const size_t init_bytes = init ? sizeof(uint64_t) * (size_t)(init_stride ? n_sets * init_stride : k) : 0;
-    if (int rc = ctx->ensure_scratch(0, hv_bytes + 256)) return rc;
-    if (int rc = ctx->ensure_scratch(1, off_bytes + init_bytes + 512)) return rc;
-    if (int rc = ctx->ensure_scratch(2, out_bytes)) return rc;
-    char *d_hv = (char *)ctx->scratch[0];
-    int64_t *d_off = offsets ? (int64_t *)ctx->scratch[1] : nullptr;
-    uint64_t *d_init = init ? (uint64_t *)((char *)ctx->scratch[1] + ((off_bytes + 255) & ~(size_t)255)) : nullptr;
-    char *d_out = (char *)ctx->scratch[2];
+    Stage s(ctx);
+    const auto p_hv = s.piece(Stage::In, ts * (size_t)total);
+    const auto p_off = s.piece(Stage::Aux, offsets ? sizeof(int64_t) * (size_t)(n_sets + 1) : 0);
+    const auto p_init = s.piece(Stage::Aux, init_bytes);
+    const auto p_out = s.piece(Stage::Out, os * (size_t)(n_sets * k));
+    s.ask(Stage::In, p_hv.bytes + 256);
+    s.ask(Stage::Aux, p_off.bytes + init_bytes + 512);
+    MHX_TRY(s.commit());
+    char *d_hv = s.at<char>(p_hv), *d_out = s.at<char>(p_out);
+    int64_t *d_off = offsets ? s.at<int64_t>(p_off) : nullptr;
+    uint64_t *d_init = init ? s.at<uint64_t>(p_init) : nullptr;
 
     // large corpora: upload, kernels and download overlap piece by piece
     const int64_t chunk_opt = ctx->opt_host_chunk_bytes;
     const int64_t target = chunk_opt > 0 ? chunk_opt : (int64_t)96 << 20;
-    const bool pipelined = chunk_opt > 0 || (chunk_opt == 0 && hv_bytes + out_bytes > ((size_t)256 << 20));
+    const bool pipelined = chunk_opt > 0 || (chunk_opt == 0 && p_hv.bytes + p_out.bytes > ((size_t)256 << 20));
     if (pipelined) {
         const std::vector<Piece> pieces = cut_pieces(offsets, fixed_len, n_sets, k, target, (int64_t)ts, (int64_t)os);
         if (pieces.size() > 1) {
             // small operands first, on the compute stream: every piece's kernels are ordered after them
-            if (off_bytes) MHX_HIP_CHECK(hipMemcpyAsync(d_off, offsets, off_bytes, hipMemcpyHostToDevice, ctx->stream));
-            if (init && !init_stride)
-                MHX_HIP_CHECK(hipMemcpyAsync(d_init, init, init_bytes, hipMemcpyHostToDevice, ctx->stream));
+            MHX_TRY(s.upload(p_off, offsets));
+            if (init && !init_stride) MHX_TRY(s.upload(p_init, init));
             const int rc = bulk_pipelined(perm, (const char *)hv, hv_dtype, offsets, fixed_len, n_sets, init, init_stride,
                                           (char *)out, out_dtype, d_hv, d_off, d_init, d_out, pieces);
             if (rc != kNoSecondThread) return rc;
         }
     }
-    if (hv_bytes) MHX_HIP_CHECK(hipMemcpyAsync(d_hv, hv, hv_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (off_bytes) MHX_HIP_CHECK(hipMemcpyAsync(d_off, offsets, off_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (init_bytes) MHX_HIP_CHECK(hipMemcpyAsync(d_init, init, init_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = mhx::launch_minhash_bulk(perm, d_hv, hv_dtype, d_off, fixed_len, n_sets, total, d_init,
-                                          init_stride, d_out, out_dtype))
-        return rc;
-    MHX_HIP_CHECK(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return MHX_OK;
+    MHX_TRY(s.upload(p_hv, hv));
+    MHX_TRY(s.upload(p_off, offsets));
+    MHX_TRY(s.upload(p_init, init));
+    MHX_TRY(mhx::launch_minhash_bulk(perm, d_hv, hv_dtype, d_off, fixed_len, n_sets, total, d_init, init_stride, d_out, out_dtype));
+    return s.fetch(out, p_out);
 }
 
 int mhx_minhash_bulk(mhx_perm *perm, const uint64_t *hv, const int64_t *offsets, int64_t fixed_len,
@@ -898,70 +975,64 @@ int mhx_minhash_bulk(mhx_perm *perm, const uint64_t *hv, const int64_t *offsets,
 }
 
 // ---- token hashing (sha1_hash32 / sha1_hash64 of byte tokens) ----------------------------------
-int mhx_sha1_tokens_dev(mhx_ctx *ctx, const uint8_t *d_bytes, const int64_t *d_byte_offsets, int64_t n_tokens,
-                        int out_dtype, void *d_out) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
+static int check_sha1(int64_t n_tokens, int out_dtype) {
     MHX_REQUIRE(n_tokens >= 0, "n_tokens must be >= 0");
-    MHX_REQUIRE(out_dtype == MHX_U32 || out_dtype == MHX_U64, "out_dtype must be MHX_U32 or MHX_U64");
+    MHX_CHECK_DTYPE(out_dtype);
+    return MHX_OK;
+}
+
+int mhx_sha1_tokens_dev(mhx_ctx *ctx, const uint8_t *d_bytes, const int64_t *d_byte_offsets, int64_t n_tokens, int out_dtype, void *d_out) {
+    MHX_ENTER(ctx, ctx);
+    MHX_TRY(check_sha1(n_tokens, out_dtype));
     if (n_tokens == 0) return MHX_OK;
-    MHX_REQUIRE(d_byte_offsets && d_out, "NULL device pointer");
-    if (int rc = ctx->activate()) return rc;
+    MHX_REQUIRE_POINTERS(d_byte_offsets && d_out, kDevice);
+    MHX_TRY(ctx->activate());
     return mhx::launch_sha1_tokens(ctx, d_bytes, d_byte_offsets, n_tokens, out_dtype, d_out);
 }
 
-namespace {
-// validate + upload a packed byte corpus: bytes -> scratch[0], byte offsets -> scratch[3]
-int upload_tokens(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens,
-                  uint8_t **d_bytes, int64_t **d_offs) {
+// validate + upload a packed byte corpus: bytes -> In, byte offsets -> Offsets
+static int upload_tokens(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens, uint8_t **d_bytes, int64_t **d_offs) {
     MHX_REQUIRE(byte_offsets, "byte_offsets is NULL");
     MHX_REQUIRE(byte_offsets[0] == 0, "byte_offsets[0] must be 0");
     for (int64_t i = 0; i < n_tokens; ++i)
         MHX_REQUIRE(byte_offsets[i + 1] >= byte_offsets[i], "byte_offsets must be non-decreasing (token %lld)", (long long)i);
     const int64_t total = byte_offsets[n_tokens];
     MHX_REQUIRE(bytes || total == 0, "bytes is NULL");
-    if (int rc = ctx->ensure_scratch(0, (size_t)total + 256)) return rc;
-    if (int rc = ctx->ensure_scratch(3, sizeof(int64_t) * (size_t)(n_tokens + 1))) return rc;
-    *d_bytes = (uint8_t *)ctx->scratch[0];
-    *d_offs = (int64_t *)ctx->scratch[3];
-    if (total) MHX_HIP_CHECK(hipMemcpyAsync(*d_bytes, bytes, (size_t)total, hipMemcpyHostToDevice, ctx->stream));
-    MHX_HIP_CHECK(hipMemcpyAsync(*d_offs, byte_offsets, sizeof(int64_t) * (size_t)(n_tokens + 1), hipMemcpyHostToDevice,
-                                 ctx->stream));
-    return MHX_OK;
+    Stage s(ctx);
+    const auto p_bytes = s.piece(Stage::In, (size_t)total);
+    const auto p_offs = s.piece(Stage::Offsets, sizeof(int64_t) * (size_t)(n_tokens + 1));
+    s.ask(Stage::In, (size_t)total + 256);
+    MHX_TRY(s.commit());
+    *d_bytes = s.at<uint8_t>(p_bytes);
+    *d_offs = s.at<int64_t>(p_offs);
+    MHX_TRY(s.upload(p_bytes, bytes));
+    return s.upload(p_offs, byte_offsets);
 }
-}  // namespace
 
-int mhx_sha1_tokens(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens,
-                    int out_dtype, void *out) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    MHX_REQUIRE(n_tokens >= 0, "n_tokens must be >= 0");
-    MHX_REQUIRE(out_dtype == MHX_U32 || out_dtype == MHX_U64, "out_dtype must be MHX_U32 or MHX_U64");
+int mhx_sha1_tokens(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens, int out_dtype, void *out) {
+    MHX_ENTER(ctx, ctx);
+    MHX_TRY(check_sha1(n_tokens, out_dtype));
     if (n_tokens == 0) return MHX_OK;
     MHX_REQUIRE(out, "out is NULL");
-    if (int rc = ctx->activate()) return rc;
+    MHX_TRY(ctx->activate());
     uint8_t *d_bytes = nullptr;
     int64_t *d_offs = nullptr;
-    if (int rc = upload_tokens(ctx, bytes, byte_offsets, n_tokens, &d_bytes, &d_offs)) return rc;
-    const size_t out_bytes = (size_t)n_tokens * (out_dtype == MHX_U32 ? 4 : 8);
-    if (int rc = ctx->ensure_scratch(2, out_bytes)) return rc;
-    if (int rc = mhx::launch_sha1_tokens(ctx, d_bytes, d_offs, n_tokens, out_dtype, ctx->scratch[2])) return rc;
-    MHX_HIP_CHECK(hipMemcpyAsync(out, ctx->scratch[2], out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return MHX_OK;
+    MHX_TRY(upload_tokens(ctx, bytes, byte_offsets, n_tokens, &d_bytes, &d_offs));
+    Stage s(ctx);
+    const auto p_out = s.piece(Stage::Out, (size_t)n_tokens * (out_dtype == MHX_U32 ? 4 : 8));
+    MHX_TRY(s.commit());
+    MHX_TRY(mhx::launch_sha1_tokens(ctx, d_bytes, d_offs, n_tokens, out_dtype, s.at<void>(p_out)));
+    return s.fetch(out, p_out);
 }
 
-int mhx_minhash_bulk_bytes(mhx_perm *perm, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens,
-                           const int64_t *set_offsets, int64_t n_sets, const uint64_t *init, int64_t init_stride,
-                           uint64_t *out) {
+int mhx_minhash_bulk_bytes(mhx_perm *perm, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens, const int64_t *set_offsets,
+                           int64_t n_sets, const uint64_t *init, int64_t init_stride, uint64_t *out) {
     return mhx_minhash_bulk_bytes_typed(perm, bytes, byte_offsets, n_tokens, MHX_U32, set_offsets, n_sets, init, init_stride, out);
 }
 
-int mhx_minhash_bulk_bytes_typed(mhx_perm *perm, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens,
-                                 int hash_dtype, const int64_t *set_offsets, int64_t n_sets, const uint64_t *init,
-                                 int64_t init_stride, uint64_t *out) {
-    if (!perm) return fail(MHX_ERR_INVALID, "perm is NULL");
-    MHX_GUARD(perm->ctx);
+int mhx_minhash_bulk_bytes_typed(mhx_perm *perm, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens, int hash_dtype,
+                                 const int64_t *set_offsets, int64_t n_sets, const uint64_t *init, int64_t init_stride, uint64_t *out) {
+    MHX_ENTER(perm, perm->ctx);
     MHX_REQUIRE(hash_dtype == MHX_U32 || hash_dtype == MHX_U64, "hash_dtype must be MHX_U32 (sha1_hash32) or MHX_U64 (sha1_hash64)");
     MHX_REQUIRE(n_sets >= 0 && n_tokens >= 0, "n_sets and n_tokens must be >= 0");
     if (n_sets == 0) return MHX_OK;
@@ -970,549 +1041,421 @@ int mhx_minhash_bulk_bytes_typed(mhx_perm *perm, const uint8_t *bytes, const int
     for (int64_t i = 0; i < n_sets; ++i)
         MHX_REQUIRE(set_offsets[i + 1] >= set_offsets[i], "set_offsets must be non-decreasing (set %lld)", (long long)i);
     mhx_ctx *ctx = perm->ctx;
-    if (int rc = ctx->activate()) return rc;
+    MHX_TRY(ctx->activate());
     const int64_t k = perm->num_perm;
     uint8_t *d_bytes = nullptr;
     int64_t *d_boffs = nullptr;
-    if (n_tokens > 0)
-        if (int rc = upload_tokens(ctx, bytes, byte_offsets, n_tokens, &d_bytes, &d_boffs)) return rc;
-    // scratch[1]: set offsets | init | token hashes (uint32 or uint64);  scratch[2]: signatures
-    const size_t hs = hash_dtype == MHX_U32 ? 4 : 8;
-    const size_t off_bytes = sizeof(int64_t) * (size_t)(n_sets + 1);
-    const size_t init_bytes = init ? sizeof(uint64_t) * (size_t)(init_stride ? n_sets * init_stride : k) : 0;
-    const size_t off_pad = (off_bytes + 255) & ~(size_t)255, init_pad = (init_bytes + 255) & ~(size_t)255;
-    const size_t out_bytes = sizeof(uint64_t) * (size_t)(n_sets * k);
-    if (int rc = ctx->ensure_scratch(1, off_pad + init_pad + hs * (size_t)n_tokens + 256)) return rc;
-    if (int rc = ctx->ensure_scratch(2, out_bytes)) return rc;
-    int64_t *d_soffs = (int64_t *)ctx->scratch[1];
-    uint64_t *d_init = init ? (uint64_t *)((char *)ctx->scratch[1] + off_pad) : nullptr;
-    void *d_hv = (char *)ctx->scratch[1] + off_pad + init_pad;
-    uint64_t *d_out = (uint64_t *)ctx->scratch[2];
-    MHX_HIP_CHECK(hipMemcpyAsync(d_soffs, set_offsets, off_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (init_bytes) MHX_HIP_CHECK(hipMemcpyAsync(d_init, init, init_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = mhx::launch_sha1_tokens(ctx, d_bytes, d_boffs, n_tokens, hash_dtype, d_hv)) return rc;
-    if (int rc = mhx::launch_minhash_bulk(perm, d_hv, hash_dtype, d_soffs, 0, n_sets, n_tokens, d_init, init_stride, d_out,
-                                          MHX_U64))
-        return rc;
-    MHX_HIP_CHECK(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return MHX_OK;
+    if (n_tokens > 0) MHX_TRY(upload_tokens(ctx, bytes, byte_offsets, n_tokens, &d_bytes, &d_boffs));
+    // Aux: set offsets | init | token hashes (uint32 or uint64);  Out: signatures
+    Stage s(ctx);
+    const auto p_soffs = s.piece(Stage::Aux, sizeof(int64_t) * (size_t)(n_sets + 1));
+    const auto p_init = s.piece(Stage::Aux, init ? sizeof(uint64_t) * (size_t)(init_stride ? n_sets * init_stride : k) : 0);
+    const auto p_hv = s.piece(Stage::Aux, (hash_dtype == MHX_U32 ? 4 : 8) * (size_t)n_tokens);
+    const auto p_out = s.piece(Stage::Out, sizeof(uint64_t) * (size_t)(n_sets * k));
+    s.ask(Stage::Aux, p_hv.at + p_hv.bytes + 256);
+    MHX_TRY(s.commit());
+    uint64_t *d_init = init ? s.at<uint64_t>(p_init) : nullptr;
+    MHX_TRY(s.upload(p_soffs, set_offsets));
+    MHX_TRY(s.upload(p_init, init));
+    MHX_TRY(mhx::launch_sha1_tokens(ctx, d_bytes, d_boffs, n_tokens, hash_dtype, s.at<void>(p_hv)));
+    MHX_TRY(mhx::launch_minhash_bulk(perm, s.at<void>(p_hv), hash_dtype, s.at<int64_t>(p_soffs), 0, n_sets, n_tokens, d_init, init_stride,
+                                     s.at<uint64_t>(p_out), MHX_U64));
+    return s.fetch(out, p_out);
 }
 
 int mhx_minhash_update_batch(mhx_perm *perm, const uint64_t *hv, int64_t n, uint64_t *hashvalues) {
-    if (!perm) return fail(MHX_ERR_INVALID, "perm is NULL");
-    MHX_GUARD(perm->ctx);
+    MHX_ENTER(perm, perm->ctx);
     MHX_REQUIRE(n >= 0, "n must be >= 0");
     if (n == 0) return MHX_OK;  // ref: minhash.py:265-266
     MHX_REQUIRE(hv && hashvalues, "hv/hashvalues is NULL");
     return mhx_minhash_bulk(perm, hv, nullptr, n, 1, hashvalues, 0, hashvalues);
 }
 
-int mhx_minhash_merge_dev(mhx_ctx *ctx, const uint64_t *d_x, const uint64_t *d_y, int64_t count,
-                          uint64_t *d_out) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
+static int minhash_merge(mhx_ctx *ctx, const uint64_t *x, const uint64_t *y, int64_t count, uint64_t *out, Where where) {
+    MHX_ENTER(ctx, ctx);
     MHX_REQUIRE(count >= 0, "count must be >= 0");
     if (count == 0) return MHX_OK;
-    MHX_REQUIRE(d_x && d_y && d_out, "NULL device pointer");
-    if (int rc = ctx->activate()) return rc;
-    return mhx::launch_minhash_merge(ctx, d_x, d_y, count, d_out);
+    MHX_REQUIRE_POINTERS(x && y && out, where);
+    MHX_TRY(ctx->activate());
+    if (where == kDevice) return mhx::launch_minhash_merge(ctx, x, y, count, out);
+    Stage s(ctx);
+    const auto p_x = s.piece(Stage::In, sizeof(uint64_t) * (size_t)count), p_y = s.piece(Stage::Out, p_x.bytes);
+    MHX_TRY(s.commit());
+    MHX_TRY(s.upload(p_x, x));
+    MHX_TRY(s.upload(p_y, y));
+    MHX_TRY(mhx::launch_minhash_merge(ctx, s.at<uint64_t>(p_x), s.at<uint64_t>(p_y), count, s.at<uint64_t>(p_x)));
+    return s.fetch(out, p_x);
+}
+
+int mhx_minhash_merge_dev(mhx_ctx *ctx, const uint64_t *d_x, const uint64_t *d_y, int64_t count, uint64_t *d_out) {
+    return minhash_merge(ctx, d_x, d_y, count, d_out, kDevice);
 }
 
 int mhx_minhash_merge(mhx_ctx *ctx, const uint64_t *x, const uint64_t *y, int64_t count, uint64_t *out) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    MHX_REQUIRE(count >= 0, "count must be >= 0");
-    if (count == 0) return MHX_OK;
-    MHX_REQUIRE(x && y && out, "NULL host pointer");
-    if (int rc = ctx->activate()) return rc;
-    const size_t bytes = sizeof(uint64_t) * (size_t)count;
-    if (int rc = ctx->ensure_scratch(0, bytes)) return rc;
-    if (int rc = ctx->ensure_scratch(2, bytes)) return rc;
-    uint64_t *dx = (uint64_t *)ctx->scratch[0], *dy = (uint64_t *)ctx->scratch[2];
-    MHX_HIP_CHECK(hipMemcpyAsync(dx, x, bytes, hipMemcpyHostToDevice, ctx->stream));
-    MHX_HIP_CHECK(hipMemcpyAsync(dy, y, bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = mhx::launch_minhash_merge(ctx, dx, dy, count, dx)) return rc;
-    MHX_HIP_CHECK(hipMemcpyAsync(out, dx, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return MHX_OK;
+    return minhash_merge(ctx, x, y, count, out, kHost);
 }
 
-// ---- packing -------------------------------------------------------------------------------
-int mhx_bbit_num_blocks(int32_t num_perm, int32_t b, int32_t *num_blocks) {
-    if (!num_blocks) return fail(MHX_ERR_INVALID, "num_blocks is NULL");
-    MHX_REQUIRE(b >= 0 && b <= 32, "b must be an integer in [0, 32]");
+// ---- packing, band digests, sorted bands, Lean records -----------------------------------------------------------------
+// One core per operation.  The host forms (where == kHost) take uint64 signatures: the matrix goes to In, the results come
+// back from Out.
+int mhx_bbit_num_blocks(int32_t num_perm, int32_t b, int32_t *num_blocks_out) {
+    if (!num_blocks_out) return fail(MHX_ERR_INVALID, "num_blocks is NULL");
+    MHX_CHECK_B(b);
     MHX_REQUIRE(num_perm > 0, "num_perm must be positive");
-    const int per = 64 / mhx::bbit_slot_size(b);
-    *num_blocks = (num_perm + per - 1) / per;
+    *num_blocks_out = num_blocks(num_perm, b);
     return MHX_OK;
 }
 
-int mhx_bbit_pack_dev(mhx_ctx *ctx, const uint64_t *d_sig, int64_t n, int32_t k, int32_t b,
-                      uint64_t *d_out) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    MHX_REQUIRE(b >= 0 && b <= 32, "b must be an integer in [0, 32]");
+static int bbit_pack(mhx_ctx *ctx, const void *sig, int sig_dtype, int64_t n, int32_t k, int32_t b, uint64_t *out, Where where) {
+    MHX_ENTER(ctx, ctx);
+    MHX_CHECK_DTYPE(sig_dtype);
+    MHX_CHECK_B(b);
     MHX_REQUIRE(k > 0 && n >= 0, "bad shape");
     if (n == 0) return MHX_OK;
-    MHX_REQUIRE(d_sig && d_out, "NULL device pointer");
-    if (int rc = ctx->activate()) return rc;
-    return mhx::launch_bbit_pack(ctx, d_sig, MHX_U64, n, k, b, d_out);
+    MHX_REQUIRE_POINTERS(sig && out, where);
+    MHX_TRY(ctx->activate());
+    auto launch = [&](const void *d_sig, void *d_out) { return mhx::launch_bbit_pack(ctx, d_sig, sig_dtype, n, k, b, (uint64_t *)d_out); };
+    if (where == kDevice) return launch(sig, out);
+    return through_scratch(ctx, sig, sizeof(uint64_t) * (size_t)(n * k), out, sizeof(uint64_t) * (size_t)(n * num_blocks(k, b)), launch);
 }
 
-int mhx_bbit_pack_dev_typed(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n, int32_t k, int32_t b,
-                            uint64_t *d_out) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    MHX_REQUIRE(sig_dtype == MHX_U64 || sig_dtype == MHX_U32, "bad sig_dtype %d", sig_dtype);
-    MHX_REQUIRE(b >= 0 && b <= 32, "b must be an integer in [0, 32]");
+int mhx_bbit_pack_dev_typed(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n, int32_t k, int32_t b, uint64_t *d_out) {
+    return bbit_pack(ctx, d_sig, sig_dtype, n, k, b, d_out, kDevice);
+}
+
+int mhx_bbit_pack_dev(mhx_ctx *ctx, const uint64_t *d_sig, int64_t n, int32_t k, int32_t b, uint64_t *d_out) {
+    return mhx_bbit_pack_dev_typed(ctx, d_sig, MHX_U64, n, k, b, d_out);
+}
+
+int mhx_bbit_pack(mhx_ctx *ctx, const uint64_t *sig, int64_t n, int32_t k, int32_t b, uint64_t *out) {
+    return bbit_pack(ctx, sig, MHX_U64, n, k, b, out, kHost);
+}
+
+static int bbit_unpack(mhx_ctx *ctx, const uint64_t *blocks, int64_t n, int32_t k, int32_t b, uint32_t *out, Where where) {
+    MHX_ENTER(ctx, ctx);
     MHX_REQUIRE(k > 0 && n >= 0, "bad shape");
+    MHX_CHECK_B(b);
     if (n == 0) return MHX_OK;
-    MHX_REQUIRE(d_sig && d_out, "NULL device pointer");
-    if (int rc = ctx->activate()) return rc;
-    return mhx::launch_bbit_pack(ctx, d_sig, sig_dtype, n, k, b, d_out);
+    MHX_REQUIRE_POINTERS(blocks && out, where);
+    MHX_TRY(ctx->activate());
+    auto launch = [&](const void *d_blocks, void *d_out) { return mhx::launch_bbit_unpack(ctx, (const uint64_t *)d_blocks, n, k, b, (uint32_t *)d_out); };
+    if (where == kDevice) return launch(blocks, out);
+    return through_scratch(ctx, blocks, sizeof(uint64_t) * (size_t)n * num_blocks(k, b), out, sizeof(uint32_t) * (size_t)n * k, launch);
+}
+
+int mhx_bbit_unpack_dev(mhx_ctx *ctx, const uint64_t *d_blocks, int64_t n, int32_t k, int32_t b, uint32_t *d_out) {
+    return bbit_unpack(ctx, d_blocks, n, k, b, d_out, kDevice);
+}
+
+int mhx_bbit_unpack(mhx_ctx *ctx, const uint64_t *blocks, int64_t n, int32_t k, int32_t b, uint32_t *out) {
+    return bbit_unpack(ctx, blocks, n, k, b, out, kHost);
+}
+
+static int band_keys(mhx_ctx *ctx, const uint64_t *sig, int64_t n, int32_t k, int32_t bands, int32_t r, uint64_t *out, Where where) {
+    MHX_ENTER(ctx, ctx);
+    MHX_CHECK_BANDS(bands, r, k);
+    MHX_REQUIRE(n >= 0, "bad shape");
+    if (n == 0) return MHX_OK;
+    MHX_REQUIRE_POINTERS(sig && out, where);
+    MHX_TRY(ctx->activate());
+    auto launch = [&](const void *d_sig, void *d_out) { return mhx::launch_band_keys(ctx, (const uint64_t *)d_sig, n, k, bands, r, (uint64_t *)d_out); };
+    if (where == kDevice) return launch(sig, out);
+    return through_scratch(ctx, sig, sizeof(uint64_t) * (size_t)(n * k), out, sizeof(uint64_t) * (size_t)(n * bands * r), launch);
+}
+
+int mhx_band_keys_dev(mhx_ctx *ctx, const uint64_t *d_sig, int64_t n, int32_t k, int32_t bands, int32_t r, uint64_t *d_out) {
+    return band_keys(ctx, d_sig, n, k, bands, r, d_out, kDevice);
+}
+
+int mhx_band_keys(mhx_ctx *ctx, const uint64_t *sig, int64_t n, int32_t k, int32_t bands, int32_t r, uint64_t *out) {
+    return band_keys(ctx, sig, n, k, bands, r, out, kHost);
+}
+
+static int band_digests(mhx_ctx *ctx, const void *sig, int sig_dtype, int64_t n, int32_t k, int32_t bands, int32_t r, int layout,
+                        uint64_t *out, Where where) {
+    MHX_ENTER(ctx, ctx);
+    MHX_CHECK_DTYPE(sig_dtype);
+    MHX_CHECK_BANDS(bands, r, k);
+    MHX_REQUIRE(n >= 0, "bad shape");
+    MHX_CHECK_LAYOUT(layout);
+    if (n == 0) return MHX_OK;
+    MHX_REQUIRE_POINTERS(sig && out, where);
+    MHX_TRY(ctx->activate());
+    auto launch = [&](const void *d_sig, void *d_out) { return mhx::launch_band_digests(ctx, d_sig, sig_dtype, n, k, bands, r, (uint64_t *)d_out, layout); };
+    if (where == kDevice) return launch(sig, out);
+    return through_scratch(ctx, sig, sizeof(uint64_t) * (size_t)(n * k), out, sizeof(uint64_t) * (size_t)(n * bands), launch);
 }
 
 int mhx_band_digests_layout_dev(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n, int32_t k, int32_t bands,
                                 int32_t r, int layout, uint64_t *d_out) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    MHX_REQUIRE(sig_dtype == MHX_U64 || sig_dtype == MHX_U32, "bad sig_dtype %d", sig_dtype);
-    MHX_REQUIRE(bands > 0 && r > 0 && (int64_t)bands * r <= k, "bands*r must be in (0, num_perm]");
-    MHX_REQUIRE(n >= 0, "bad shape");
-    MHX_REQUIRE(layout == MHX_ROW_MAJOR || layout == MHX_BAND_MAJOR, "bad layout %d", layout);
-    if (n == 0) return MHX_OK;
-    MHX_REQUIRE(d_sig && d_out, "NULL device pointer");
-    if (int rc = ctx->activate()) return rc;
-    return mhx::launch_band_digests(ctx, d_sig, sig_dtype, n, k, bands, r, d_out, layout);
+    return band_digests(ctx, d_sig, sig_dtype, n, k, bands, r, layout, d_out, kDevice);
 }
 
-int mhx_band_digests_dev_typed(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n, int32_t k, int32_t bands,
-                               int32_t r, uint64_t *d_out) {
+int mhx_band_digests_dev_typed(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n, int32_t k, int32_t bands, int32_t r, uint64_t *d_out) {
     return mhx_band_digests_layout_dev(ctx, d_sig, sig_dtype, n, k, bands, r, MHX_ROW_MAJOR, d_out);
+}
+
+int mhx_band_digests_dev(mhx_ctx *ctx, const uint64_t *d_sig, int64_t n, int32_t k, int32_t bands, int32_t r, uint64_t *d_out) {
+    return mhx_band_digests_layout_dev(ctx, d_sig, MHX_U64, n, k, bands, r, MHX_ROW_MAJOR, d_out);
+}
+
+int mhx_band_digests(mhx_ctx *ctx, const uint64_t *sig, int64_t n, int32_t k, int32_t bands, int32_t r, uint64_t *out) {
+    return band_digests(ctx, sig, MHX_U64, n, k, bands, r, MHX_ROW_MAJOR, out, kHost);
 }
 
 // b-bit blocks and band digests of the same matrix: one read when the shape allows the fused kernel, the two kernels otherwise
 int mhx_bbit_pack_band_digests_dev(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n, int32_t k, int32_t b,
                                    int32_t bands, int32_t r, int digest_layout, uint64_t *d_blocks, uint64_t *d_digests, int *fused) {
     if (fused) *fused = 0;
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    MHX_REQUIRE(sig_dtype == MHX_U64 || sig_dtype == MHX_U32, "bad sig_dtype %d", sig_dtype);
+    MHX_ENTER(ctx, ctx);
+    MHX_CHECK_DTYPE(sig_dtype);
     MHX_REQUIRE(b >= 1 && b <= 32, "b must be in [1, 32]");
-    MHX_REQUIRE(bands > 0 && r > 0 && (int64_t)bands * r <= k, "bands*r must be in (0, num_perm]");
+    MHX_CHECK_BANDS(bands, r, k);
     MHX_REQUIRE(n >= 0 && k > 0, "bad shape");
-    MHX_REQUIRE(digest_layout == MHX_ROW_MAJOR || digest_layout == MHX_BAND_MAJOR, "bad layout %d", digest_layout);
+    MHX_CHECK_LAYOUT(digest_layout);
     if (n == 0) return MHX_OK;
-    MHX_REQUIRE(d_sig && d_blocks && d_digests, "NULL device pointer");
-    if (int rc = ctx->activate()) return rc;
+    MHX_REQUIRE_POINTERS(d_sig && d_blocks && d_digests, kDevice);
+    MHX_TRY(ctx->activate());
     bool done = false;
     if (ctx->opt_pack_fused != 1)
-        if (int rc = mhx::launch_bbit_digest_fused(ctx, d_sig, sig_dtype, n, k, b, bands, r, d_blocks, d_digests, digest_layout, &done)) return rc;
+        MHX_TRY(mhx::launch_bbit_digest_fused(ctx, d_sig, sig_dtype, n, k, b, bands, r, d_blocks, d_digests, digest_layout, &done));
     if (fused) *fused = done ? 1 : 0;
     if (done) return MHX_OK;
-    if (int rc = mhx::launch_bbit_pack(ctx, d_sig, sig_dtype, n, k, b, d_blocks)) return rc;
+    MHX_TRY(mhx::launch_bbit_pack(ctx, d_sig, sig_dtype, n, k, b, d_blocks));
     return mhx::launch_band_digests(ctx, d_sig, sig_dtype, n, k, bands, r, d_digests, digest_layout);
+}
+
+static int lsh_sort_bands(mhx_ctx *ctx, const void *sig, int sig_dtype, int64_t n, int32_t k, int32_t bands, int32_t r,
+                          uint64_t *sorted_digests, uint32_t *sorted_rows, Where where) {
+    MHX_ENTER(ctx, ctx);
+    MHX_CHECK_DTYPE(sig_dtype);
+    MHX_CHECK_BANDS(bands, r, k);
+    MHX_REQUIRE(n >= 0, "bad shape");
+    if (n == 0) return MHX_OK;
+    MHX_REQUIRE_POINTERS(sig && sorted_digests && sorted_rows, where);
+    MHX_TRY(ctx->activate());
+    if (where == kDevice) return mhx::launch_lsh_sort_bands(ctx, sig, sig_dtype, n, k, bands, r, sorted_digests, sorted_rows);
+    Stage s(ctx);
+    const auto p_sig = s.piece(Stage::In, sizeof(uint64_t) * (size_t)(n * k));
+    const auto p_dig = s.piece(Stage::Out, sizeof(uint64_t) * (size_t)n * bands);
+    const auto p_rows = s.piece(Stage::Out, sizeof(uint32_t) * (size_t)n * bands);
+    MHX_TRY(s.commit());
+    MHX_TRY(s.upload(p_sig, sig));
+    MHX_TRY(mhx::launch_lsh_sort_bands(ctx, s.at<void>(p_sig), sig_dtype, n, k, bands, r, s.at<uint64_t>(p_dig), s.at<uint32_t>(p_rows)));
+    MHX_TRY(s.download(sorted_digests, p_dig));
+    return s.fetch(sorted_rows, p_rows);
 }
 
 int mhx_lsh_sort_bands_dev_typed(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n, int32_t k, int32_t bands,
                                  int32_t r, uint64_t *d_sorted_digests, uint32_t *d_sorted_rows) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    MHX_REQUIRE(sig_dtype == MHX_U64 || sig_dtype == MHX_U32, "bad sig_dtype %d", sig_dtype);
-    MHX_REQUIRE(bands > 0 && r > 0 && (int64_t)bands * r <= k, "bands*r must be in (0, num_perm]");
-    MHX_REQUIRE(n >= 0, "bad shape");
-    if (n == 0) return MHX_OK;
-    MHX_REQUIRE(d_sig && d_sorted_digests && d_sorted_rows, "NULL device pointer");
-    if (int rc = ctx->activate()) return rc;
-    return mhx::launch_lsh_sort_bands(ctx, d_sig, sig_dtype, n, k, bands, r, d_sorted_digests, d_sorted_rows);
-}
-
-int mhx_jaccard_pairs_dev_typed(mhx_ctx *ctx, const void *d_sig_a, const void *d_sig_b, int sig_dtype, int32_t k,
-                                const int64_t *d_pairs, int64_t n_pairs, int32_t *d_counts) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    MHX_REQUIRE(sig_dtype == MHX_U64 || sig_dtype == MHX_U32, "bad sig_dtype %d", sig_dtype);
-    MHX_REQUIRE(k > 0 && n_pairs >= 0, "bad shape");
-    if (n_pairs == 0) return MHX_OK;
-    MHX_REQUIRE(d_sig_a && d_sig_b && d_pairs && d_counts, "NULL device pointer");
-    if (int rc = ctx->activate()) return rc;
-    return mhx::launch_jaccard_pairs(ctx, d_sig_a, d_sig_b, sig_dtype, k, d_pairs, n_pairs, d_counts);
-}
-
-int mhx_band_keys_dev(mhx_ctx *ctx, const uint64_t *d_sig, int64_t n, int32_t k, int32_t bands,
-                      int32_t r, uint64_t *d_out) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    MHX_REQUIRE(bands > 0 && r > 0 && (int64_t)bands * r <= k, "bands*r must be in (0, num_perm]");
-    MHX_REQUIRE(n >= 0, "bad shape");
-    if (n == 0) return MHX_OK;
-    MHX_REQUIRE(d_sig && d_out, "NULL device pointer");
-    if (int rc = ctx->activate()) return rc;
-    return mhx::launch_band_keys(ctx, d_sig, n, k, bands, r, d_out);
-}
-
-int mhx_lean_serialize_dev(mhx_ctx *ctx, const uint64_t *d_sig, int64_t n, int32_t k, int64_t seed,
-                           uint8_t *d_out) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    MHX_REQUIRE(k > 0 && n >= 0, "bad shape");
-    if (n == 0) return MHX_OK;
-    MHX_REQUIRE(d_sig && d_out, "NULL device pointer");
-    if (int rc = ctx->activate()) return rc;
-    return mhx::launch_lean_serialize(ctx, d_sig, MHX_U64, n, k, seed, 0, d_out);
-}
-
-int mhx_lean_serialize_dev_typed(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n, int32_t k, int64_t seed, int byteorder,
-                                 uint8_t *d_out) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    MHX_REQUIRE(k > 0 && n >= 0, "bad shape");
-    MHX_REQUIRE(sig_dtype == MHX_U64 || sig_dtype == MHX_U32, "unknown sig_dtype %d", sig_dtype);
-    MHX_REQUIRE(byteorder == MHX_LITTLE_ENDIAN || byteorder == MHX_BIG_ENDIAN, "unknown byte order %d", byteorder);
-    if (n == 0) return MHX_OK;
-    MHX_REQUIRE(d_sig && d_out, "NULL device pointer");
-    if (int rc = ctx->activate()) return rc;
-    return mhx::launch_lean_serialize(ctx, d_sig, sig_dtype, n, k, seed, byteorder, d_out);
-}
-
-int mhx_lean_deserialize_dev(mhx_ctx *ctx, const uint8_t *d_records, int64_t n, int32_t k, int byteorder, int sig_dtype, void *d_sig,
-                             int64_t *d_seeds, uint32_t *d_bad) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    MHX_REQUIRE(k > 0 && n >= 0, "bad shape");
-    MHX_REQUIRE(sig_dtype == MHX_U64 || sig_dtype == MHX_U32, "unknown sig_dtype %d", sig_dtype);
-    MHX_REQUIRE(byteorder == MHX_LITTLE_ENDIAN || byteorder == MHX_BIG_ENDIAN, "unknown byte order %d", byteorder);
-    if (n == 0) return MHX_OK;
-    MHX_REQUIRE(d_records && d_sig, "NULL device pointer");
-    MHX_REQUIRE(((uintptr_t)d_records & 3) == 0, "records must be 4-byte aligned");
-    if (int rc = ctx->activate()) return rc;
-    return mhx::launch_lean_deserialize(ctx, d_records, n, k, byteorder, sig_dtype, d_sig, d_seeds, d_bad);
-}
-
-int mhx_bbit_unpack_dev(mhx_ctx *ctx, const uint64_t *d_blocks, int64_t n, int32_t k, int32_t b, uint32_t *d_out) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    MHX_REQUIRE(k > 0 && n >= 0, "bad shape");
-    MHX_REQUIRE(b >= 0 && b <= 32, "b must be in [0, 32]");
-    if (n == 0) return MHX_OK;
-    MHX_REQUIRE(d_blocks && d_out, "NULL device pointer");
-    if (int rc = ctx->activate()) return rc;
-    return mhx::launch_bbit_unpack(ctx, d_blocks, n, k, b, d_out);
-}
-
-// host wrappers: stage signature matrix in scratch[0], result in scratch[2]
-static int stage_sig(mhx_ctx *ctx, const uint64_t *sig, int64_t n, int32_t k, size_t out_bytes) {
-    if (int rc = ctx->activate()) return rc;
-    const size_t in_bytes = sizeof(uint64_t) * (size_t)(n * k);
-    if (int rc = ctx->ensure_scratch(0, in_bytes)) return rc;
-    if (int rc = ctx->ensure_scratch(2, out_bytes)) return rc;
-    MHX_HIP_CHECK(hipMemcpyAsync(ctx->scratch[0], sig, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    return MHX_OK;
-}
-
-static int fetch_out(mhx_ctx *ctx, void *out, size_t out_bytes) {
-    MHX_HIP_CHECK(hipMemcpyAsync(out, ctx->scratch[2], out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return MHX_OK;
-}
-
-int mhx_bbit_pack(mhx_ctx *ctx, const uint64_t *sig, int64_t n, int32_t k, int32_t b, uint64_t *out) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    int32_t nb = 0;
-    if (int rc = mhx_bbit_num_blocks(k, b, &nb)) return rc;
-    MHX_REQUIRE(n >= 0, "bad shape");
-    if (n == 0) return MHX_OK;
-    MHX_REQUIRE(sig && out, "NULL host pointer");
-    const size_t out_bytes = sizeof(uint64_t) * (size_t)(n * nb);
-    if (int rc = stage_sig(ctx, sig, n, k, out_bytes)) return rc;
-    if (int rc = mhx::launch_bbit_pack(ctx, ctx->scratch[0], MHX_U64, n, k, b, (uint64_t *)ctx->scratch[2]))
-        return rc;
-    return fetch_out(ctx, out, out_bytes);
-}
-
-int mhx_band_keys(mhx_ctx *ctx, const uint64_t *sig, int64_t n, int32_t k, int32_t bands, int32_t r,
-                  uint64_t *out) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    MHX_REQUIRE(bands > 0 && r > 0 && (int64_t)bands * r <= k, "bands*r must be in (0, num_perm]");
-    MHX_REQUIRE(n >= 0, "bad shape");
-    if (n == 0) return MHX_OK;
-    MHX_REQUIRE(sig && out, "NULL host pointer");
-    const size_t out_bytes = sizeof(uint64_t) * (size_t)(n * bands * r);
-    if (int rc = stage_sig(ctx, sig, n, k, out_bytes)) return rc;
-    if (int rc = mhx::launch_band_keys(ctx, (const uint64_t *)ctx->scratch[0], n, k, bands, r,
-                                       (uint64_t *)ctx->scratch[2]))
-        return rc;
-    return fetch_out(ctx, out, out_bytes);
-}
-
-int mhx_band_digests_dev(mhx_ctx *ctx, const uint64_t *d_sig, int64_t n, int32_t k, int32_t bands, int32_t r,
-                         uint64_t *d_out) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    MHX_REQUIRE(bands > 0 && r > 0 && (int64_t)bands * r <= k, "bands*r must be in (0, num_perm]");
-    MHX_REQUIRE(n >= 0, "bad shape");
-    if (n == 0) return MHX_OK;
-    MHX_REQUIRE(d_sig && d_out, "NULL device pointer");
-    if (int rc = ctx->activate()) return rc;
-    return mhx::launch_band_digests(ctx, d_sig, MHX_U64, n, k, bands, r, d_out);
-}
-
-int mhx_band_digests(mhx_ctx *ctx, const uint64_t *sig, int64_t n, int32_t k, int32_t bands, int32_t r,
-                     uint64_t *out) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    MHX_REQUIRE(bands > 0 && r > 0 && (int64_t)bands * r <= k, "bands*r must be in (0, num_perm]");
-    MHX_REQUIRE(n >= 0, "bad shape");
-    if (n == 0) return MHX_OK;
-    MHX_REQUIRE(sig && out, "NULL host pointer");
-    const size_t out_bytes = sizeof(uint64_t) * (size_t)(n * bands);
-    if (int rc = stage_sig(ctx, sig, n, k, out_bytes)) return rc;
-    if (int rc = mhx::launch_band_digests(ctx, ctx->scratch[0], MHX_U64, n, k, bands, r,
-                                          (uint64_t *)ctx->scratch[2]))
-        return rc;
-    return fetch_out(ctx, out, out_bytes);
-}
-
-int mhx_lsh_sort_digests_layout_dev(mhx_ctx *ctx, const uint64_t *d_digests, int64_t n, int32_t bands, int layout, uint64_t *d_sorted_digests,
-                             uint32_t *d_sorted_rows) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    MHX_REQUIRE(n >= 0 && bands > 0, "bad shape");
-    MHX_REQUIRE(layout == MHX_ROW_MAJOR || layout == MHX_BAND_MAJOR, "bad layout %d", layout);
-    if (n == 0) return MHX_OK;
-    MHX_REQUIRE(d_digests && d_sorted_digests && d_sorted_rows, "NULL device pointer");
-    if (int rc = ctx->activate()) return rc;
-    return mhx::launch_lsh_sort_bands(ctx, d_digests, layout == MHX_BAND_MAJOR ? mhx::kSigDigestsBM : mhx::kSigDigests, n, bands, bands, 1, d_sorted_digests, d_sorted_rows);
-}
-
-int mhx_lsh_sort_digests_dev(mhx_ctx *ctx, const uint64_t *d_digests, int64_t n, int32_t bands, uint64_t *d_sorted_digests,
-                             uint32_t *d_sorted_rows) {
-    return mhx_lsh_sort_digests_layout_dev(ctx, d_digests, n, bands, MHX_ROW_MAJOR, d_sorted_digests, d_sorted_rows);
+    return lsh_sort_bands(ctx, d_sig, sig_dtype, n, k, bands, r, d_sorted_digests, d_sorted_rows, kDevice);
 }
 
 int mhx_lsh_sort_bands_dev(mhx_ctx *ctx, const uint64_t *d_sig, int64_t n, int32_t k, int32_t bands, int32_t r,
                            uint64_t *d_sorted_digests, uint32_t *d_sorted_rows) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    MHX_REQUIRE(bands > 0 && r > 0 && (int64_t)bands * r <= k, "bands*r must be in (0, num_perm]");
-    MHX_REQUIRE(n >= 0, "bad shape");
-    if (n == 0) return MHX_OK;
-    MHX_REQUIRE(d_sig && d_sorted_digests && d_sorted_rows, "NULL device pointer");
-    if (int rc = ctx->activate()) return rc;
-    return mhx::launch_lsh_sort_bands(ctx, d_sig, MHX_U64, n, k, bands, r, d_sorted_digests, d_sorted_rows);
+    return mhx_lsh_sort_bands_dev_typed(ctx, d_sig, MHX_U64, n, k, bands, r, d_sorted_digests, d_sorted_rows);
 }
 
 int mhx_lsh_sort_bands(mhx_ctx *ctx, const uint64_t *sig, int64_t n, int32_t k, int32_t bands, int32_t r,
                        uint64_t *sorted_digests, uint32_t *sorted_rows) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    MHX_REQUIRE(bands > 0 && r > 0 && (int64_t)bands * r <= k, "bands*r must be in (0, num_perm]");
-    MHX_REQUIRE(n >= 0, "bad shape");
+    return lsh_sort_bands(ctx, sig, MHX_U64, n, k, bands, r, sorted_digests, sorted_rows, kHost);
+}
+
+int mhx_lsh_sort_digests_layout_dev(mhx_ctx *ctx, const uint64_t *d_digests, int64_t n, int32_t bands, int layout, uint64_t *d_sorted_digests,
+                                    uint32_t *d_sorted_rows) {
+    MHX_ENTER(ctx, ctx);
+    MHX_REQUIRE(n >= 0 && bands > 0, "bad shape");
+    MHX_CHECK_LAYOUT(layout);
     if (n == 0) return MHX_OK;
-    MHX_REQUIRE(sig && sorted_digests && sorted_rows, "NULL host pointer");
-    const size_t dig_bytes = sizeof(uint64_t) * (size_t)n * bands, row_bytes = sizeof(uint32_t) * (size_t)n * bands;
-    const size_t dig_pad = (dig_bytes + 255) & ~(size_t)255;
-    if (int rc = stage_sig(ctx, sig, n, k, dig_pad + row_bytes)) return rc;
-    uint64_t *d_dig = (uint64_t *)ctx->scratch[2];
-    uint32_t *d_rows = (uint32_t *)((char *)ctx->scratch[2] + dig_pad);
-    if (int rc = mhx::launch_lsh_sort_bands(ctx, ctx->scratch[0], MHX_U64, n, k, bands, r, d_dig, d_rows)) return rc;
-    MHX_HIP_CHECK(hipMemcpyAsync(sorted_digests, d_dig, dig_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    MHX_HIP_CHECK(hipMemcpyAsync(sorted_rows, d_rows, row_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return MHX_OK;
+    MHX_REQUIRE_POINTERS(d_digests && d_sorted_digests && d_sorted_rows, kDevice);
+    MHX_TRY(ctx->activate());
+    return mhx::launch_lsh_sort_bands(ctx, d_digests, layout == MHX_BAND_MAJOR ? mhx::kSigDigestsBM : mhx::kSigDigests, n, bands, bands, 1,
+                                      d_sorted_digests, d_sorted_rows);
+}
+
+int mhx_lsh_sort_digests_dev(mhx_ctx *ctx, const uint64_t *d_digests, int64_t n, int32_t bands, uint64_t *d_sorted_digests, uint32_t *d_sorted_rows) {
+    return mhx_lsh_sort_digests_layout_dev(ctx, d_digests, n, bands, MHX_ROW_MAJOR, d_sorted_digests, d_sorted_rows);
 }
 
 int mhx_lsh_candidate_pairs_dev(mhx_ctx *ctx, const uint64_t *d_sorted_digests, const uint32_t *d_sorted_rows, int64_t n,
                                 int32_t bands, int64_t *d_pairs, int64_t capacity, int64_t *n_pairs, int64_t *n_raw) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
+    MHX_ENTER(ctx, ctx);
     MHX_REQUIRE(n_pairs, "n_pairs is NULL");
     MHX_REQUIRE(bands > 0 && n >= 0 && capacity >= 0, "bad shape");
-    MHX_REQUIRE(n < ((int64_t)1 << 32), "more than 2^32-1 signatures per call");
+    MHX_CHECK_ROWS32(n);
     *n_pairs = 0;
     if (n_raw) *n_raw = 0;
     if (n == 0) return MHX_OK;
-    MHX_REQUIRE(d_sorted_digests && d_sorted_rows && (d_pairs || capacity == 0), "NULL device pointer");
-    if (int rc = ctx->activate()) return rc;
+    MHX_REQUIRE_POINTERS(d_sorted_digests && d_sorted_rows && (d_pairs || capacity == 0), kDevice);
+    MHX_TRY(ctx->activate());
     return mhx::launch_lsh_candidate_pairs(ctx, d_sorted_digests, d_sorted_rows, n, bands, d_pairs, capacity, n_pairs, n_raw);
 }
 
+// host signatures -> candidate pairs: the sort and the pair kernel back to back.  Out: sorted digests | sorted rows | pairs
 int mhx_lsh_candidate_pairs(mhx_ctx *ctx, const uint64_t *sig, int64_t n, int32_t k, int32_t bands, int32_t r,
                             int64_t *pairs, int64_t capacity, int64_t *n_pairs, int64_t *n_raw) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
+    MHX_ENTER(ctx, ctx);
     MHX_REQUIRE(n_pairs, "n_pairs is NULL");
-    MHX_REQUIRE(bands > 0 && r > 0 && (int64_t)bands * r <= k, "bands*r must be in (0, num_perm]");
+    MHX_CHECK_BANDS(bands, r, k);
     MHX_REQUIRE(n >= 0 && capacity >= 0, "bad shape");
     *n_pairs = 0;
     if (n_raw) *n_raw = 0;
     if (n == 0) return MHX_OK;
-    MHX_REQUIRE(sig && (pairs || capacity == 0), "NULL host pointer");
-    // scratch[2]: sorted digests | sorted rows | pairs
-    const size_t dig_bytes = ((sizeof(uint64_t) * (size_t)n * bands) + 255) & ~(size_t)255;
-    const size_t row_bytes = ((sizeof(uint32_t) * (size_t)n * bands) + 255) & ~(size_t)255;
-    const size_t pair_bytes = sizeof(int64_t) * 2 * (size_t)capacity;
-    if (int rc = stage_sig(ctx, sig, n, k, dig_bytes + row_bytes + pair_bytes)) return rc;
-    uint64_t *d_dig = (uint64_t *)ctx->scratch[2];
-    uint32_t *d_rows = (uint32_t *)((char *)ctx->scratch[2] + dig_bytes);
-    int64_t *d_pairs = (int64_t *)((char *)ctx->scratch[2] + dig_bytes + row_bytes);
-    if (int rc = mhx::launch_lsh_sort_bands(ctx, ctx->scratch[0], MHX_U64, n, k, bands, r, d_dig, d_rows)) return rc;
-    if (int rc = mhx::launch_lsh_candidate_pairs(ctx, d_dig, d_rows, n, bands, d_pairs, capacity, n_pairs, n_raw)) return rc;
-    if (*n_pairs > 0 && *n_pairs <= capacity)
-        MHX_HIP_CHECK(hipMemcpyAsync(pairs, d_pairs, sizeof(int64_t) * 2 * (size_t)*n_pairs, hipMemcpyDeviceToHost, ctx->stream));
-    MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return MHX_OK;
+    MHX_REQUIRE_POINTERS(sig && (pairs || capacity == 0), kHost);
+    MHX_TRY(ctx->activate());
+    Stage s(ctx);
+    const auto p_sig = s.piece(Stage::In, sizeof(uint64_t) * (size_t)(n * k));
+    const auto p_dig = s.piece(Stage::Out, sizeof(uint64_t) * (size_t)n * bands);
+    const auto p_rows = s.piece(Stage::Out, sizeof(uint32_t) * (size_t)n * bands);
+    const auto p_pairs = s.piece(Stage::Out, sizeof(int64_t) * 2 * (size_t)capacity);
+    MHX_TRY(s.commit());
+    MHX_TRY(s.upload(p_sig, sig));
+    MHX_TRY(mhx::launch_lsh_sort_bands(ctx, s.at<void>(p_sig), MHX_U64, n, k, bands, r, s.at<uint64_t>(p_dig), s.at<uint32_t>(p_rows)));
+    MHX_TRY(mhx::launch_lsh_candidate_pairs(ctx, s.at<uint64_t>(p_dig), s.at<uint32_t>(p_rows), n, bands, s.at<int64_t>(p_pairs), capacity,
+                                            n_pairs, n_raw));
+    if (*n_pairs > 0 && *n_pairs <= capacity) MHX_TRY(s.download(pairs, p_pairs, sizeof(int64_t) * 2 * (size_t)*n_pairs));
+    return s.synchronize();
 }
 
 int mhx_lsh_query_dev(mhx_ctx *ctx, const uint64_t *d_sorted_digests, const uint32_t *d_sorted_rows, int64_t n,
                       int32_t bands, int32_t r, const void *d_query_sig, const void *d_index_sig, int sig_dtype,
                       int32_t k, int64_t m, int64_t *d_pairs, int64_t capacity, int64_t *n_pairs) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
+    MHX_ENTER(ctx, ctx);
     MHX_REQUIRE(n_pairs, "n_pairs is NULL");
-    MHX_REQUIRE(sig_dtype == MHX_U64 || sig_dtype == MHX_U32, "bad sig_dtype %d", sig_dtype);
-    MHX_REQUIRE(bands > 0 && r > 0 && (int64_t)bands * r <= k, "bands*r must be in (0, num_perm]");
+    MHX_CHECK_DTYPE(sig_dtype);
+    MHX_CHECK_BANDS(bands, r, k);
     MHX_REQUIRE(n >= 0 && m >= 0 && capacity >= 0, "bad shape");
-    MHX_REQUIRE(n < ((int64_t)1 << 32) && m < ((int64_t)1 << 32), "more than 2^32-1 rows per call");
+    MHX_CHECK_ROWS32(n);
+    MHX_CHECK_ROWS32(m);
     *n_pairs = 0;
     if (n == 0 || m == 0) return MHX_OK;
-    MHX_REQUIRE(d_sorted_digests && d_sorted_rows && d_query_sig && (d_pairs || capacity == 0), "NULL device pointer");
-    if (int rc = ctx->activate()) return rc;
+    MHX_REQUIRE_POINTERS(d_sorted_digests && d_sorted_rows && d_query_sig && (d_pairs || capacity == 0), kDevice);
+    MHX_TRY(ctx->activate());
     return mhx::launch_lsh_query(ctx, d_sorted_digests, d_sorted_rows, n, bands, r, d_query_sig, d_index_sig, sig_dtype, k, m,
                                  d_pairs, capacity, n_pairs);
 }
 
-int mhx_jaccard_pairs_dev(mhx_ctx *ctx, const uint64_t *d_sig_a, const uint64_t *d_sig_b, int32_t k,
-                          const int64_t *d_pairs, int64_t n_pairs, int32_t *d_counts) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    MHX_REQUIRE(k > 0 && n_pairs >= 0, "bad shape");
-    if (n_pairs == 0) return MHX_OK;
-    MHX_REQUIRE(d_sig_a && d_sig_b && d_pairs && d_counts, "NULL device pointer");
-    if (int rc = ctx->activate()) return rc;
-    return mhx::launch_jaccard_pairs(ctx, d_sig_a, d_sig_b, MHX_U64, k, d_pairs, n_pairs, d_counts);
-}
-
-int mhx_jaccard_pairs(mhx_ctx *ctx, const uint64_t *sig, int64_t n, int32_t k, const int64_t *pairs,
-                      int64_t n_pairs, int32_t *counts) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
+// Agreeing positions of listed pairs.  b < 0: dense rows of sig_dtype, else b-bit blocks.  The host form takes the n rows
+// both ends of a pair index (In), the pairs (Aux) and returns the counts (Out).
+static int listed_pairs(mhx_ctx *ctx, const void *rows_a, const void *rows_b, int64_t n, int sig_dtype, int32_t k, int32_t b,
+                        const int64_t *pairs, int64_t n_pairs, int32_t *counts, Where where) {
+    MHX_ENTER(ctx, ctx);
+    MHX_CHECK_DTYPE(sig_dtype);
+    if (b >= 0) MHX_CHECK_B(b);
     MHX_REQUIRE(k > 0 && n >= 0 && n_pairs >= 0, "bad shape");
     if (n_pairs == 0) return MHX_OK;
-    MHX_REQUIRE(sig && pairs && counts, "NULL host pointer");
-    for (int64_t p = 0; p < 2 * n_pairs; ++p)
-        MHX_REQUIRE(pairs[p] >= 0 && pairs[p] < n, "pair index %lld out of range [0,%lld)", (long long)pairs[p], (long long)n);
-    const size_t out_bytes = sizeof(int32_t) * (size_t)n_pairs;
-    if (int rc = stage_sig(ctx, sig, n, k, out_bytes)) return rc;
-    if (int rc = ctx->ensure_scratch(1, sizeof(int64_t) * 2 * (size_t)n_pairs)) return rc;
-    MHX_HIP_CHECK(hipMemcpyAsync(ctx->scratch[1], pairs, sizeof(int64_t) * 2 * (size_t)n_pairs, hipMemcpyHostToDevice,
-                                 ctx->stream));
-    const uint64_t *d_sig = (const uint64_t *)ctx->scratch[0];
-    if (int rc = mhx::launch_jaccard_pairs(ctx, d_sig, d_sig, MHX_U64, k, (const int64_t *)ctx->scratch[1], n_pairs,
-                                           (int32_t *)ctx->scratch[2]))
-        return rc;
-    return fetch_out(ctx, counts, out_bytes);
+    MHX_REQUIRE_POINTERS(rows_a && rows_b && pairs && counts, where);
+    MHX_TRY(ctx->activate());
+    Stage s(ctx);
+    Stage::Piece p_counts{};
+    if (where == kHost) {
+        for (int64_t p = 0; p < 2 * n_pairs; ++p)
+            MHX_REQUIRE(pairs[p] >= 0 && pairs[p] < n, "pair index %lld out of range [0,%lld)", (long long)pairs[p], (long long)n);
+        const auto p_rows = s.piece(Stage::In, sizeof(uint64_t) * (size_t)n * (size_t)(b < 0 ? k : num_blocks(k, b)));
+        const auto p_pairs = s.piece(Stage::Aux, sizeof(int64_t) * 2 * (size_t)n_pairs);
+        p_counts = s.piece(Stage::Out, sizeof(int32_t) * (size_t)n_pairs);
+        MHX_TRY(s.commit());
+        MHX_TRY(s.upload(p_rows, rows_a));
+        MHX_TRY(s.upload(p_pairs, pairs));
+        rows_a = rows_b = s.at<void>(p_rows);
+        pairs = s.at<int64_t>(p_pairs);
+    }
+    int32_t *d_counts = where == kHost ? s.at<int32_t>(p_counts) : counts;
+    if (b < 0) MHX_TRY(mhx::launch_jaccard_pairs(ctx, rows_a, rows_b, sig_dtype, k, pairs, n_pairs, d_counts));
+    else MHX_TRY(mhx::launch_bbit_jaccard(ctx, (const uint64_t *)rows_a, (const uint64_t *)rows_b, k, b, pairs, n_pairs, d_counts));
+    return where == kHost ? s.fetch(counts, p_counts) : MHX_OK;
+}
+
+int mhx_jaccard_pairs_dev_typed(mhx_ctx *ctx, const void *d_sig_a, const void *d_sig_b, int sig_dtype, int32_t k,
+                                const int64_t *d_pairs, int64_t n_pairs, int32_t *d_counts) {
+    return listed_pairs(ctx, d_sig_a, d_sig_b, 0, sig_dtype, k, -1, d_pairs, n_pairs, d_counts, kDevice);
+}
+
+int mhx_jaccard_pairs_dev(mhx_ctx *ctx, const uint64_t *d_sig_a, const uint64_t *d_sig_b, int32_t k,
+                          const int64_t *d_pairs, int64_t n_pairs, int32_t *d_counts) {
+    return mhx_jaccard_pairs_dev_typed(ctx, d_sig_a, d_sig_b, MHX_U64, k, d_pairs, n_pairs, d_counts);
+}
+
+int mhx_jaccard_pairs(mhx_ctx *ctx, const uint64_t *sig, int64_t n, int32_t k, const int64_t *pairs, int64_t n_pairs, int32_t *counts) {
+    return listed_pairs(ctx, sig, sig, n, MHX_U64, k, -1, pairs, n_pairs, counts, kHost);
 }
 
 int mhx_bbit_jaccard_pairs_dev(mhx_ctx *ctx, const uint64_t *d_blocks_a, const uint64_t *d_blocks_b, int32_t k, int32_t b,
                                const int64_t *d_pairs, int64_t n_pairs, int32_t *d_counts) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    MHX_REQUIRE(b >= 0 && b <= 32, "b must be an integer in [0, 32]");
-    MHX_REQUIRE(k > 0 && n_pairs >= 0, "bad shape");
-    if (n_pairs == 0) return MHX_OK;
-    MHX_REQUIRE(d_blocks_a && d_blocks_b && d_pairs && d_counts, "NULL device pointer");
-    if (int rc = ctx->activate()) return rc;
-    return mhx::launch_bbit_jaccard(ctx, d_blocks_a, d_blocks_b, k, b, d_pairs, n_pairs, d_counts);
+    MHX_CHECK_B(b);
+    return listed_pairs(ctx, d_blocks_a, d_blocks_b, 0, MHX_U64, k, b, d_pairs, n_pairs, d_counts, kDevice);
 }
 
 int mhx_bbit_jaccard_pairs(mhx_ctx *ctx, const uint64_t *blocks, int64_t n, int32_t k, int32_t b, const int64_t *pairs,
                            int64_t n_pairs, int32_t *counts) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    int32_t nb = 0;
-    if (int rc = mhx_bbit_num_blocks(k, b, &nb)) return rc;
-    MHX_REQUIRE(n >= 0 && n_pairs >= 0, "bad shape");
-    if (n_pairs == 0) return MHX_OK;
-    MHX_REQUIRE(blocks && pairs && counts, "NULL host pointer");
-    for (int64_t p = 0; p < 2 * n_pairs; ++p)
-        MHX_REQUIRE(pairs[p] >= 0 && pairs[p] < n, "pair index %lld out of range [0,%lld)", (long long)pairs[p], (long long)n);
-    if (int rc = ctx->activate()) return rc;
-    const size_t in_bytes = sizeof(uint64_t) * (size_t)n * (size_t)nb, pair_bytes = sizeof(int64_t) * 2 * (size_t)n_pairs;
-    const size_t out_bytes = sizeof(int32_t) * (size_t)n_pairs;
-    if (int rc = ctx->ensure_scratch(0, in_bytes)) return rc;
-    if (int rc = ctx->ensure_scratch(1, pair_bytes)) return rc;
-    if (int rc = ctx->ensure_scratch(2, out_bytes)) return rc;
-    MHX_HIP_CHECK(hipMemcpyAsync(ctx->scratch[0], blocks, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    MHX_HIP_CHECK(hipMemcpyAsync(ctx->scratch[1], pairs, pair_bytes, hipMemcpyHostToDevice, ctx->stream));
-    const uint64_t *d_blocks = (const uint64_t *)ctx->scratch[0];
-    if (int rc = mhx::launch_bbit_jaccard(ctx, d_blocks, d_blocks, k, b, (const int64_t *)ctx->scratch[1], n_pairs,
-                                          (int32_t *)ctx->scratch[2]))
-        return rc;
-    return fetch_out(ctx, counts, out_bytes);
+    MHX_CHECK_B(b);
+    return listed_pairs(ctx, blocks, blocks, n, MHX_U64, k, b, pairs, n_pairs, counts, kHost);
+}
+
+static int lean_serialize(mhx_ctx *ctx, const void *sig, int sig_dtype, int64_t n, int32_t k, int64_t seed, int byteorder, uint8_t *out,
+                          Where where) {
+    MHX_ENTER(ctx, ctx);
+    MHX_REQUIRE(k > 0 && n >= 0, "bad shape");
+    MHX_CHECK_DTYPE(sig_dtype);
+    MHX_CHECK_BYTEORDER(byteorder);
+    if (n == 0) return MHX_OK;
+    MHX_REQUIRE_POINTERS(sig && out, where);
+    MHX_TRY(ctx->activate());
+    auto launch = [&](const void *d_sig, void *d_out) { return mhx::launch_lean_serialize(ctx, d_sig, sig_dtype, n, k, seed, byteorder, (uint8_t *)d_out); };
+    if (where == kDevice) return launch(sig, out);
+    return through_scratch(ctx, sig, sizeof(uint64_t) * (size_t)(n * k), out, (size_t)n * (12 + 4 * (size_t)k), launch);
+}
+
+int mhx_lean_serialize_dev_typed(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n, int32_t k, int64_t seed, int byteorder, uint8_t *d_out) {
+    return lean_serialize(ctx, d_sig, sig_dtype, n, k, seed, byteorder, d_out, kDevice);
+}
+
+int mhx_lean_serialize_dev(mhx_ctx *ctx, const uint64_t *d_sig, int64_t n, int32_t k, int64_t seed, uint8_t *d_out) {
+    return mhx_lean_serialize_dev_typed(ctx, d_sig, MHX_U64, n, k, seed, MHX_LITTLE_ENDIAN, d_out);
 }
 
 int mhx_lean_serialize(mhx_ctx *ctx, const uint64_t *sig, int64_t n, int32_t k, int64_t seed, uint8_t *out) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    MHX_REQUIRE(k > 0 && n >= 0, "bad shape");
-    if (n == 0) return MHX_OK;
-    MHX_REQUIRE(sig && out, "NULL host pointer");
-    const size_t out_bytes = (size_t)n * (12 + 4 * (size_t)k);
-    if (int rc = stage_sig(ctx, sig, n, k, out_bytes)) return rc;
-    if (int rc = mhx::launch_lean_serialize(ctx, ctx->scratch[0], MHX_U64, n, k, seed, 0, (uint8_t *)ctx->scratch[2]))
-        return rc;
-    return fetch_out(ctx, out, out_bytes);
+    return lean_serialize(ctx, sig, MHX_U64, n, k, seed, MHX_LITTLE_ENDIAN, out, kHost);
 }
 
-// records (host) -> [n, k] uint64 hashvalues + seeds; a record whose length field is not k: MHX_ERR_INVALID, nothing written
-int mhx_lean_deserialize(mhx_ctx *ctx, const uint8_t *records, int64_t n, int32_t k, int byteorder, uint64_t *sig, int64_t *seeds) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
+// records -> [n, k] hashvalues + seeds.  The host form: a record whose length field is not k: MHX_ERR_INVALID, nothing written
+static int lean_deserialize(mhx_ctx *ctx, const uint8_t *records, int64_t n, int32_t k, int byteorder, int sig_dtype, void *sig,
+                            int64_t *seeds, uint32_t *d_bad, Where where) {
+    MHX_ENTER(ctx, ctx);
     MHX_REQUIRE(k > 0 && n >= 0, "bad shape");
-    MHX_REQUIRE(byteorder == MHX_LITTLE_ENDIAN || byteorder == MHX_BIG_ENDIAN, "unknown byte order %d", byteorder);
+    MHX_CHECK_DTYPE(sig_dtype);
+    MHX_CHECK_BYTEORDER(byteorder);
     if (n == 0) return MHX_OK;
-    MHX_REQUIRE(records && sig, "NULL host pointer");
-    if (int rc = ctx->activate()) return rc;
-    const size_t rec_bytes = (size_t)n * (12 + 4 * (size_t)k), sig_bytes = sizeof(uint64_t) * (size_t)n * k;
-    const size_t seeds_at = (sig_bytes + 255) & ~(size_t)255, bad_at = seeds_at + (((size_t)n * 8 + 255) & ~(size_t)255);
-    if (int rc = ctx->ensure_scratch(0, rec_bytes)) return rc;
-    if (int rc = ctx->ensure_scratch(2, bad_at + 256)) return rc;
-    char *base = (char *)ctx->scratch[2];
-    unsigned int *d_bad = (unsigned int *)(base + bad_at);
-    MHX_HIP_CHECK(hipMemcpyAsync(ctx->scratch[0], records, rec_bytes, hipMemcpyHostToDevice, ctx->stream));
-    MHX_HIP_CHECK(hipMemsetAsync(d_bad, 0, sizeof(unsigned int), ctx->stream));
-    if (int rc = mhx::launch_lean_deserialize(ctx, (const uint8_t *)ctx->scratch[0], n, k, byteorder, MHX_U64, base, (int64_t *)(base + seeds_at), d_bad))
-        return rc;
+    MHX_REQUIRE_POINTERS(records && sig, where);
+    if (where == kDevice) MHX_REQUIRE(((uintptr_t)records & 3) == 0, "records must be 4-byte aligned");
+    MHX_TRY(ctx->activate());
+    if (where == kDevice) return mhx::launch_lean_deserialize(ctx, records, n, k, byteorder, sig_dtype, sig, seeds, d_bad);
+    Stage s(ctx);
+    const auto p_rec = s.piece(Stage::In, (size_t)n * (12 + 4 * (size_t)k));
+    const auto p_sig = s.piece(Stage::Out, sizeof(uint64_t) * (size_t)n * k);
+    const auto p_seeds = s.piece(Stage::Out, (size_t)n * 8);
+    const auto p_bad = s.piece(Stage::Out, sizeof(unsigned int));
+    s.ask(Stage::Out, p_bad.at + 256);
+    MHX_TRY(s.commit());
+    MHX_TRY(s.upload(p_rec, records));
+    MHX_HIP_CHECK(hipMemsetAsync(s.at<void>(p_bad), 0, sizeof(unsigned int), ctx->stream));
+    MHX_TRY(mhx::launch_lean_deserialize(ctx, s.at<uint8_t>(p_rec), n, k, byteorder, sig_dtype, s.at<void>(p_sig), s.at<int64_t>(p_seeds),
+                                         s.at<unsigned int>(p_bad)));
     unsigned int bad = 0;
-    MHX_HIP_CHECK(hipMemcpyAsync(&bad, d_bad, sizeof(bad), hipMemcpyDeviceToHost, ctx->stream));
-    MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    MHX_TRY(s.fetch(&bad, p_bad));
     if (bad) return fail(MHX_ERR_INVALID, "%u of %lld records do not hold %d hash values (length field)", bad, (long long)n, k);
-    MHX_HIP_CHECK(hipMemcpyAsync(sig, base, sig_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    if (seeds) MHX_HIP_CHECK(hipMemcpyAsync(seeds, base + seeds_at, (size_t)n * 8, hipMemcpyDeviceToHost, ctx->stream));
-    MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return MHX_OK;
+    MHX_TRY(s.download(sig, p_sig));
+    if (seeds) MHX_TRY(s.download(seeds, p_seeds));
+    return s.synchronize();
 }
 
-int mhx_bbit_unpack(mhx_ctx *ctx, const uint64_t *blocks, int64_t n, int32_t k, int32_t b, uint32_t *out) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    MHX_REQUIRE(k > 0 && n >= 0, "bad shape");
-    MHX_REQUIRE(b >= 0 && b <= 32, "b must be in [0, 32]");
-    if (n == 0) return MHX_OK;
-    MHX_REQUIRE(blocks && out, "NULL host pointer");
-    if (int rc = ctx->activate()) return rc;
-    int32_t nb = 0;
-    if (int rc = mhx_bbit_num_blocks(k, b, &nb)) return rc;
-    const size_t in_bytes = sizeof(uint64_t) * (size_t)n * nb, out_bytes = sizeof(uint32_t) * (size_t)n * k;
-    if (int rc = ctx->ensure_scratch(0, in_bytes)) return rc;
-    if (int rc = ctx->ensure_scratch(2, out_bytes)) return rc;
-    MHX_HIP_CHECK(hipMemcpyAsync(ctx->scratch[0], blocks, in_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = mhx::launch_bbit_unpack(ctx, (const uint64_t *)ctx->scratch[0], n, k, b, (uint32_t *)ctx->scratch[2])) return rc;
-    return fetch_out(ctx, out, out_bytes);
+int mhx_lean_deserialize_dev(mhx_ctx *ctx, const uint8_t *d_records, int64_t n, int32_t k, int byteorder, int sig_dtype, void *d_sig,
+                             int64_t *d_seeds, uint32_t *d_bad) {
+    return lean_deserialize(ctx, d_records, n, k, byteorder, sig_dtype, d_sig, d_seeds, d_bad, kDevice);
+}
+
+int mhx_lean_deserialize(mhx_ctx *ctx, const uint8_t *records, int64_t n, int32_t k, int byteorder, uint64_t *sig, int64_t *seeds) {
+    return lean_deserialize(ctx, records, n, k, byteorder, MHX_U64, sig, seeds, nullptr, kHost);
 }
 
 // ---- weighted ------------------------------------------------------------------------------
@@ -1595,89 +1538,59 @@ int mhx_wgen_destroy(mhx_wgen *gen) {
     return MHX_OK;
 }
 
-int mhx_weighted_minhash_many_dev(mhx_wgen *gen, const int64_t *d_indptr, const int32_t *d_indices,
-                                  const float *d_values, int values_are_logs, int64_t n_rows,
-                                  int64_t nnz, int64_t *d_out, uint8_t *d_nonempty) {
-    if (!gen) return fail(MHX_ERR_INVALID, "gen is NULL");
-    MHX_GUARD(gen->ctx);
+int mhx_weighted_minhash_many_dev(mhx_wgen *gen, const int64_t *d_indptr, const int32_t *d_indices, const float *d_values, int values_are_logs,
+                                  int64_t n_rows, int64_t nnz, int64_t *d_out, uint8_t *d_nonempty) {
+    MHX_ENTER(gen, gen->ctx);
     MHX_REQUIRE(n_rows >= 0 && nnz >= 0, "bad shape");
     if (n_rows == 0) return MHX_OK;
-    MHX_REQUIRE(d_indptr && d_out && d_nonempty, "NULL device pointer");
-    MHX_REQUIRE((d_indices && d_values) || nnz == 0, "NULL device pointer");
-    if (int rc = gen->ctx->activate()) return rc;
+    MHX_REQUIRE_POINTERS(d_indptr && d_out && d_nonempty, kDevice);
+    MHX_REQUIRE_POINTERS((d_indices && d_values) || nnz == 0, kDevice);
+    MHX_TRY(gen->ctx->activate());
     return mhx::launch_weighted(gen, d_indptr, d_indices, d_values, values_are_logs, n_rows, nnz, d_out,
                                 d_nonempty);
 }
 
-int mhx_weighted_minhash_many(mhx_wgen *gen, const int64_t *indptr, const int32_t *indices,
-                              const float *values, int values_are_logs, int64_t n_rows, int64_t *out,
-                              uint8_t *nonempty) {
-    if (!gen) return fail(MHX_ERR_INVALID, "gen is NULL");
-    MHX_GUARD(gen->ctx);
+// CSR rows on the host.  In: indices | values;  Aux: indptr;  Out: samples | nonempty
+int mhx_weighted_minhash_many(mhx_wgen *gen, const int64_t *indptr, const int32_t *indices, const float *values, int values_are_logs, int64_t n_rows,
+                              int64_t *out, uint8_t *nonempty) {
+    MHX_ENTER(gen, gen->ctx);
     MHX_REQUIRE(n_rows >= 0, "bad shape");
     if (n_rows == 0) return MHX_OK;
-    MHX_REQUIRE(indptr && out && nonempty, "NULL host pointer");
+    MHX_REQUIRE_POINTERS(indptr && out && nonempty, kHost);
     mhx_ctx *ctx = gen->ctx;
-    if (int rc = ctx->activate()) return rc;
+    MHX_TRY(ctx->activate());
     for (int64_t i = 0; i < n_rows; ++i)
         MHX_REQUIRE(indptr[i + 1] >= indptr[i], "indptr must be non-decreasing (row %lld)", (long long)i);
     MHX_REQUIRE(indptr[0] == 0, "indptr[0] must be 0");
     const int64_t nnz = indptr[n_rows];
-    MHX_REQUIRE((indices && values) || nnz == 0, "NULL host pointer");
+    MHX_REQUIRE_POINTERS((indices && values) || nnz == 0, kHost);
     for (int64_t j = 0; j < nnz; ++j)
         MHX_REQUIRE(indices[j] >= 0 && indices[j] < gen->dim, "column index %d out of range [0,%d)", indices[j], gen->dim);
-    const size_t ptr_bytes = sizeof(int64_t) * (size_t)(n_rows + 1);
-    const size_t idx_bytes = ((sizeof(int32_t) * (size_t)nnz) + 255) & ~(size_t)255;
-    const size_t val_bytes = sizeof(float) * (size_t)nnz;
-    const size_t out_bytes = sizeof(int64_t) * 2 * (size_t)gen->sample_size * (size_t)n_rows;
-    const size_t ne_off = (out_bytes + 255) & ~(size_t)255;
-    if (int rc = ctx->ensure_scratch(0, idx_bytes + val_bytes + 256)) return rc;
-    if (int rc = ctx->ensure_scratch(1, ptr_bytes)) return rc;
-    if (int rc = ctx->ensure_scratch(2, ne_off + (size_t)n_rows)) return rc;
-    int32_t *d_idx = (int32_t *)ctx->scratch[0];
-    float *d_val = (float *)((char *)ctx->scratch[0] + idx_bytes);
-    int64_t *d_ptr = (int64_t *)ctx->scratch[1];
-    int64_t *d_out = (int64_t *)ctx->scratch[2];
-    uint8_t *d_ne = (uint8_t *)ctx->scratch[2] + ne_off;
-    MHX_HIP_CHECK(hipMemcpyAsync(d_ptr, indptr, ptr_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (nnz) {
-        MHX_HIP_CHECK(hipMemcpyAsync(d_idx, indices, sizeof(int32_t) * (size_t)nnz, hipMemcpyHostToDevice, ctx->stream));
-        MHX_HIP_CHECK(hipMemcpyAsync(d_val, values, val_bytes, hipMemcpyHostToDevice, ctx->stream));
-    }
-    if (int rc = mhx::launch_weighted(gen, d_ptr, d_idx, d_val, values_are_logs, n_rows, nnz, d_out, d_ne))
-        return rc;
-    MHX_HIP_CHECK(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    MHX_HIP_CHECK(hipMemcpyAsync(nonempty, d_ne, (size_t)n_rows, hipMemcpyDeviceToHost, ctx->stream));
-    MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return MHX_OK;
+    Stage s(ctx);
+    const auto p_idx = s.piece(Stage::In, sizeof(int32_t) * (size_t)nnz);
+    const auto p_val = s.piece(Stage::In, sizeof(float) * (size_t)nnz);
+    const auto p_ptr = s.piece(Stage::Aux, sizeof(int64_t) * (size_t)(n_rows + 1));
+    const auto p_out = s.piece(Stage::Out, sizeof(int64_t) * 2 * (size_t)gen->sample_size * (size_t)n_rows);
+    const auto p_ne = s.piece(Stage::Out, (size_t)n_rows);
+    s.ask(Stage::In, p_val.at + p_val.bytes + 256);
+    MHX_TRY(s.commit());
+    MHX_TRY(s.upload(p_ptr, indptr));
+    MHX_TRY(s.upload(p_idx, indices));
+    MHX_TRY(s.upload(p_val, values));
+    MHX_TRY(mhx::launch_weighted(gen, s.at<int64_t>(p_ptr), s.at<int32_t>(p_idx), s.at<float>(p_val), values_are_logs, n_rows, nnz,
+                                 s.at<int64_t>(p_out), s.at<uint8_t>(p_ne)));
+    MHX_TRY(s.download(out, p_out));
+    return s.fetch(nonempty, p_ne);
 }
 
 int mhx_weighted_logf(mhx_ctx *ctx, const float *x, int64_t n, float *out) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
+    MHX_ENTER(ctx, ctx);
     MHX_REQUIRE(n >= 0, "bad shape");
     if (n == 0) return MHX_OK;
-    MHX_REQUIRE(x && out, "NULL host pointer");
-    if (int rc = ctx->activate()) return rc;
-    const size_t bytes = sizeof(float) * (size_t)n;
-    if (int rc = ctx->ensure_scratch(0, bytes)) return rc;
-    if (int rc = ctx->ensure_scratch(2, bytes)) return rc;
-    MHX_HIP_CHECK(hipMemcpyAsync(ctx->scratch[0], x, bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = mhx::launch_weighted_log(ctx, (const float *)ctx->scratch[0], n, (float *)ctx->scratch[2])) return rc;
-    MHX_HIP_CHECK(hipMemcpyAsync(out, ctx->scratch[2], bytes, hipMemcpyDeviceToHost, ctx->stream));
-    MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return MHX_OK;
-}
-
-int mhx_weighted_minhash_many_dense_dev(mhx_wgen *gen, const float *d_x, int values_are_logs, int64_t n_rows,
-                                        int64_t *d_out, uint8_t *d_nonempty) {
-    if (!gen) return fail(MHX_ERR_INVALID, "gen is NULL");
-    MHX_GUARD(gen->ctx);
-    MHX_REQUIRE(n_rows >= 0, "bad shape");
-    if (n_rows == 0) return MHX_OK;
-    MHX_REQUIRE(d_x && d_out && d_nonempty, "NULL device pointer");
-    if (int rc = gen->ctx->activate()) return rc;
-    return mhx::launch_weighted_dense(gen, d_x, values_are_logs, n_rows, d_out, d_nonempty);
+    MHX_REQUIRE_POINTERS(x && out, kHost);
+    MHX_TRY(ctx->activate());
+    return through_scratch(ctx, x, sizeof(float) * (size_t)n, out, sizeof(float) * (size_t)n,
+                           [&](const void *d_x, void *d_out) { return mhx::launch_weighted_log(ctx, (const float *)d_x, n, (float *)d_out); });
 }
 
 }  // extern "C" (the feed's state and helpers are C++)
@@ -1808,19 +1721,18 @@ int mhx_weighted_dense_end(mhx_wfeed *f) {
     return rc;
 }
 
-int mhx_weighted_minhash_many_dense(mhx_wgen *gen, const float *x, int values_are_logs, int64_t n_rows, int64_t *out,
-                                    uint8_t *nonempty) {
-    if (!gen) return fail(MHX_ERR_INVALID, "gen is NULL");
-    MHX_GUARD(gen->ctx);
+static int weighted_dense(mhx_wgen *gen, const float *x, int values_are_logs, int64_t n_rows, int64_t *out, uint8_t *nonempty, Where where) {
+    MHX_ENTER(gen, gen->ctx);
     MHX_REQUIRE(n_rows >= 0, "bad shape");
     if (n_rows == 0) return MHX_OK;
-    MHX_REQUIRE(x && out && nonempty, "NULL host pointer");
+    MHX_REQUIRE_POINTERS(x && out && nonempty, where);
     mhx_ctx *ctx = gen->ctx;
-    if (int rc = ctx->activate()) return rc;
+    MHX_TRY(ctx->activate());
+    if (where == kDevice) return mhx::launch_weighted_dense(gen, x, values_are_logs, n_rows, out, nonempty);
     const int64_t piece = dense_piece_rows(gen);
     if (n_rows >= 2 * piece && ctx->opt_host_chunk_bytes >= 0) {  // upload, evaluation and download side by side
         mhx_wfeed *f = nullptr;
-        if (int rc = mhx_weighted_dense_begin(gen, values_are_logs, piece, &f)) return rc;
+        MHX_TRY(mhx_weighted_dense_begin(gen, values_are_logs, piece, &f));
         int rc = MHX_OK;
         for (int64_t lo = 0; lo < n_rows && !rc; lo += piece) {
             const int64_t rows = std::min(piece, n_rows - lo);
@@ -1830,247 +1742,209 @@ int mhx_weighted_minhash_many_dense(mhx_wgen *gen, const float *x, int values_ar
         const int rc_end = mhx_weighted_dense_end(f);
         return rc ? rc : rc_end;
     }
-    const size_t x_bytes = sizeof(float) * (size_t)n_rows * (size_t)gen->dim;
-    const size_t out_bytes = sizeof(int64_t) * 2 * (size_t)gen->sample_size * (size_t)n_rows;
-    const size_t ne_off = (out_bytes + 255) & ~(size_t)255;
-    if (int rc = ctx->ensure_scratch(0, x_bytes)) return rc;
-    if (int rc = ctx->ensure_scratch(2, ne_off + (size_t)n_rows)) return rc;
-    float *d_x = (float *)ctx->scratch[0];
-    int64_t *d_out = (int64_t *)ctx->scratch[2];
-    uint8_t *d_ne = (uint8_t *)ctx->scratch[2] + ne_off;
-    MHX_HIP_CHECK(hipMemcpyAsync(d_x, x, x_bytes, hipMemcpyHostToDevice, ctx->stream));
-    if (int rc = mhx::launch_weighted_dense(gen, d_x, values_are_logs, n_rows, d_out, d_ne)) return rc;
-    MHX_HIP_CHECK(hipMemcpyAsync(out, d_out, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-    MHX_HIP_CHECK(hipMemcpyAsync(nonempty, d_ne, (size_t)n_rows, hipMemcpyDeviceToHost, ctx->stream));
-    MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return MHX_OK;
+    Stage s(ctx);
+    const auto p_x = s.piece(Stage::In, sizeof(float) * (size_t)n_rows * (size_t)gen->dim);
+    const auto p_out = s.piece(Stage::Out, sizeof(int64_t) * 2 * (size_t)gen->sample_size * (size_t)n_rows);
+    const auto p_ne = s.piece(Stage::Out, (size_t)n_rows);
+    MHX_TRY(s.commit());
+    MHX_TRY(s.upload(p_x, x));
+    MHX_TRY(mhx::launch_weighted_dense(gen, s.at<float>(p_x), values_are_logs, n_rows, s.at<int64_t>(p_out), s.at<uint8_t>(p_ne)));
+    MHX_TRY(s.download(out, p_out));
+    return s.fetch(nonempty, p_ne);
+}
+
+int mhx_weighted_minhash_many_dense_dev(mhx_wgen *gen, const float *d_x, int values_are_logs, int64_t n_rows, int64_t *d_out, uint8_t *d_nonempty) {
+    return weighted_dense(gen, d_x, values_are_logs, n_rows, d_out, d_nonempty, kDevice);
+}
+
+int mhx_weighted_minhash_many_dense(mhx_wgen *gen, const float *x, int values_are_logs, int64_t n_rows, int64_t *out, uint8_t *nonempty) {
+    return weighted_dense(gen, x, values_are_logs, n_rows, out, nonempty, kHost);
 }
 
 // ---- all-pairs Jaccard (jaccard_kernels.hip) -------------------------------------------------
 // Shared argument checks.  b < 0: dense rows of sig_dtype, else b-bit blocks.
 static int check_all_pairs(int64_t n_a, int64_t n_b, int sig_dtype, int32_t k, int32_t b) {
-    MHX_REQUIRE(sig_dtype == MHX_U64 || sig_dtype == MHX_U32, "bad sig_dtype %d", sig_dtype);
-    MHX_REQUIRE(b < 0 || b <= 32, "b must be an integer in [0, 32]");
+    MHX_CHECK_DTYPE(sig_dtype);
+    if (b >= 0) MHX_CHECK_B(b);
     MHX_REQUIRE(k > 0, "num_perm must be positive");
     MHX_REQUIRE(n_a >= 0 && n_b >= 0, "bad shape");
-    MHX_REQUIRE(n_a < ((int64_t)1 << 32) && n_b < ((int64_t)1 << 32), "more than 2^32-1 rows per call");
+    MHX_CHECK_ROWS32(n_a);
+    MHX_CHECK_ROWS32(n_b);
     return MHX_OK;
 }
 
-static int all_pairs_matrix_dev(mhx_ctx *ctx, const void *d_a, int64_t n_a, const void *d_b, int64_t n_b, int sig_dtype,
-                                int32_t k, int32_t b, int32_t *d_counts, int64_t ldc) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    if (int rc = check_all_pairs(n_a, n_b, sig_dtype, k, b)) return rc;
-    if (!d_b) n_b = n_a;
-    MHX_REQUIRE(ldc >= n_b, "ldc must be >= n_b");
-    if (n_a == 0 || n_b == 0) return MHX_OK;
-    MHX_REQUIRE(d_a && d_counts, "NULL device pointer");
-    if (int rc = ctx->activate()) return rc;
-    return mhx::launch_jaccard_matrix(ctx, d_a, n_a, d_b ? d_b : d_a, n_b, sig_dtype, k, b, d_counts, ldc);
-}
-
-static int all_pairs_threshold_dev(mhx_ctx *ctx, const void *d_a, int64_t n_a, const void *d_b, int64_t n_b, int sig_dtype,
-                                   int32_t k, int32_t b, int32_t min_count, int64_t *d_pairs, int32_t *d_counts, int64_t capacity,
-                                   int64_t *n_pairs) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    MHX_REQUIRE(n_pairs, "n_pairs is NULL");
-    *n_pairs = 0;
-    if (int rc = check_all_pairs(n_a, n_b, sig_dtype, k, b)) return rc;
-    MHX_REQUIRE(capacity >= 0, "bad capacity");
-    if (!d_b) n_b = n_a;
-    if (n_a == 0 || n_b == 0 || min_count > k) return MHX_OK;
-    MHX_REQUIRE(d_a && ((d_pairs && d_counts) || capacity == 0), "NULL device pointer");
-    if (int rc = ctx->activate()) return rc;
-    return mhx::launch_jaccard_threshold(ctx, d_a, n_a, d_b, n_b, sig_dtype, k, b, min_count, d_pairs, d_counts, capacity,
-                                         n_pairs);
-}
-
-// host form of the matrix: B staged once (scratch[1]); A and the counts go through scratch[0] / scratch[2] in row blocks
-static int all_pairs_matrix_host(mhx_ctx *ctx, const uint64_t *a, int64_t n_a, const uint64_t *b, int64_t n_b, int32_t k, int32_t bb,
-                                 int32_t *counts) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    if (int rc = check_all_pairs(n_a, n_b, MHX_U64, k, bb)) return rc;
+// The matrix of counts.  Host form: B staged once (Aux); A and the counts go through In / Out in row blocks
+static int all_pairs_matrix(mhx_ctx *ctx, const void *a, int64_t n_a, const void *b, int64_t n_b, int sig_dtype, int32_t k, int32_t bb,
+                            int32_t *counts, int64_t ldc, Where where) {
+    MHX_ENTER(ctx, ctx);
+    MHX_TRY(check_all_pairs(n_a, n_b, sig_dtype, k, bb));
     if (!b) {
         b = a;
         n_b = n_a;
     }
+    if (where == kHost) ldc = n_b;  // the host matrix is dense
+    MHX_REQUIRE(ldc >= n_b, "ldc must be >= n_b");
     if (n_a == 0 || n_b == 0) return MHX_OK;
-    MHX_REQUIRE(a && counts, "NULL host pointer");
-    int32_t words = k;  // uint64 per row
-    if (bb >= 0 && mhx_bbit_num_blocks(k, bb, &words)) return MHX_ERR_INVALID;
-    if (int rc = ctx->activate()) return rc;
-    const size_t row_bytes = sizeof(uint64_t) * (size_t)words;
+    MHX_REQUIRE_POINTERS(a && counts, where);
+    MHX_TRY(ctx->activate());
+    if (where == kDevice) return mhx::launch_jaccard_matrix(ctx, a, n_a, b, n_b, sig_dtype, k, bb, counts, ldc);
+    const size_t row_bytes = sizeof(uint64_t) * (size_t)(bb < 0 ? k : num_blocks(k, bb));
     const size_t out_row = sizeof(int32_t) * (size_t)n_b;
     const int64_t block = std::max<int64_t>(1, std::min<int64_t>(n_a, (int64_t)((256ull << 20) / out_row)));
-    if (int rc = ctx->ensure_scratch(1, row_bytes * (size_t)n_b)) return rc;
-    if (int rc = ctx->ensure_scratch(0, row_bytes * (size_t)block)) return rc;
-    if (int rc = ctx->ensure_scratch(2, out_row * (size_t)block)) return rc;
-    MHX_HIP_CHECK(hipMemcpyAsync(ctx->scratch[1], b, row_bytes * (size_t)n_b, hipMemcpyHostToDevice, ctx->stream));
+    Stage s(ctx);
+    const auto p_b = s.piece(Stage::Aux, row_bytes * (size_t)n_b);
+    const auto p_a = s.piece(Stage::In, row_bytes * (size_t)block);
+    const auto p_counts = s.piece(Stage::Out, out_row * (size_t)block);
+    MHX_TRY(s.commit());
+    MHX_TRY(s.upload(p_b, b));
     for (int64_t i0 = 0; i0 < n_a; i0 += block) {
         const int64_t m = std::min<int64_t>(block, n_a - i0);
-        MHX_HIP_CHECK(hipMemcpyAsync(ctx->scratch[0], a + i0 * words, row_bytes * (size_t)m, hipMemcpyHostToDevice, ctx->stream));
-        if (int rc = mhx::launch_jaccard_matrix(ctx, ctx->scratch[0], m, ctx->scratch[1], n_b, MHX_U64, k, bb,
-                                                (int32_t *)ctx->scratch[2], n_b))
-            return rc;
-        MHX_HIP_CHECK(hipMemcpyAsync(counts + i0 * n_b, ctx->scratch[2], out_row * (size_t)m, hipMemcpyDeviceToHost, ctx->stream));
-        MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        MHX_TRY(s.upload(p_a, (const char *)a + (size_t)i0 * row_bytes, row_bytes * (size_t)m));
+        MHX_TRY(mhx::launch_jaccard_matrix(ctx, s.at<void>(p_a), m, s.at<void>(p_b), n_b, sig_dtype, k, bb, s.at<int32_t>(p_counts), n_b));
+        MHX_TRY(s.download(counts + i0 * n_b, p_counts, out_row * (size_t)m));
+        MHX_TRY(s.synchronize());
     }
     return MHX_OK;
 }
 
-// host form of the threshold query: A in scratch[0], B in scratch[1], pairs | counts in scratch[2]
-static int all_pairs_threshold_host(mhx_ctx *ctx, const uint64_t *a, int64_t n_a, const uint64_t *b, int64_t n_b, int32_t k,
-                                    int32_t bb, int32_t min_count, int64_t *pairs, int32_t *counts, int64_t capacity,
-                                    int64_t *n_pairs) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
+// Pairs with at least min_count agreeing positions.  Host form: A in In, B in Aux, pairs | counts in Out
+static int all_pairs_threshold(mhx_ctx *ctx, const void *a, int64_t n_a, const void *b, int64_t n_b, int sig_dtype, int32_t k, int32_t bb,
+                               int32_t min_count, int64_t *pairs, int32_t *counts, int64_t capacity, int64_t *n_pairs, Where where) {
+    MHX_ENTER(ctx, ctx);
     MHX_REQUIRE(n_pairs, "n_pairs is NULL");
     *n_pairs = 0;
-    if (int rc = check_all_pairs(n_a, n_b, MHX_U64, k, bb)) return rc;
+    MHX_TRY(check_all_pairs(n_a, n_b, sig_dtype, k, bb));
     MHX_REQUIRE(capacity >= 0, "bad capacity");
     if (!b) n_b = n_a;
     if (n_a == 0 || n_b == 0 || min_count > k) return MHX_OK;
-    MHX_REQUIRE(a && ((pairs && counts) || capacity == 0), "NULL host pointer");
-    int32_t words = k;
-    if (bb >= 0 && mhx_bbit_num_blocks(k, bb, &words)) return MHX_ERR_INVALID;
-    if (int rc = ctx->activate()) return rc;
-    const size_t row_bytes = sizeof(uint64_t) * (size_t)words;
-    const size_t pair_bytes = ((sizeof(int64_t) * 2 * (size_t)capacity) + 255) & ~(size_t)255;
-    if (int rc = ctx->ensure_scratch(0, row_bytes * (size_t)n_a)) return rc;
-    if (b) {
-        if (int rc = ctx->ensure_scratch(1, row_bytes * (size_t)n_b)) return rc;
-    }
-    if (int rc = ctx->ensure_scratch(2, pair_bytes + sizeof(int32_t) * (size_t)capacity + 256)) return rc;
-    MHX_HIP_CHECK(hipMemcpyAsync(ctx->scratch[0], a, row_bytes * (size_t)n_a, hipMemcpyHostToDevice, ctx->stream));
-    if (b) MHX_HIP_CHECK(hipMemcpyAsync(ctx->scratch[1], b, row_bytes * (size_t)n_b, hipMemcpyHostToDevice, ctx->stream));
-    int64_t *d_pairs = capacity ? (int64_t *)ctx->scratch[2] : nullptr;
-    int32_t *d_counts = capacity ? (int32_t *)((char *)ctx->scratch[2] + pair_bytes) : nullptr;
-    if (int rc = mhx::launch_jaccard_threshold(ctx, ctx->scratch[0], n_a, b ? ctx->scratch[1] : nullptr, n_b, MHX_U64, k, bb,
-                                               min_count, d_pairs, d_counts, capacity, n_pairs))
-        return rc;
+    MHX_REQUIRE_POINTERS(a && ((pairs && counts) || capacity == 0), where);
+    MHX_TRY(ctx->activate());
+    if (where == kDevice)
+        return mhx::launch_jaccard_threshold(ctx, a, n_a, b, n_b, sig_dtype, k, bb, min_count, pairs, counts, capacity, n_pairs);
+    const size_t row_bytes = sizeof(uint64_t) * (size_t)(bb < 0 ? k : num_blocks(k, bb));
+    Stage s(ctx);
+    const auto p_a = s.piece(Stage::In, row_bytes * (size_t)n_a);
+    const auto p_b = b ? s.piece(Stage::Aux, row_bytes * (size_t)n_b) : Stage::Piece{};
+    const auto p_pairs = s.piece(Stage::Out, sizeof(int64_t) * 2 * (size_t)capacity);
+    const auto p_counts = s.piece(Stage::Out, sizeof(int32_t) * (size_t)capacity);
+    s.ask(Stage::Out, p_counts.at + p_counts.bytes + 256);
+    MHX_TRY(s.commit());
+    MHX_TRY(s.upload(p_a, a));
+    if (b) MHX_TRY(s.upload(p_b, b));
+    MHX_TRY(mhx::launch_jaccard_threshold(ctx, s.at<void>(p_a), n_a, b ? s.at<void>(p_b) : nullptr, n_b, sig_dtype, k, bb, min_count,
+                                          capacity ? s.at<int64_t>(p_pairs) : nullptr, capacity ? s.at<int32_t>(p_counts) : nullptr,
+                                          capacity, n_pairs));
     if (*n_pairs > 0 && *n_pairs <= capacity) {
-        MHX_HIP_CHECK(hipMemcpyAsync(pairs, d_pairs, sizeof(int64_t) * 2 * (size_t)*n_pairs, hipMemcpyDeviceToHost, ctx->stream));
-        MHX_HIP_CHECK(hipMemcpyAsync(counts, d_counts, sizeof(int32_t) * (size_t)*n_pairs, hipMemcpyDeviceToHost, ctx->stream));
+        MHX_TRY(s.download(pairs, p_pairs, sizeof(int64_t) * 2 * (size_t)*n_pairs));
+        MHX_TRY(s.download(counts, p_counts, sizeof(int32_t) * (size_t)*n_pairs));
     }
-    MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    return MHX_OK;
+    return s.synchronize();
 }
 
 int mhx_jaccard_matrix_dev(mhx_ctx *ctx, const void *d_a, int64_t n_a, const void *d_b, int64_t n_b, int sig_dtype, int32_t num_perm,
                            int32_t *d_counts, int64_t ldc) {
-    return all_pairs_matrix_dev(ctx, d_a, n_a, d_b, n_b, sig_dtype, num_perm, -1, d_counts, ldc);
+    return all_pairs_matrix(ctx, d_a, n_a, d_b, n_b, sig_dtype, num_perm, -1, d_counts, ldc, kDevice);
 }
 
-int mhx_jaccard_matrix(mhx_ctx *ctx, const uint64_t *a, int64_t n_a, const uint64_t *b, int64_t n_b, int32_t num_perm,
-                       int32_t *counts) {
-    return all_pairs_matrix_host(ctx, a, n_a, b, n_b, num_perm, -1, counts);
+int mhx_jaccard_matrix(mhx_ctx *ctx, const uint64_t *a, int64_t n_a, const uint64_t *b, int64_t n_b, int32_t num_perm, int32_t *counts) {
+    return all_pairs_matrix(ctx, a, n_a, b, n_b, MHX_U64, num_perm, -1, counts, 0, kHost);
 }
 
-int mhx_jaccard_threshold_pairs_dev(mhx_ctx *ctx, const void *d_a, int64_t n_a, const void *d_b, int64_t n_b, int sig_dtype,
-                                    int32_t num_perm, int32_t min_count, int64_t *d_pairs, int32_t *d_counts, int64_t capacity,
-                                    int64_t *n_pairs) {
-    return all_pairs_threshold_dev(ctx, d_a, n_a, d_b, n_b, sig_dtype, num_perm, -1, min_count, d_pairs, d_counts, capacity, n_pairs);
+int mhx_jaccard_threshold_pairs_dev(mhx_ctx *ctx, const void *d_a, int64_t n_a, const void *d_b, int64_t n_b, int sig_dtype, int32_t num_perm,
+                                    int32_t min_count, int64_t *d_pairs, int32_t *d_counts, int64_t capacity, int64_t *n_pairs) {
+    return all_pairs_threshold(ctx, d_a, n_a, d_b, n_b, sig_dtype, num_perm, -1, min_count, d_pairs, d_counts, capacity, n_pairs, kDevice);
 }
 
 int mhx_jaccard_threshold_pairs(mhx_ctx *ctx, const uint64_t *a, int64_t n_a, const uint64_t *b, int64_t n_b, int32_t num_perm,
                                 int32_t min_count, int64_t *pairs, int32_t *counts, int64_t capacity, int64_t *n_pairs) {
-    return all_pairs_threshold_host(ctx, a, n_a, b, n_b, num_perm, -1, min_count, pairs, counts, capacity, n_pairs);
+    return all_pairs_threshold(ctx, a, n_a, b, n_b, MHX_U64, num_perm, -1, min_count, pairs, counts, capacity, n_pairs, kHost);
 }
 
+// (the b-bit entries check b themselves: a negative b means dense rows to the cores)
 int mhx_bbit_jaccard_matrix_dev(mhx_ctx *ctx, const uint64_t *d_a, int64_t n_a, const uint64_t *d_b, int64_t n_b, int32_t num_perm,
                                 int32_t b, int32_t *d_counts, int64_t ldc) {
-    MHX_REQUIRE(b >= 0 && b <= 32, "b must be an integer in [0, 32]");
-    return all_pairs_matrix_dev(ctx, d_a, n_a, d_b, n_b, MHX_U64, num_perm, b, d_counts, ldc);
+    MHX_CHECK_B(b);
+    return all_pairs_matrix(ctx, d_a, n_a, d_b, n_b, MHX_U64, num_perm, b, d_counts, ldc, kDevice);
 }
 
 int mhx_bbit_jaccard_matrix(mhx_ctx *ctx, const uint64_t *a, int64_t n_a, const uint64_t *b_blocks, int64_t n_b, int32_t num_perm,
                             int32_t b, int32_t *counts) {
-    MHX_REQUIRE(b >= 0 && b <= 32, "b must be an integer in [0, 32]");
-    return all_pairs_matrix_host(ctx, a, n_a, b_blocks, n_b, num_perm, b, counts);
+    MHX_CHECK_B(b);
+    return all_pairs_matrix(ctx, a, n_a, b_blocks, n_b, MHX_U64, num_perm, b, counts, 0, kHost);
 }
 
-int mhx_bbit_jaccard_threshold_pairs_dev(mhx_ctx *ctx, const uint64_t *d_a, int64_t n_a, const uint64_t *d_b, int64_t n_b,
-                                         int32_t num_perm, int32_t b, int32_t min_count, int64_t *d_pairs, int32_t *d_counts,
-                                         int64_t capacity, int64_t *n_pairs) {
+int mhx_bbit_jaccard_threshold_pairs_dev(mhx_ctx *ctx, const uint64_t *d_a, int64_t n_a, const uint64_t *d_b, int64_t n_b, int32_t num_perm,
+                                         int32_t b, int32_t min_count, int64_t *d_pairs, int32_t *d_counts, int64_t capacity, int64_t *n_pairs) {
     if (n_pairs) *n_pairs = 0;
-    MHX_REQUIRE(b >= 0 && b <= 32, "b must be an integer in [0, 32]");
-    return all_pairs_threshold_dev(ctx, d_a, n_a, d_b, n_b, MHX_U64, num_perm, b, min_count, d_pairs, d_counts, capacity, n_pairs);
+    MHX_CHECK_B(b);
+    return all_pairs_threshold(ctx, d_a, n_a, d_b, n_b, MHX_U64, num_perm, b, min_count, d_pairs, d_counts, capacity, n_pairs, kDevice);
 }
 
-int mhx_bbit_jaccard_threshold_pairs(mhx_ctx *ctx, const uint64_t *a, int64_t n_a, const uint64_t *b_blocks, int64_t n_b,
-                                     int32_t num_perm, int32_t b, int32_t min_count, int64_t *pairs, int32_t *counts,
-                                     int64_t capacity, int64_t *n_pairs) {
+int mhx_bbit_jaccard_threshold_pairs(mhx_ctx *ctx, const uint64_t *a, int64_t n_a, const uint64_t *b_blocks, int64_t n_b, int32_t num_perm, int32_t b,
+                                     int32_t min_count, int64_t *pairs, int32_t *counts, int64_t capacity, int64_t *n_pairs) {
     if (n_pairs) *n_pairs = 0;
-    MHX_REQUIRE(b >= 0 && b <= 32, "b must be an integer in [0, 32]");
-    return all_pairs_threshold_host(ctx, a, n_a, b_blocks, n_b, num_perm, b, min_count, pairs, counts, capacity, n_pairs);
+    MHX_CHECK_B(b);
+    return all_pairs_threshold(ctx, a, n_a, b_blocks, n_b, MHX_U64, num_perm, b, min_count, pairs, counts, capacity, n_pairs, kHost);
 }
 
 int mhx_lsh_bands_merge_dev(mhx_ctx *ctx, const uint64_t *d_dig_a, const uint32_t *d_rows_a, int64_t n_a, const uint64_t *d_dig_b,
                             const uint32_t *d_rows_b, int64_t n_b, uint32_t row_offset_b, int32_t bands, uint64_t *d_dig_out,
                             uint32_t *d_rows_out) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
+    MHX_ENTER(ctx, ctx);
     MHX_REQUIRE(bands > 0, "bands must be positive");
     MHX_REQUIRE(n_a >= 0 && n_b >= 0, "bad shape");
     MHX_REQUIRE(n_a + n_b < ((int64_t)1 << 32), "more than 2^32-1 entries per band");
     if (n_a + n_b == 0) return MHX_OK;
     MHX_REQUIRE((n_a == 0 || (d_dig_a && d_rows_a)) && (n_b == 0 || (d_dig_b && d_rows_b)) && d_dig_out && d_rows_out,
                 "NULL device pointer");
-    if (int rc = ctx->activate()) return rc;
+    MHX_TRY(ctx->activate());
     return mhx::launch_lsh_bands_merge(ctx, d_dig_a, d_rows_a, n_a, d_dig_b, d_rows_b, n_b, row_offset_b, bands, d_dig_out, d_rows_out);
 }
 
 int mhx_lsh_bands_compact_dev(mhx_ctx *ctx, const uint64_t *d_dig, const uint32_t *d_rows, int64_t n, int32_t bands,
                               const uint32_t *d_live_bits, int64_t n_live, uint64_t *d_dig_out, uint32_t *d_rows_out) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
+    MHX_ENTER(ctx, ctx);
     MHX_REQUIRE(bands > 0, "bands must be positive");
     MHX_REQUIRE(n >= 0 && n_live >= 0 && n_live <= n, "bad shape");
-    MHX_REQUIRE(n < ((int64_t)1 << 32), "more than 2^32-1 rows per call");
+    MHX_CHECK_ROWS32(n);
     if (n == 0) return MHX_OK;
     MHX_REQUIRE(d_dig && d_rows && d_live_bits && ((d_dig_out && d_rows_out) || n_live == 0), "NULL device pointer");
-    if (int rc = ctx->activate()) return rc;
+    MHX_TRY(ctx->activate());
     return mhx::launch_lsh_bands_compact(ctx, d_dig, d_rows, n, bands, d_live_bits, n_live, d_dig_out, d_rows_out);
 }
 
 int mhx_rows_compact_dev(mhx_ctx *ctx, const void *d_src, int64_t row_bytes, int64_t n_rows, const uint32_t *d_live_bits, void *d_dst,
                          int64_t *n_kept) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
+    MHX_ENTER(ctx, ctx);
     MHX_REQUIRE(n_kept, "n_kept is NULL");
     *n_kept = 0;
     MHX_REQUIRE(row_bytes > 0 && n_rows >= 0, "bad shape");
-    MHX_REQUIRE(n_rows < ((int64_t)1 << 32), "more than 2^32-1 rows per call");
+    MHX_CHECK_ROWS32(n_rows);
     MHX_REQUIRE(n_rows == 0 || row_bytes <= INT64_MAX / n_rows, "row_bytes * n_rows overflows");
     if (n_rows == 0) return MHX_OK;
     MHX_REQUIRE(d_src && d_live_bits && d_dst, "NULL device pointer");
-    if (int rc = ctx->activate()) return rc;
+    MHX_TRY(ctx->activate());
     return mhx::launch_rows_compact(ctx, d_src, row_bytes, n_rows, d_live_bits, d_dst, n_kept);
 }
 
 int mhx_lsh_forest_build_dev_typed(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n, int32_t row_words, int32_t l,
                                    int32_t tree_words, uint32_t *d_order) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    MHX_REQUIRE(sig_dtype == MHX_U32 || sig_dtype == MHX_U64, "sig_dtype must be MHX_U32 or MHX_U64");
+    MHX_ENTER(ctx, ctx);
+    MHX_CHECK_DTYPE(sig_dtype);
     MHX_REQUIRE(l > 0 && l < 65536, "l must be in [1, 65535]");
     MHX_REQUIRE(tree_words > 0 && row_words > 0 && (int64_t)l * tree_words <= row_words, "l * tree_words must be in [1, row_words]");
     MHX_REQUIRE(n >= 0 && n < ((int64_t)1 << 32), "n_sigs must be in [0, 2^32)");
     if (n == 0) return MHX_OK;
     MHX_REQUIRE(d_sig && d_order, "NULL device pointer");
-    if (int rc = ctx->activate()) return rc;
+    MHX_TRY(ctx->activate());
     return mhx::launch_lsh_forest_build(ctx, d_sig, sig_dtype, n, row_words, l, tree_words, d_order);
 }
 
 int mhx_lsh_forest_query_dev_typed(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n, int32_t row_words, int32_t l,
                                    int32_t tree_words, int32_t w, const uint32_t *d_order, const void *d_probes, int64_t m, int32_t k,
                                    uint32_t *d_slots, int32_t *d_counts) {
-    if (!ctx) return fail(MHX_ERR_INVALID, "ctx is NULL");
-    MHX_GUARD(ctx);
-    MHX_REQUIRE(sig_dtype == MHX_U32 || sig_dtype == MHX_U64, "sig_dtype must be MHX_U32 or MHX_U64");
+    MHX_ENTER(ctx, ctx);
+    MHX_CHECK_DTYPE(sig_dtype);
     MHX_REQUIRE(l > 0 && l < 65536, "l must be in [1, 65535]");
     MHX_REQUIRE(tree_words > 0 && row_words > 0 && (int64_t)l * tree_words <= row_words, "l * tree_words must be in [1, row_words]");
     MHX_REQUIRE((w == 1 || w == 2) && tree_words % w == 0 && tree_words / w < 65536, "w must be 1 or 2 and divide tree_words");
@@ -2079,7 +1953,7 @@ int mhx_lsh_forest_query_dev_typed(mhx_ctx *ctx, const void *d_sig, int sig_dtyp
     MHX_REQUIRE(m >= 0 && m < ((int64_t)1 << 31), "m must be in [0, 2^31)");
     if (m == 0) return MHX_OK;
     MHX_REQUIRE(d_counts, "NULL device pointer");
-    if (int rc = ctx->activate()) return rc;
+    MHX_TRY(ctx->activate());
     if (n == 0) {
         MHX_HIP_CHECK(hipMemsetAsync(d_counts, 0, sizeof(int32_t) * (size_t)m, ctx->stream));
         return MHX_OK;
