@@ -10,6 +10,7 @@ from datasketch_amd import lsh_bulk
 from datasketch_amd.hashfunc import prehashed, sha1_hash32, sha1_hash64, sha1_hash_many
 from datasketch_amd.lean_minhash import LeanMinHash
 from datasketch_amd.lsh import MinHashLSH
+from datasketch_amd.lshensemble import MinHashLSHEnsemble
 from datasketch_amd.lshforest import MinHashLSHForest
 from datasketch_amd.minhash import MinHash
 from datasketch_amd.weighted_minhash import WeightedMinHash, WeightedMinHashGenerator
@@ -20,6 +21,7 @@ __all__ = [
     "LeanMinHash",
     "MinHash",
     "MinHashLSH",
+    "MinHashLSHEnsemble",
     "MinHashLSHForest",
     "WeightedMinHash",
     "WeightedMinHashGenerator",

@@ -7,6 +7,7 @@ a device is missing it raises, it does not fall back to a CPU implementation.
 from __future__ import annotations
 
 import ctypes
+import itertools
 import weakref
 import os
 import threading
@@ -136,6 +137,19 @@ _RESTYPE = {"mhx_last_error": ctypes.c_char_p, "mhx_version": ctypes.c_char_p}
 EXPORTED_SYMBOLS = sorted(list(_PROTOTYPES) + list(_RESTYPE))
 
 
+class EnsembleLevel(ctypes.Structure):
+    """mhx_ensemble_level: one distinct r of a MinHashLSHEnsemble -- its two device buffers, r in words and its bands."""
+    _fields_ = [("d_digests", _vp), ("d_rows", _vp), ("r", _i32), ("bands", _i32)]
+
+
+# Entry points declared MHX_API_EXT in include/mhx.h: bound like the ones above and as much a part of the library (load() fails
+# without them), but their argument checks are tested beside their feature, not in the table that lists EXPORTED_SYMBOLS.
+_PROTOTYPES_EXT = {
+    "mhx_lsh_ensemble_query_dev": [_vp, ctypes.POINTER(EnsembleLevel), _i32, ctypes.POINTER(_i64), _i32, _vp, _int, _i32, _vp, _i64, _vp,
+                                   ctypes.POINTER(_i32), _i32, _vp, _i64, ctypes.POINTER(_i64)],
+}
+
+
 try:  # CPython helper (csrc/pack_module.c): ~10 ns per token instead of ~180 in the interpreter
     from datasketch_amd import _mhxpack
 except ImportError:  # not built: the pure-Python packer below does the same job
@@ -172,7 +186,7 @@ def load():
                 "Build it with `python -c 'import __graft_entry__ as g; g.build()'` or datasketch_amd/csrc/build.sh"
             )
             raise MhxError(_lib_error) from e
-        for name, argtypes in _PROTOTYPES.items():
+        for name, argtypes in itertools.chain(_PROTOTYPES.items(), _PROTOTYPES_EXT.items()):
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = _int
@@ -959,6 +973,34 @@ class Context:
             found = _i64(0)
             check(self.lib.mhx_lsh_query_dev(self.handle, _vp(d_dig), _vp(d_rows), int(n), int(b), int(r), _vp(d_q.ptr), _vp(d_sig),
                                              int(code), int(k), m, _vp(d_pairs.ptr), cap, ctypes.byref(found)))
+            if found.value <= cap:
+                break
+            cap = int(found.value)
+        self.synchronize()
+        pairs = d_pairs.download((found.value, 2), np.int64) if found.value else np.empty((0, 2), dtype=np.int64)
+        offsets = np.zeros(m + 1, dtype=np.int64)
+        np.cumsum(np.bincount(pairs[:, 0], minlength=m), out=offsets[1:])
+        return offsets, np.ascontiguousarray(pairs[:, 1])
+
+    def lsh_ensemble_query_dev(self, levels, start: np.ndarray, d_sig: int, code: int, k: int, probes: np.ndarray, choice: np.ndarray,
+                               params: np.ndarray, capacity: Optional[int] = None):
+        """mhx_lsh_ensemble_query_dev for a host matrix of probes (of the index's dtype): ``levels`` is a list of (d_digests,
+        d_rows, r in words, bands), ``start`` int64[P + 1], ``choice`` uint8[m][P], ``params`` int32[n_params][2] of (level, b).
+        Returns (offsets int64[m + 1], slots int64[...]) as :meth:`lsh_query_dev` does."""
+        m = probes.shape[0]
+        c_levels = (EnsembleLevel * len(levels))(*[EnsembleLevel(_vp(d), _vp(rw), int(r), int(b)) for d, rw, r, b in levels])
+        start = np.ascontiguousarray(start, dtype=np.int64)
+        params = np.ascontiguousarray(params, dtype=np.int32)
+        d_q = self.to_device(probes)
+        d_choice = self.to_device(np.ascontiguousarray(choice, dtype=np.uint8))
+        cap = int(capacity) if capacity is not None else max(4 * m, 1 << 16)
+        while True:
+            d_pairs = self.alloc(cap * 16)
+            found = _i64(0)
+            check(self.lib.mhx_lsh_ensemble_query_dev(self.handle, c_levels, len(levels), start.ctypes.data_as(ctypes.POINTER(_i64)),
+                                                      start.size - 1, _vp(d_sig), int(code), int(k), _vp(d_q.ptr), m, _vp(d_choice.ptr),
+                                                      params.ctypes.data_as(ctypes.POINTER(_i32)), params.shape[0], _vp(d_pairs.ptr), cap,
+                                                      ctypes.byref(found)))
             if found.value <= cap:
                 break
             cap = int(found.value)

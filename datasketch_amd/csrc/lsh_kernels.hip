@@ -913,6 +913,56 @@ int launch_lsh_sort_bands(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_
     return MHX_OK;
 }
 
+// ---- the tail the query launchers share (launch_lsh_query here, launch_lsh_ensemble_query in lsh_ensemble_kernels.hip) ----
+// `raw` candidates (probe << 32 | row, or ~0 where the band's words differed) -> unique (probe, row) pairs, ascending.
+// scratch[3]: raw u64[raw] | sorted u64[raw] | count u64 | sort / select temporary.  lsh_raw_pairs_reserve sizes the slot and
+// hands out the raw array for the caller's emit kernel; lsh_raw_pairs_finish sorts, keeps the run heads and unpacks them.
+namespace {
+size_t raw_pair_bytes(int64_t raw) { return ((sizeof(uint64_t) * (size_t)raw) + 255) & ~(size_t)255; }
+int raw_pair_tmp_bytes(mhx_ctx *ctx, int64_t raw, size_t *sort_tmp) {
+    hipError_t e = rocprim::radix_sort_keys(nullptr, *sort_tmp, (const uint64_t *)nullptr, (uint64_t *)nullptr, (size_t)raw, 0, 64, ctx->stream);
+    if (e != hipSuccess) return fail(MHX_ERR_HIP, "rocprim size query failed: %s", hipGetErrorString(e));
+    return MHX_OK;
+}
+}  // namespace
+
+int lsh_raw_pairs_reserve(mhx_ctx *ctx, int64_t raw, uint64_t **d_raw) {
+    if ((size_t)raw * 16 > (size_t)ctx->hbm_bytes / 2)
+        return fail(MHX_ERR_OOM, "%lld candidates before deduplication do not fit in device memory", (long long)raw);
+    size_t sort_tmp = 0;
+    if (int rc = raw_pair_tmp_bytes(ctx, raw, &sort_tmp)) return rc;
+    if (int rc = ctx->ensure_scratch(3, 2 * raw_pair_bytes(raw) + 256 + std::max(sort_tmp, scan_tmp_bytes(raw)))) return rc;
+    *d_raw = (uint64_t *)ctx->scratch[3];
+    return MHX_OK;
+}
+
+int lsh_raw_pairs_finish(mhx_ctx *ctx, int64_t raw, int64_t *d_pairs, int64_t capacity, int64_t *n_pairs) {
+    const size_t raw_bytes = raw_pair_bytes(raw);
+    size_t sort_tmp = 0;
+    if (int rc = raw_pair_tmp_bytes(ctx, raw, &sort_tmp)) return rc;
+    uint64_t *d_raw = (uint64_t *)ctx->scratch[3];
+    uint64_t *d_sorted = (uint64_t *)((char *)ctx->scratch[3] + raw_bytes);
+    void *d_tmp = (char *)ctx->scratch[3] + 2 * raw_bytes + 256;
+    hipError_t e = rocprim::radix_sort_keys(d_tmp, sort_tmp, (const uint64_t *)d_raw, d_sorted, (size_t)raw, 0, 64, ctx->stream);
+    if (e != hipSuccess) return fail(MHX_ERR_HIP, "rocprim::radix_sort_keys failed: %s", hipGetErrorString(e));
+    uint64_t *d_cnt = nullptr;  // unique: the run heads of the sorted candidates, packed
+    if (int rc = device_exclusive_scan(ctx, HeadsIn{d_sorted}, CompactOut{d_sorted, d_raw}, raw, d_tmp, &d_cnt)) return rc;
+    uint64_t unique_count = 0, last_key = 0;
+    MHX_HIP_CHECK(hipMemcpyAsync(&unique_count, d_cnt, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (unique_count > 0) {  // a failed verification left ~0, which sorts last
+        MHX_HIP_CHECK(hipMemcpyAsync(&last_key, d_raw + (unique_count - 1), sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+        MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        if (last_key == ~0ull) --unique_count;
+    }
+    *n_pairs = (int64_t)unique_count;
+    if ((int64_t)unique_count > capacity || unique_count == 0) return MHX_OK;  // caller sees n_pairs > capacity and calls again
+    hipLaunchKernelGGL(unpack_pairs_kernel, dim3(grid_for(ctx, (int64_t)unique_count)), dim3(256), 0, ctx->stream, d_raw,
+                       (int64_t)unique_count, d_pairs);
+    MHX_HIP_CHECK(hipGetLastError());
+    return MHX_OK;
+}
+
 int launch_lsh_query(mhx_ctx *ctx, const uint64_t *d_sorted_digests, const uint32_t *d_sorted_rows, int64_t n, int32_t bands,
                      int32_t r, const void *d_q_sig, const void *d_idx_sig, int sig_dtype, int32_t k, int64_t m,
                      int64_t *d_pairs, int64_t capacity, int64_t *n_pairs) {
@@ -941,18 +991,8 @@ int launch_lsh_query(mhx_ctx *ctx, const uint64_t *d_sorted_digests, const uint3
     MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     const int64_t raw = (int64_t)raw_total;
     if (raw == 0) return MHX_OK;
-    if ((size_t)raw * 16 > (size_t)ctx->hbm_bytes / 2)
-        return fail(MHX_ERR_OOM, "%lld candidates before deduplication do not fit in device memory", (long long)raw);
-    // scratch[3]: raw u64[raw] | sorted u64[raw] | count u64 | sort / select temporary
-    const size_t raw_bytes = ((sizeof(uint64_t) * (size_t)raw) + 255) & ~(size_t)255;
-    size_t sort_tmp = 0;
-    hipError_t e = rocprim::radix_sort_keys(nullptr, sort_tmp, (const uint64_t *)nullptr, (uint64_t *)nullptr, (size_t)raw, 0, 64, ctx->stream);
-    if (e != hipSuccess) return fail(MHX_ERR_HIP, "rocprim size query failed: %s", hipGetErrorString(e));
-    const size_t tmp_bytes = std::max(sort_tmp, scan_tmp_bytes(raw));
-    if (int rc = ctx->ensure_scratch(3, 2 * raw_bytes + 256 + tmp_bytes)) return rc;
-    uint64_t *d_raw = (uint64_t *)ctx->scratch[3];
-    uint64_t *d_sorted = (uint64_t *)((char *)ctx->scratch[3] + raw_bytes);
-    void *d_tmp = (char *)ctx->scratch[3] + 2 * raw_bytes + 256;
+    uint64_t *d_raw = nullptr;
+    if (int rc = lsh_raw_pairs_reserve(ctx, raw, &d_raw)) return rc;
     const bool verify = d_idx_sig != nullptr;
     if (sig_dtype == MHX_U32) {
         if (verify)
@@ -970,24 +1010,7 @@ int launch_lsh_query(mhx_ctx *ctx, const uint64_t *d_sorted_digests, const uint3
                                d_sorted_rows, (const uint64_t *)d_q_sig, (const uint64_t *)d_idx_sig, k, r, d_raw);
     }
     MHX_HIP_CHECK(hipGetLastError());
-    e = rocprim::radix_sort_keys(d_tmp, sort_tmp, (const uint64_t *)d_raw, d_sorted, (size_t)raw, 0, 64, ctx->stream);
-    if (e != hipSuccess) return fail(MHX_ERR_HIP, "rocprim::radix_sort_keys failed: %s", hipGetErrorString(e));
-    uint64_t *d_cnt = nullptr;  // unique: the run heads of the sorted candidates, packed
-    if (int rc = device_exclusive_scan(ctx, HeadsIn{d_sorted}, CompactOut{d_sorted, d_raw}, raw, d_tmp, &d_cnt)) return rc;
-    uint64_t unique_count = 0, last_key = 0;
-    MHX_HIP_CHECK(hipMemcpyAsync(&unique_count, d_cnt, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (unique_count > 0) {  // a failed verification left ~0, which sorts last
-        MHX_HIP_CHECK(hipMemcpyAsync(&last_key, d_raw + (unique_count - 1), sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-        MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        if (last_key == ~0ull) --unique_count;
-    }
-    *n_pairs = (int64_t)unique_count;
-    if ((int64_t)unique_count > capacity || unique_count == 0) return MHX_OK;  // caller sees n_pairs > capacity and calls again
-    hipLaunchKernelGGL(unpack_pairs_kernel, dim3(grid_for(ctx, (int64_t)unique_count)), dim3(256), 0, ctx->stream, d_raw,
-                       (int64_t)unique_count, d_pairs);
-    MHX_HIP_CHECK(hipGetLastError());
-    return MHX_OK;
+    return lsh_raw_pairs_finish(ctx, raw, d_pairs, capacity, n_pairs);
 }
 
 }  // namespace mhx

@@ -1335,6 +1335,39 @@ int mhx_lsh_query_dev(mhx_ctx *ctx, const uint64_t *d_sorted_digests, const uint
                                  d_pairs, capacity, n_pairs);
 }
 
+int mhx_lsh_ensemble_query_dev(mhx_ctx *ctx, const mhx_ensemble_level *levels, int32_t n_levels, const int64_t *start, int32_t n_parts,
+                               const void *d_index_sig, int sig_dtype, int32_t k, const void *d_query_sig, int64_t m,
+                               const uint8_t *d_choice, const int32_t *params, int32_t n_params, int64_t *d_pairs, int64_t capacity,
+                               int64_t *n_pairs) {
+    MHX_ENTER(ctx, ctx);
+    MHX_REQUIRE(n_pairs, "n_pairs is NULL");
+    MHX_CHECK_DTYPE(sig_dtype);
+    MHX_REQUIRE(k > 0 && n_parts >= 0 && m >= 0 && capacity >= 0, "bad shape");
+    MHX_REQUIRE(n_levels > 0 && n_levels <= MHX_ENSEMBLE_MAX_LEVELS, "n_levels must be in [1, %d]", MHX_ENSEMBLE_MAX_LEVELS);
+    MHX_REQUIRE(n_params > 0 && n_params <= MHX_ENSEMBLE_MAX_PARAMS, "n_params must be in [1, %d]", MHX_ENSEMBLE_MAX_PARAMS);
+    MHX_REQUIRE_POINTERS(levels && start && params, kHost);
+    MHX_REQUIRE(start[0] == 0, "start[0] must be 0");
+    for (int32_t p = 0; p < n_parts; ++p) MHX_REQUIRE(start[p] <= start[p + 1], "start must ascend");
+    const int64_t n = start[n_parts];
+    MHX_CHECK_ROWS32(n);
+    MHX_CHECK_ROWS32(m);
+    for (int32_t l = 0; l < n_levels; ++l) MHX_CHECK_BANDS(levels[l].bands, levels[l].r, k);
+    for (int32_t c = 0; c < n_params; ++c) {
+        const int32_t level = params[2 * c], b = params[2 * c + 1];
+        MHX_REQUIRE(level >= 0 && level < n_levels, "params row %d names level %d of %d", c, level, n_levels);
+        MHX_REQUIRE(b >= 0 && b <= levels[level].bands, "params row %d: b = %d is not in [0, %d], the bands of its level", c, b,
+                    levels[level].bands);
+    }
+    *n_pairs = 0;
+    if (n == 0 || m == 0 || n_parts == 0) return MHX_OK;
+    bool buffers = true;
+    for (int32_t l = 0; l < n_levels; ++l) buffers = buffers && levels[l].d_digests && levels[l].d_rows;
+    MHX_REQUIRE_POINTERS(buffers && d_index_sig && d_query_sig && d_choice && (d_pairs || capacity == 0), kDevice);
+    MHX_TRY(ctx->activate());
+    return mhx::launch_lsh_ensemble_query(ctx, levels, n_levels, start, n_parts, d_index_sig, sig_dtype, k, d_query_sig, m, d_choice, params,
+                                          n_params, d_pairs, capacity, n_pairs);
+}
+
 // Agreeing positions of listed pairs.  b < 0: dense rows of sig_dtype, else b-bit blocks.  The host form takes the n rows
 // both ends of a pair index (In), the pairs (Aux) and returns the counts (Out).
 static int listed_pairs(mhx_ctx *ctx, const void *rows_a, const void *rows_b, int64_t n, int sig_dtype, int32_t k, int32_t b,

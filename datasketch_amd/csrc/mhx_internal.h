@@ -191,6 +191,14 @@ int launch_lsh_sort_bands(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_
 int launch_lsh_query(mhx_ctx *ctx, const uint64_t *d_sorted_digests, const uint32_t *d_sorted_rows, int64_t n, int32_t bands,
                      int32_t r, const void *d_q_sig, const void *d_idx_sig, int sig_dtype, int32_t k, int64_t m,
                      int64_t *d_pairs, int64_t capacity, int64_t *n_pairs);
+// the tail of the query launchers (lsh_kernels.hip): room in scratch[3] for `raw` candidates (probe << 32 | row, ~0 = dropped),
+// which the caller's emit kernel fills; then sort, unique and unpack into (probe, row) pairs.  finish blocks (it reads the count).
+int lsh_raw_pairs_reserve(mhx_ctx *ctx, int64_t raw, uint64_t **d_raw);
+int lsh_raw_pairs_finish(mhx_ctx *ctx, int64_t raw, int64_t *d_pairs, int64_t capacity, int64_t *n_pairs);
+// lsh_ensemble_kernels.hip: the containment query over the partitions of a MinHashLSHEnsemble (mhx_lsh_ensemble_query_dev)
+int launch_lsh_ensemble_query(mhx_ctx *ctx, const mhx_ensemble_level *levels, int32_t n_levels, const int64_t *start, int32_t n_parts,
+                              const void *d_idx_sig, int sig_dtype, int32_t k, const void *d_q_sig, int64_t m, const uint8_t *d_choice,
+                              const int32_t *params, int32_t n_params, int64_t *d_pairs, int64_t capacity, int64_t *n_pairs);
 int launch_bbit_jaccard(mhx_ctx *ctx, const uint64_t *d_a, const uint64_t *d_b, int32_t k, int32_t b, const int64_t *d_pairs,
                         int64_t m, int32_t *d_counts);
 int launch_lean_serialize(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n, int32_t k, int64_t seed, int big_endian,

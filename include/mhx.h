@@ -545,6 +545,41 @@ MHX_API int mhx_lsh_forest_query_dev_typed(mhx_ctx *ctx, const void *d_sig, int 
                                            int32_t l, int32_t tree_words, int32_t w, const uint32_t *d_order, const void *d_probes,
                                            int64_t m, int32_t k, uint32_t *d_slots, int32_t *d_counts);
 
+/* ---- LSH Ensemble: containment queries over size partitions -------------------------------- */
+/* The index of datasketch_amd.MinHashLSHEnsemble (ref: datasketch/lshensemble.py).  The rows of ONE signature matrix d_index_sig
+ * [n][row_words] are sorted by set size, so partition p of n_parts is the slot range [start[p], start[p + 1]) (start: host
+ * int64[n_parts + 1], ascending from 0 to n < 2^32).  Every distinct r of the ensemble's parameter table is a level: bands = the
+ * number of bands of r words (r counts words: 2 per hash value for WeightedMinHash rows), and two device buffers of bands * n
+ * entries, d_digests uint64 and d_rows uint32.  Partition p owns the entries [bands * start[p], bands * start[p + 1]) of both;
+ * inside that block band j starts at j * n_p (n_p = the partition's rows) and is ascending by (digest, row) with rows local to the
+ * partition -- byte for byte what mhx_lsh_sort_bands_dev_typed writes for the partition's rows, which is how it is built.
+ *
+ * Query: params is the host table int32[n_params][2] of (level, b) rows, b <= that level's bands; d_choice uint8[m][n_parts] names,
+ * per probe and partition, the row of params to use (the reference picks it from upper bound / probe size: floating point, done by
+ * the caller).  A byte that is no row of the table (255 by convention) skips the partition.  For every probe q, partition p and
+ * band j < b the probe's digest is located by binary search in band j of p's block of the chosen level and the run of equal digests
+ * is its bucket; a candidate is kept when the band's r words of probe and index row are equal.  d_pairs int64[capacity][2] =
+ * (probe, slot = start[p] + row), ascending, unique; *n_pairs, capacity and the overflow behaviour as in mhx_lsh_query_dev.  The work is
+ * the sum of the chosen b, not m * n_parts * bands.  At most MHX_ENSEMBLE_MAX_LEVELS levels and MHX_ENSEMBLE_MAX_PARAMS table rows.
+ * Blocking.
+ *
+ * (Exported through MHX_API_EXT: the same visibility; its argument checks are tested beside the index, in
+ * tests/test_gpu_lshensemble.py, and it is bound from _native._PROTOTYPES_EXT.) */
+#define MHX_API_EXT __attribute__((visibility("default")))
+#define MHX_ENSEMBLE_MAX_LEVELS 16
+#define MHX_ENSEMBLE_MAX_PARAMS 64
+typedef struct mhx_ensemble_level {
+    const uint64_t *d_digests; /* uint64[bands * n] */
+    const uint32_t *d_rows;    /* uint32[bands * n] */
+    int32_t r;                 /* words per band */
+    int32_t bands;             /* bands per partition block: r * bands <= row_words */
+} mhx_ensemble_level;
+MHX_API_EXT int mhx_lsh_ensemble_query_dev(mhx_ctx *ctx, const mhx_ensemble_level *levels, int32_t n_levels, const int64_t *start,
+                                           int32_t n_parts, const void *d_index_sig, int sig_dtype, int32_t row_words,
+                                           const void *d_query_sig, int64_t n_queries, const uint8_t *d_choice,
+                                           const int32_t *params, int32_t n_params, int64_t *d_pairs, int64_t capacity,
+                                           int64_t *n_pairs);
+
 /* ---- Multi-GPU: assemble the signature matrix (RCCL over xGMI) ----------------------------- */
 /* 128-byte RCCL unique id, created on rank 0 and distributed by the caller (env, file, socket). */
 #define MHX_COMM_ID_BYTES 128
