@@ -7,7 +7,6 @@ a device is missing it raises, it does not fall back to a CPU implementation.
 from __future__ import annotations
 
 import ctypes
-import itertools
 import weakref
 import os
 import threading
@@ -28,6 +27,11 @@ _i64 = ctypes.c_int64
 _i32 = ctypes.c_int32
 _int = ctypes.c_int
 _sz = ctypes.c_size_t
+
+class EnsembleLevel(ctypes.Structure):
+    """mhx_ensemble_level: one distinct r of a MinHashLSHEnsemble -- its two device buffers, r in words and its bands."""
+    _fields_ = [("d_digests", _vp), ("d_rows", _vp), ("r", _i32), ("bands", _i32)]
+
 
 # name -> argtypes; every function returns int unless listed in _RESTYPE
 _PROTOTYPES = {
@@ -92,6 +96,8 @@ _PROTOTYPES = {
     "mhx_lsh_candidate_pairs": [_vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64,
                                 ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
     "mhx_lsh_query_dev": [_vp, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _int, _i32, _i64, _vp, _i64, ctypes.POINTER(_i64)],
+    "mhx_lsh_ensemble_query_dev": [_vp, ctypes.POINTER(EnsembleLevel), _i32, ctypes.POINTER(_i64), _i32, _vp, _int, _i32, _vp, _i64, _vp,
+                                   ctypes.POINTER(_i32), _i32, _vp, _i64, ctypes.POINTER(_i64)],
     "mhx_jaccard_pairs_dev": [_vp, _vp, _vp, _i32, _vp, _i64, _vp],
     "mhx_jaccard_pairs": [_vp, _vp, _i64, _i32, _vp, _i64, _vp],
     "mhx_bbit_pack_dev_typed": [_vp, _vp, _int, _i64, _i32, _i32, _vp],
@@ -137,19 +143,6 @@ _RESTYPE = {"mhx_last_error": ctypes.c_char_p, "mhx_version": ctypes.c_char_p}
 EXPORTED_SYMBOLS = sorted(list(_PROTOTYPES) + list(_RESTYPE))
 
 
-class EnsembleLevel(ctypes.Structure):
-    """mhx_ensemble_level: one distinct r of a MinHashLSHEnsemble -- its two device buffers, r in words and its bands."""
-    _fields_ = [("d_digests", _vp), ("d_rows", _vp), ("r", _i32), ("bands", _i32)]
-
-
-# Entry points declared MHX_API_EXT in include/mhx.h: bound like the ones above and as much a part of the library (load() fails
-# without them), but their argument checks are tested beside their feature, not in the table that lists EXPORTED_SYMBOLS.
-_PROTOTYPES_EXT = {
-    "mhx_lsh_ensemble_query_dev": [_vp, ctypes.POINTER(EnsembleLevel), _i32, ctypes.POINTER(_i64), _i32, _vp, _int, _i32, _vp, _i64, _vp,
-                                   ctypes.POINTER(_i32), _i32, _vp, _i64, ctypes.POINTER(_i64)],
-}
-
-
 try:  # CPython helper (csrc/pack_module.c): ~10 ns per token instead of ~180 in the interpreter
     from datasketch_amd import _mhxpack
 except ImportError:  # not built: the pure-Python packer below does the same job
@@ -186,7 +179,7 @@ def load():
                 "Build it with `python -c 'import __graft_entry__ as g; g.build()'` or datasketch_amd/csrc/build.sh"
             )
             raise MhxError(_lib_error) from e
-        for name, argtypes in itertools.chain(_PROTOTYPES.items(), _PROTOTYPES_EXT.items()):
+        for name, argtypes in _PROTOTYPES.items():
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = _int
@@ -756,15 +749,16 @@ class Context:
         first guess of M; a larger answer costs one more call."""
         sig = np.ascontiguousarray(sig, dtype=np.uint64)
         n, k = sig.shape
-        cap = int(capacity) if capacity is not None else max(4 * n, 1 << 16)
-        while True:
+        raw = _i64(0)
+
+        def call(cap, found):
             pairs = np.empty((cap, 2), dtype=np.int64)
-            found, raw = _i64(0), _i64(0)
-            check(self.lib.mhx_lsh_candidate_pairs(self.handle, _ptr(sig), n, k, int(bands), int(r), _ptr(pairs), cap,
-                                                   ctypes.byref(found), ctypes.byref(raw)))
-            if found.value <= cap:
-                return pairs[: found.value], int(raw.value)
-            cap = int(found.value)
+            check(self.lib.mhx_lsh_candidate_pairs(self.handle, _ptr(sig), n, k, int(bands), int(r), _ptr(pairs), cap, found,
+                                                   ctypes.byref(raw)))
+            return pairs
+
+        pairs, found = self._capacity_retry(call, capacity if capacity is not None else max(4 * n, 1 << 16))
+        return pairs[:found], int(raw.value)
 
     def jaccard_pairs(self, sig: np.ndarray, pairs: np.ndarray) -> np.ndarray:
         """int32 counts of equal positions for rows (pairs[:,0], pairs[:,1]) of one signature matrix."""
@@ -858,16 +852,36 @@ class Context:
         check(self.lib.mhx_bbit_num_blocks(int(num_perm), int(b), ctypes.byref(nb)))
         return nb.value
 
-    def _threshold_retry(self, call, capacity: int):
+    @staticmethod
+    def _capacity_retry(call, capacity: int):
+        """The entry points that report ``found`` answers and write them only when they fit: ``call(cap, byref(found))`` makes
+        room for ``cap`` answers, runs the entry point and returns its buffers; a larger answer costs one more call with
+        cap = found.  Returns (the buffers of the call that fit, found)."""
         cap = int(capacity)
         while True:
+            found = _i64(0)
+            out = call(cap, ctypes.byref(found))
+            if found.value <= cap:
+                return out, int(found.value)
+            cap = int(found.value)
+
+    def _threshold_retry(self, call, capacity: int):
+        def sized(cap, found):
             pairs = np.empty((cap, 2), dtype=np.int64)
             counts = np.empty(cap, dtype=np.int32)
-            found = _i64(0)
-            check(call(_ptr(pairs), _ptr(counts), cap, ctypes.byref(found)))
-            if found.value <= cap:
-                return pairs[: found.value], counts[: found.value]
-            cap = int(found.value)
+            check(call(_ptr(pairs), _ptr(counts), cap, found))
+            return pairs, counts
+
+        (pairs, counts), found = self._capacity_retry(sized, capacity)
+        return pairs[:found], counts[:found]
+
+    def _pairs_to_offsets(self, d_pairs: "DeviceBuffer", found: int, m: int):
+        """(offsets int64[m + 1], rows int64[found]) of ``found`` ascending (probe, row) pairs on the device."""
+        self.synchronize()
+        pairs = d_pairs.download((found, 2), np.int64) if found else np.empty((0, 2), dtype=np.int64)
+        offsets = np.zeros(m + 1, dtype=np.int64)
+        np.cumsum(np.bincount(pairs[:, 0], minlength=m), out=offsets[1:])
+        return offsets, np.ascontiguousarray(pairs[:, 1])
 
     def jaccard_matrix(self, a: np.ndarray, b: Optional[np.ndarray] = None) -> np.ndarray:
         """int32 [n_a, n_b]: equal positions of every row of A against every row of B (mhx_jaccard_matrix)."""
@@ -967,20 +981,14 @@ class Context:
         larger answer costs one more call."""
         m = probes.shape[0]
         d_q = self.to_device(probes)
-        cap = int(capacity) if capacity is not None else max(4 * m, 1 << 16)
-        while True:
+
+        def call(cap, found):
             d_pairs = self.alloc(cap * 16)
-            found = _i64(0)
             check(self.lib.mhx_lsh_query_dev(self.handle, _vp(d_dig), _vp(d_rows), int(n), int(b), int(r), _vp(d_q.ptr), _vp(d_sig),
-                                             int(code), int(k), m, _vp(d_pairs.ptr), cap, ctypes.byref(found)))
-            if found.value <= cap:
-                break
-            cap = int(found.value)
-        self.synchronize()
-        pairs = d_pairs.download((found.value, 2), np.int64) if found.value else np.empty((0, 2), dtype=np.int64)
-        offsets = np.zeros(m + 1, dtype=np.int64)
-        np.cumsum(np.bincount(pairs[:, 0], minlength=m), out=offsets[1:])
-        return offsets, np.ascontiguousarray(pairs[:, 1])
+                                             int(code), int(k), m, _vp(d_pairs.ptr), cap, found))
+            return d_pairs
+
+        return self._pairs_to_offsets(*self._capacity_retry(call, capacity if capacity is not None else max(4 * m, 1 << 16)), m)
 
     def lsh_ensemble_query_dev(self, levels, start: np.ndarray, d_sig: int, code: int, k: int, probes: np.ndarray, choice: np.ndarray,
                                params: np.ndarray, capacity: Optional[int] = None):
@@ -993,22 +1001,16 @@ class Context:
         params = np.ascontiguousarray(params, dtype=np.int32)
         d_q = self.to_device(probes)
         d_choice = self.to_device(np.ascontiguousarray(choice, dtype=np.uint8))
-        cap = int(capacity) if capacity is not None else max(4 * m, 1 << 16)
-        while True:
+
+        def call(cap, found):
             d_pairs = self.alloc(cap * 16)
-            found = _i64(0)
             check(self.lib.mhx_lsh_ensemble_query_dev(self.handle, c_levels, len(levels), start.ctypes.data_as(ctypes.POINTER(_i64)),
                                                       start.size - 1, _vp(d_sig), int(code), int(k), _vp(d_q.ptr), m, _vp(d_choice.ptr),
                                                       params.ctypes.data_as(ctypes.POINTER(_i32)), params.shape[0], _vp(d_pairs.ptr), cap,
-                                                      ctypes.byref(found)))
-            if found.value <= cap:
-                break
-            cap = int(found.value)
-        self.synchronize()
-        pairs = d_pairs.download((found.value, 2), np.int64) if found.value else np.empty((0, 2), dtype=np.int64)
-        offsets = np.zeros(m + 1, dtype=np.int64)
-        np.cumsum(np.bincount(pairs[:, 0], minlength=m), out=offsets[1:])
-        return offsets, np.ascontiguousarray(pairs[:, 1])
+                                                      found))
+            return d_pairs
+
+        return self._pairs_to_offsets(*self._capacity_retry(call, capacity if capacity is not None else max(4 * m, 1 << 16)), m)
 
     def lsh_forest_build_dev(self, d_sig: int, sig_dtype: int, n: int, row_words: int, l: int, tree_words: int, d_order: int) -> None:
         """mhx_lsh_forest_build_dev_typed: per tree, the rows ascending by (the tree's words, row) into order u32[l][n]; enqueued."""

@@ -1,4 +1,4 @@
-// device_scan.h -- the hand-written device-wide exclusive scan of lsh_kernels.hip, shared with lsh_index_kernels.hip.
+// device_scan.h -- the hand-written device-wide exclusive scan, and the read-back of its total: lsh_query_kernels.hip and lsh_index_kernels.hip.
 // Header-only: every kernel and helper is in an anonymous namespace, so each translation unit that includes it has its own copy.
 #pragma once
 
@@ -126,6 +126,13 @@ int device_exclusive_scan(mhx_ctx *ctx, In in, Out out, int64_t n, void *d_tmp, 
     hipLaunchKernelGGL(scan_tile_offsets_kernel, dim3(1), dim3(1024), 0, ctx->stream, tiles, n_tiles, *d_total);
     hipLaunchKernelGGL((scan_apply_kernel<In, Out>), dim3((unsigned)n_tiles), dim3(256), 0, ctx->stream, in, n, tiles, out);
     MHX_HIP_CHECK(hipGetLastError());
+    return MHX_OK;
+}
+
+// one device word -- a scan's total -- back on the host: blocks until the stream has drained
+inline int read_back_u64(mhx_ctx *ctx, const uint64_t *d_word, uint64_t *word) {
+    MHX_HIP_CHECK(hipMemcpyAsync(word, d_word, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+    MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
     return MHX_OK;
 }
 

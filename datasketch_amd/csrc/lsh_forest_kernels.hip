@@ -28,10 +28,6 @@
 namespace mhx {
 namespace {
 
-unsigned forest_grid(const mhx_ctx *ctx, int64_t items) {
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + 255) / 256, (int64_t)ctx->num_cus * 32));
-}
-
 // ---- build --------------------------------------------------------------------------------------------------------------
 // keys[t * n + i] = (t << 32) | half-word `col32` of tree t's key of the slot at position i of tree t's current order (the slots
 // in slot order when there is none yet: the first pass, which also writes that order for the sort to carry).
@@ -204,14 +200,13 @@ int launch_lsh_forest_build(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int6
                                              (uint32_t *)nullptr, (size_t)total, 0, end_bit, ctx->stream);
     if (e != hipSuccess) return fail(MHX_ERR_HIP, "rocprim::radix_sort_pairs (size query) failed: %s", hipGetErrorString(e));
     // scratch[3]: keys u64[total] | sorted keys u64[total] | the other order buffer u32[total] | sort temporary
-    const size_t key_bytes = ((sizeof(uint64_t) * (size_t)total) + 255) & ~(size_t)255;
-    const size_t val_bytes = ((sizeof(uint32_t) * (size_t)total) + 255) & ~(size_t)255;
+    const size_t key_bytes = pad256(sizeof(uint64_t) * (size_t)total), val_bytes = pad256(sizeof(uint32_t) * (size_t)total);
     if (int rc = ctx->ensure_scratch(3, 2 * key_bytes + val_bytes + tmp_bytes + 256)) return rc;
     char *base = (char *)ctx->scratch[3];
     uint64_t *d_keys = (uint64_t *)base, *d_keys_sorted = (uint64_t *)(base + key_bytes);
     uint32_t *d_other = (uint32_t *)(base + 2 * key_bytes);
     void *d_tmp = base + 2 * key_bytes + val_bytes;
-    const dim3 grid(forest_grid(ctx, total));
+    const dim3 grid(grid_for(ctx, total, 32));
     for (int p = 0; p < passes; ++p) {  // least significant half-word first; the last pass lands in d_order
         const int word = tree_words - 1 - p / halves;
         const int64_t col32 = (int64_t)word * halves + (halves == 2 ? p % 2 : 0);
@@ -242,7 +237,7 @@ int launch_lsh_forest_query(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int6
     if (lds + 64 > (size_t)ctx->lds_per_block) return fail(MHX_ERR_UNSUPPORTED, "%zu bytes of LDS per workgroup are not available", lds);
     if (int rc = ctx->ensure_scratch(3, sizeof(uint4) * (size_t)m * (size_t)l)) return rc;
     uint4 *d_win = (uint4 *)ctx->scratch[3];
-    const dim3 sgrid(forest_grid(ctx, m * l)), rgrid((unsigned)(per_wave ? (m + 3) / 4 : m));
+    const dim3 sgrid(grid_for(ctx, m * l, 32)), rgrid((unsigned)(per_wave ? (m + 3) / 4 : m));
 #define MHX_FOREST_QUERY(T)                                                                                                              \
     do {                                                                                                                                 \
         hipLaunchKernelGGL(forest_search_kernel<T>, sgrid, dim3(256), 0, ctx->stream, (const T *)d_sig, n, row_words, l, tree_words, w,  \

@@ -187,15 +187,11 @@ __global__ __launch_bounds__(256) void rows_compact_kernel(const V *__restrict__
     }
 }
 
-unsigned grid_of(const mhx_ctx *ctx, int64_t items) {
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + 255) / 256, (int64_t)ctx->num_cus * 16));
-}
-
 // scratch[3]: prefix u32[n_words] | scan temporary; the popcount scan enqueued, its total in *d_total
 int live_prefix(mhx_ctx *ctx, const uint32_t *d_bits, int64_t n, size_t extra_tmp, uint32_t **d_prefix, void **d_tmp,
                 uint64_t **d_total) {
     const int64_t n_words = (n + 31) / 32;
-    const size_t prefix_bytes = ((sizeof(uint32_t) * (size_t)n_words) + 255) & ~(size_t)255;
+    const size_t prefix_bytes = pad256(sizeof(uint32_t) * (size_t)n_words);
     const size_t tmp = std::max(scan_tmp_bytes(n_words), extra_tmp);
     if (int rc = ctx->ensure_scratch(3, prefix_bytes + tmp)) return rc;
     *d_prefix = (uint32_t *)ctx->scratch[3];
@@ -216,7 +212,7 @@ int launch_lsh_bands_merge(mhx_ctx *ctx, const uint64_t *d_dig_a, const uint32_t
     if (tiles * bands * kMergeThreads >= ((int64_t)1 << 32)) return fail(MHX_ERR_UNSUPPORTED, "too many merge tiles for one launch");
     if (int rc = ctx->ensure_scratch(3, sizeof(int64_t) * (size_t)bands * (size_t)(tiles + 1))) return rc;
     int64_t *d_part = (int64_t *)ctx->scratch[3];
-    hipLaunchKernelGGL(bands_merge_partition_kernel, dim3(grid_of(ctx, (int64_t)bands * (tiles + 1))), dim3(256), 0, ctx->stream,
+    hipLaunchKernelGGL(bands_merge_partition_kernel, dim3(grid_for(ctx, (int64_t)bands * (tiles + 1))), dim3(256), 0, ctx->stream,
                        d_dig_a, n_a, d_dig_b, n_b, bands, tiles, tile, d_part);
     if (items == 16)
         hipLaunchKernelGGL(bands_merge_kernel<16>, dim3((unsigned)(tiles * bands)), dim3(kMergeThreads), 0, ctx->stream, d_dig_a, d_rows_a,
@@ -236,8 +232,7 @@ int launch_lsh_bands_compact(mhx_ctx *ctx, const uint64_t *d_dig, const uint32_t
     uint64_t *d_live_total = nullptr, *d_kept_total = nullptr;
     if (int rc = live_prefix(ctx, d_live_bits, n, scan_tmp_bytes(total) + 256, &d_prefix, &d_tmp, &d_live_total)) return rc;
     uint64_t live_total = 0;  // once it is read back, the flat scan below reuses the popcount scan's temporary
-    MHX_HIP_CHECK(hipMemcpyAsync(&live_total, d_live_total, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (int rc = read_back_u64(ctx, d_live_total, &live_total)) return rc;
     if ((int64_t)live_total != n_live)
         return fail(MHX_ERR_INVALID, "n_live %lld differs from the %llu live slots of the bitmap", (long long)n_live,
                     (unsigned long long)live_total);
@@ -247,8 +242,7 @@ int launch_lsh_bands_compact(mhx_ctx *ctx, const uint64_t *d_dig, const uint32_t
                                        &d_kept_total))
         return rc;
     uint64_t kept = 0;
-    MHX_HIP_CHECK(hipMemcpyAsync(&kept, d_kept_total, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (int rc = read_back_u64(ctx, d_kept_total, &kept)) return rc;
     if ((int64_t)kept != limit)
         return fail(MHX_ERR_INVALID, "the bands hold %llu live entries, not bands * n_live = %lld (is every band a permutation of the slots?)",
                     (unsigned long long)kept, (long long)limit);
@@ -264,7 +258,7 @@ int launch_rows_compact(mhx_ctx *ctx, const void *d_src, int64_t row_bytes, int6
     const uintptr_t align = reinterpret_cast<uintptr_t>(d_src) | reinterpret_cast<uintptr_t>(d_dst) | (uintptr_t)row_bytes;
     const int unit = align % 16 == 0 ? 16 : align % 8 == 0 ? 8 : align % 4 == 0 ? 4 : 1;
     const int64_t units = row_bytes / unit;
-    const dim3 grid(grid_of(ctx, n_rows * units));
+    const dim3 grid(grid_for(ctx, n_rows * units));
     if (unit == 16)
         hipLaunchKernelGGL(rows_compact_kernel<uint4>, grid, dim3(256), 0, ctx->stream, (const uint4 *)d_src, units, n_rows, d_live_bits,
                            d_prefix, (uint4 *)d_dst);
@@ -279,8 +273,7 @@ int launch_rows_compact(mhx_ctx *ctx, const void *d_src, int64_t row_bytes, int6
                            d_live_bits, d_prefix, (uint8_t *)d_dst);
     MHX_HIP_CHECK(hipGetLastError());
     uint64_t kept = 0;
-    MHX_HIP_CHECK(hipMemcpyAsync(&kept, d_total, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+    if (int rc = read_back_u64(ctx, d_total, &kept)) return rc;
     *n_kept = (int64_t)kept;
     return MHX_OK;
 }

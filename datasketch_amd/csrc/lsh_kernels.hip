@@ -5,15 +5,15 @@
 // key in at least one band.  Here the grouping is a sort: per band, the 64-bit digests of the band keys
 // (pack_kernels.hip: FNV-1a-64 of exactly the reference's key bytes) are sorted together with the row
 // numbers, so every bucket becomes a run of equal digests.  The bucketing itself is hand-written (two or three passes, below);
-// its fallback for corpora it cannot bin, and the sort of the raw candidate pairs, are rocPRIM's device radix sort (a library
-// primitive) -- everything around it, including the scans and the deduplication, is ours.
+// its fallback for corpora it cannot bin is rocPRIM's device radix sort (a library
+// primitive) -- everything around it is ours.  What reads the sorted bands -- candidate pairs, the bulk query, the ensemble's query --
+// is lsh_query_kernels.hip.
 #include <cstring>
 
 #include <rocprim/device/device_radix_sort.hpp>
 
 #include "band_digest.h"
 #include "mhx_internal.h"
-#include "device_scan.h"
 
 namespace mhx {
 namespace {
@@ -443,197 +443,7 @@ __global__ __launch_bounds__(256) void order_mixed_runs_kernel(const uint64_t *_
     }
 }
 
-// ---- candidate pairs from the sorted bands --------------------------------------------------------
-// A bucket is a run of equal digests inside one band.  Element p of a run that starts at s pairs with
-// the p - s elements in front of it, so the run of length L yields L(L-1)/2 pairs, each exactly once.
-// Most elements are alone in their bucket: only an element that equals its predecessor looks for the
-// start of its run (binary search in the sorted band, ~log2 n reads).
-
-// ahead[p] = number of earlier elements of p's run (0 for a run's first element)
-__global__ __launch_bounds__(256) void run_position_kernel(const uint64_t *__restrict__ digests, int64_t n, int64_t total,
-                                                           uint32_t *__restrict__ ahead) {
-    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t band_start = p / n * n;
-        uint32_t c = 0;
-        if (p > band_start && digests[p] == digests[p - 1]) {
-            const uint64_t d = digests[p];
-            int64_t lo = band_start, hi = p - 1;  // first index in [band_start, p-1] holding d
-            while (lo < hi) {
-                const int64_t mid = (lo + hi) >> 1;
-                if (digests[mid] < d) lo = mid + 1; else hi = mid;
-            }
-            c = (uint32_t)(p - lo);
-        }
-        ahead[p] = c;
-    }
-}
-
-// raw[where[p] + q] = (min(row_p, row_q) << 32) | max(row_p, row_q) for the ahead[p] elements q in front of p
-__global__ __launch_bounds__(256) void emit_pairs_kernel(const uint32_t *__restrict__ rows, const uint32_t *__restrict__ ahead,
-                                                         const uint64_t *__restrict__ where, int64_t total,
-                                                         uint64_t *__restrict__ raw) {
-    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < total; p += (int64_t)gridDim.x * blockDim.x) {
-        const uint32_t c = ahead[p];
-        if (c == 0) continue;
-        const uint32_t me = rows[p];
-        uint64_t *dst = raw + where[p];
-        for (uint32_t q = 0; q < c; ++q) {
-            const uint32_t other = rows[p - c + q];
-            const uint32_t lo = me < other ? me : other, hi = me < other ? other : me;
-            dst[q] = ((uint64_t)lo << 32) | hi;
-        }
-    }
-}
-
-__global__ __launch_bounds__(256) void unpack_pairs_kernel(const uint64_t *__restrict__ keys, int64_t count,
-                                                           int64_t *__restrict__ pairs) {
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) {
-        const uint64_t key = keys[i];
-        longlong2 v;
-        v.x = (long long)(key >> 32);
-        v.y = (long long)(key & 0xFFFFFFFFu);
-        reinterpret_cast<longlong2 *>(pairs)[i] = v;
-    }
-}
-
-
-// ---- bulk query against sorted bands ---------------------------------------------------------------
-// What MinHashLSH.query does per probe (ref: datasketch/lsh.py:423-431: for every band, look the band key up
-// in that band's dictionary and union the buckets), for M probes at once against an index of n rows held as
-// sorted bands: the probe's band digest is located by binary search in the band's ascending digests; the
-// matching run is its bucket.
-
-// per (probe q, band j): first[idx] = position of the first equal digest in the band, count[idx] = run length
-__global__ __launch_bounds__(256) void query_ranges_kernel(const uint64_t *__restrict__ q_digests, int64_t m, int32_t bands,
-                                                           const uint64_t *__restrict__ sorted_digests, int64_t n,
-                                                           uint32_t *__restrict__ first, uint32_t *__restrict__ count) {
-    const int64_t total = m * (int64_t)bands;
-    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-        const int band = (int)(idx % bands);
-        const uint64_t d = q_digests[idx];
-        const uint64_t *col = sorted_digests + (int64_t)band * n;
-        int64_t lo = 0, hi = n;  // lower bound
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (col[mid] < d) lo = mid + 1; else hi = mid;
-        }
-        int64_t end = lo;
-        if (lo < n && col[lo] == d) {  // upper bound by galloping: buckets are short
-            int64_t step = 1;
-            end = lo + 1;
-            while (end < n && col[end] == d) {
-                end = std::min<int64_t>(n, end + step);
-                step <<= 1;
-            }
-            int64_t a = std::max<int64_t>(lo, end - step / 2 - 1), b = end;  // last equal is in [a, b)
-            while (a < b) {
-                const int64_t mid = (a + b) >> 1;
-                if (col[mid] <= d) a = mid + 1; else b = mid;
-            }
-            end = a;
-        }
-        first[idx] = (uint32_t)lo;
-        count[idx] = (uint32_t)(end - lo);
-    }
-}
-
-// raw[where[idx] + i] = (q << 32) | row for the rows of the probe's bucket in band j.  With VERIFY the r words of
-// the band are compared (probe signature against index signature): a 64-bit digest collision between different
-// band keys then yields no candidate -- exactly the reference's dictionary semantics -- and the slot gets ~0.
-template <typename SigT, bool VERIFY>
-__global__ __launch_bounds__(256) void query_emit_kernel(const uint32_t *__restrict__ first, const uint32_t *__restrict__ count,
-                                                         const uint64_t *__restrict__ where, int64_t m, int32_t bands, int64_t n,
-                                                         const uint32_t *__restrict__ sorted_rows,
-                                                         const SigT *__restrict__ q_sig, const SigT *__restrict__ idx_sig,
-                                                         int32_t k, int32_t r, uint64_t *__restrict__ raw) {
-    const int64_t total = m * (int64_t)bands;
-    for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
-        const uint32_t c = count[idx];
-        if (c == 0) continue;
-        const int64_t q = idx / bands;
-        const int band = (int)(idx - q * bands);
-        const uint32_t *rows = sorted_rows + (int64_t)band * n + first[idx];
-        uint64_t *dst = raw + where[idx];
-        for (uint32_t i = 0; i < c; ++i) {
-            const uint32_t row = rows[i];
-            bool same = true;
-            if (VERIFY) {
-                const SigT *x = q_sig + q * k + (int64_t)band * r, *y = idx_sig + (int64_t)row * k + (int64_t)band * r;
-                for (int w = 0; w < r; ++w) same &= x[w] == y[w];
-            }
-            dst[i] = same ? (((uint64_t)q << 32) | row) : ~0ull;
-        }
-    }
-}
-
-// the device-wide exclusive scan (device_exclusive_scan) is in device_scan.h: lsh_index_kernels.hip uses it too
-
-unsigned grid_for(const mhx_ctx *ctx, int64_t items) {
-    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + 255) / 256, (int64_t)ctx->num_cus * 16));
-}
-
 }  // namespace
-
-int launch_lsh_candidate_pairs(mhx_ctx *ctx, const uint64_t *d_sorted_digests, const uint32_t *d_sorted_rows, int64_t n,
-                               int32_t bands, int64_t *d_pairs, int64_t capacity, int64_t *n_pairs, int64_t *n_raw) {
-    *n_pairs = 0;
-    if (n_raw) *n_raw = 0;
-    const int64_t total = n * (int64_t)bands;
-    if (total == 0) return MHX_OK;
-    // scratch[4], first part: ahead u32[total] | where u64[total] | tail u64[2] | scan temporary
-    const size_t ahead_bytes = ((sizeof(uint32_t) * (size_t)total) + 255) & ~(size_t)255;
-    const size_t where_bytes = ((sizeof(uint64_t) * (size_t)total) + 255) & ~(size_t)255;
-    const size_t scan_tmp = scan_tmp_bytes(total);
-    if (int rc = ctx->ensure_scratch(4, ahead_bytes + where_bytes + 256 + scan_tmp)) return rc;
-    uint32_t *d_ahead = (uint32_t *)ctx->scratch[4];
-    uint64_t *d_where = (uint64_t *)((char *)ctx->scratch[4] + ahead_bytes);
-    void *d_scan_tmp = (char *)ctx->scratch[4] + ahead_bytes + where_bytes + 256;
-    hipLaunchKernelGGL(run_position_kernel, dim3(grid_for(ctx, total)), dim3(256), 0, ctx->stream, d_sorted_digests, n, total,
-                       d_ahead);
-    MHX_HIP_CHECK(hipGetLastError());
-    uint64_t *d_raw_total = nullptr;
-    if (int rc = device_exclusive_scan(ctx, CountsIn{d_ahead}, WhereOut{d_where}, total, d_scan_tmp, &d_raw_total)) return rc;
-    uint64_t raw_total = 0;
-    MHX_HIP_CHECK(hipMemcpyAsync(&raw_total, d_raw_total, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    const int64_t raw = (int64_t)raw_total;  // pairs before deduplication across bands
-    if (n_raw) *n_raw = raw;
-    if (raw == 0) return MHX_OK;
-    if ((size_t)raw * 16 > (size_t)ctx->hbm_bytes / 2)
-        return fail(MHX_ERR_OOM, "%lld candidate pairs before deduplication (large buckets of equal band keys) do not fit in device memory",
-                    (long long)raw);
-
-    // scratch[3]: raw u64[raw] | sorted u64[raw] | count u64 | sort / select temporary
-    const size_t raw_bytes = ((sizeof(uint64_t) * (size_t)raw) + 255) & ~(size_t)255;
-    int end_bit = 33;  // the high word holds a row number < n
-    while (end_bit < 64 && ((int64_t)1 << (end_bit - 32)) < n) ++end_bit;
-    size_t sort_tmp = 0;
-    hipError_t e = rocprim::radix_sort_keys(nullptr, sort_tmp, (const uint64_t *)nullptr, (uint64_t *)nullptr, (size_t)raw, 0, end_bit,
-                                            ctx->stream);  // (the one library primitive left on this path: a radix sort of the raw pairs)
-    if (e != hipSuccess) return fail(MHX_ERR_HIP, "rocprim size query failed: %s", hipGetErrorString(e));
-    const size_t tmp_bytes = std::max(sort_tmp, scan_tmp_bytes(raw));
-    if (int rc = ctx->ensure_scratch(3, 2 * raw_bytes + 256 + tmp_bytes)) return rc;
-    uint64_t *d_raw = (uint64_t *)ctx->scratch[3];
-    uint64_t *d_sorted = (uint64_t *)((char *)ctx->scratch[3] + raw_bytes);
-    void *d_tmp = (char *)ctx->scratch[3] + 2 * raw_bytes + 256;
-    hipLaunchKernelGGL(emit_pairs_kernel, dim3(grid_for(ctx, total)), dim3(256), 0, ctx->stream, d_sorted_rows, d_ahead, d_where,
-                       total, d_raw);
-    MHX_HIP_CHECK(hipGetLastError());
-    e = rocprim::radix_sort_keys(d_tmp, sort_tmp, (const uint64_t *)d_raw, d_sorted, (size_t)raw, 0, end_bit, ctx->stream);
-    if (e != hipSuccess) return fail(MHX_ERR_HIP, "rocprim::radix_sort_keys failed: %s", hipGetErrorString(e));
-    // unique: the heads of the runs of equal sorted pairs, packed (the scan above with other functors)
-    uint64_t *d_count = nullptr;
-    if (int rc = device_exclusive_scan(ctx, HeadsIn{d_sorted}, CompactOut{d_sorted, d_raw}, raw, d_tmp, &d_count)) return rc;
-    uint64_t unique_count = 0;
-    MHX_HIP_CHECK(hipMemcpyAsync(&unique_count, d_count, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    *n_pairs = (int64_t)unique_count;
-    if ((int64_t)unique_count > capacity) return MHX_OK;  // caller sees n_pairs > capacity and calls again
-    hipLaunchKernelGGL(unpack_pairs_kernel, dim3(grid_for(ctx, (int64_t)unique_count)), dim3(256), 0, ctx->stream, d_raw,
-                       (int64_t)unique_count, d_pairs);
-    MHX_HIP_CHECK(hipGetLastError());
-    return MHX_OK;
-}
 
 // the two-pass bucketing; *done = false when a bin overflowed (the caller falls back to the radix sort)
 // [n, bands] digests -> [bands, n] (bands a power of two <= 64): a workgroup takes 2048 consecutive (row, band) pairs -- whole rows,
@@ -745,9 +555,9 @@ static int launch_lsh_bucket_bands(mhx_ctx *ctx, const void *d_sig, int sig_dtyp
     const int64_t nb = (int64_t)1 << bin_bits, bins = nb * bands;
     const int64_t big_bins = hi_bits ? ((int64_t)bands << hi_bits) : 0;
     const uint32_t cap0 = hi_bits ? (uint32_t)std::min<int64_t>(0xFFFFFFFFll, (n >> hi_bits) + (n >> hi_bits) / 32 + 4096) : 0;  // 3 % + 4096 over the mean (sigma = sqrt(mean))
-    const size_t cur_bytes = ((sizeof(uint32_t) * (size_t)(2 * bins + big_bins + 2)) + 255) & ~(size_t)255;  // cursor[bins] | overflow | cursor0[big_bins] | overflow0 | bin_start[bins]: 2 * bins + big_bins + 2 words (both overflow words counted)
+    const size_t cur_bytes = pad256(sizeof(uint32_t) * (size_t)(2 * bins + big_bins + 2));  // cursor[bins] | overflow | cursor0[big_bins] | overflow0 | bin_start[bins]: 2 * bins + big_bins + 2 words (both overflow words counted)
     const size_t dig_bytes = sizeof(uint64_t) * (size_t)bins * bin_cap, row_bytes = sizeof(uint32_t) * (size_t)bins * bin_cap;
-    const size_t dig0_bytes = ((sizeof(uint64_t) * (size_t)big_bins * cap0) + 255) & ~(size_t)255, row0_bytes = ((sizeof(uint32_t) * (size_t)big_bins * cap0) + 255) & ~(size_t)255;
+    const size_t dig0_bytes = pad256(sizeof(uint64_t) * (size_t)big_bins * cap0), row0_bytes = pad256(sizeof(uint32_t) * (size_t)big_bins * cap0);
     if (cur_bytes + dig_bytes + row_bytes + dig0_bytes + row0_bytes > (size_t)ctx->hbm_bytes / 4) return MHX_OK;
     // bands whose r values of a row share a 128-byte line go to one workgroup (at most four) -- as far as the teams'
     // staging areas fit the LDS of a workgroup; not even one team fitting, a slab that cannot be had, a launch that is
@@ -844,8 +654,8 @@ int launch_lsh_sort_bands(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_
     // scratch[3]: digests[n, bands] | keys u64[total] | sorted keys u64[total] | rows u32[total] | marks u8[total] |
     // rocPRIM temporary
     const int64_t total = n * (int64_t)bands;
-    const size_t dig_bytes = ((sizeof(uint64_t) * (size_t)total) + 255) & ~(size_t)255;
-    const size_t row_bytes = ((sizeof(uint32_t) * (size_t)total) + 255) & ~(size_t)255;
+    const size_t dig_bytes = pad256(sizeof(uint64_t) * (size_t)total);
+    const size_t row_bytes = pad256(sizeof(uint32_t) * (size_t)total);
     int band_bits = 1;
     while (((int64_t)1 << band_bits) < bands) ++band_bits;
     if (band_bits > 16) return fail(MHX_ERR_UNSUPPORTED, "more than 65536 bands");
@@ -861,7 +671,7 @@ int launch_lsh_sort_bands(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_
                                              (const uint32_t *)nullptr, (uint32_t *)nullptr, (size_t)total, 0, sort_bits,
                                              ctx->stream);
     if (e != hipSuccess) return fail(MHX_ERR_HIP, "rocprim::radix_sort_pairs (size query) failed: %s", hipGetErrorString(e));
-    const size_t mark_bytes = ((size_t)total + 255) & ~(size_t)255;
+    const size_t mark_bytes = pad256((size_t)total);
     if (int rc = ctx->ensure_scratch(3, 3 * dig_bytes + row_bytes + mark_bytes + tmp_bytes + 512)) return rc;
     uint64_t *d_dig = (uint64_t *)ctx->scratch[3];
     uint64_t *d_keys = (uint64_t *)((char *)ctx->scratch[3] + dig_bytes);
@@ -911,106 +721,6 @@ int launch_lsh_sort_bands(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_
                        d_sorted_digests, d_sorted_rows);
     MHX_HIP_CHECK(hipGetLastError());
     return MHX_OK;
-}
-
-// ---- the tail the query launchers share (launch_lsh_query here, launch_lsh_ensemble_query in lsh_ensemble_kernels.hip) ----
-// `raw` candidates (probe << 32 | row, or ~0 where the band's words differed) -> unique (probe, row) pairs, ascending.
-// scratch[3]: raw u64[raw] | sorted u64[raw] | count u64 | sort / select temporary.  lsh_raw_pairs_reserve sizes the slot and
-// hands out the raw array for the caller's emit kernel; lsh_raw_pairs_finish sorts, keeps the run heads and unpacks them.
-namespace {
-size_t raw_pair_bytes(int64_t raw) { return ((sizeof(uint64_t) * (size_t)raw) + 255) & ~(size_t)255; }
-int raw_pair_tmp_bytes(mhx_ctx *ctx, int64_t raw, size_t *sort_tmp) {
-    hipError_t e = rocprim::radix_sort_keys(nullptr, *sort_tmp, (const uint64_t *)nullptr, (uint64_t *)nullptr, (size_t)raw, 0, 64, ctx->stream);
-    if (e != hipSuccess) return fail(MHX_ERR_HIP, "rocprim size query failed: %s", hipGetErrorString(e));
-    return MHX_OK;
-}
-}  // namespace
-
-int lsh_raw_pairs_reserve(mhx_ctx *ctx, int64_t raw, uint64_t **d_raw) {
-    if ((size_t)raw * 16 > (size_t)ctx->hbm_bytes / 2)
-        return fail(MHX_ERR_OOM, "%lld candidates before deduplication do not fit in device memory", (long long)raw);
-    size_t sort_tmp = 0;
-    if (int rc = raw_pair_tmp_bytes(ctx, raw, &sort_tmp)) return rc;
-    if (int rc = ctx->ensure_scratch(3, 2 * raw_pair_bytes(raw) + 256 + std::max(sort_tmp, scan_tmp_bytes(raw)))) return rc;
-    *d_raw = (uint64_t *)ctx->scratch[3];
-    return MHX_OK;
-}
-
-int lsh_raw_pairs_finish(mhx_ctx *ctx, int64_t raw, int64_t *d_pairs, int64_t capacity, int64_t *n_pairs) {
-    const size_t raw_bytes = raw_pair_bytes(raw);
-    size_t sort_tmp = 0;
-    if (int rc = raw_pair_tmp_bytes(ctx, raw, &sort_tmp)) return rc;
-    uint64_t *d_raw = (uint64_t *)ctx->scratch[3];
-    uint64_t *d_sorted = (uint64_t *)((char *)ctx->scratch[3] + raw_bytes);
-    void *d_tmp = (char *)ctx->scratch[3] + 2 * raw_bytes + 256;
-    hipError_t e = rocprim::radix_sort_keys(d_tmp, sort_tmp, (const uint64_t *)d_raw, d_sorted, (size_t)raw, 0, 64, ctx->stream);
-    if (e != hipSuccess) return fail(MHX_ERR_HIP, "rocprim::radix_sort_keys failed: %s", hipGetErrorString(e));
-    uint64_t *d_cnt = nullptr;  // unique: the run heads of the sorted candidates, packed
-    if (int rc = device_exclusive_scan(ctx, HeadsIn{d_sorted}, CompactOut{d_sorted, d_raw}, raw, d_tmp, &d_cnt)) return rc;
-    uint64_t unique_count = 0, last_key = 0;
-    MHX_HIP_CHECK(hipMemcpyAsync(&unique_count, d_cnt, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    if (unique_count > 0) {  // a failed verification left ~0, which sorts last
-        MHX_HIP_CHECK(hipMemcpyAsync(&last_key, d_raw + (unique_count - 1), sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-        MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-        if (last_key == ~0ull) --unique_count;
-    }
-    *n_pairs = (int64_t)unique_count;
-    if ((int64_t)unique_count > capacity || unique_count == 0) return MHX_OK;  // caller sees n_pairs > capacity and calls again
-    hipLaunchKernelGGL(unpack_pairs_kernel, dim3(grid_for(ctx, (int64_t)unique_count)), dim3(256), 0, ctx->stream, d_raw,
-                       (int64_t)unique_count, d_pairs);
-    MHX_HIP_CHECK(hipGetLastError());
-    return MHX_OK;
-}
-
-int launch_lsh_query(mhx_ctx *ctx, const uint64_t *d_sorted_digests, const uint32_t *d_sorted_rows, int64_t n, int32_t bands,
-                     int32_t r, const void *d_q_sig, const void *d_idx_sig, int sig_dtype, int32_t k, int64_t m,
-                     int64_t *d_pairs, int64_t capacity, int64_t *n_pairs) {
-    *n_pairs = 0;
-    const int64_t total = m * (int64_t)bands;
-    if (total == 0 || n == 0) return MHX_OK;
-    // scratch[4]: probe digests u64[total] | first u32[total] | count u32[total] | where u64[total] | scan temporary
-    const size_t dig_bytes = ((sizeof(uint64_t) * (size_t)total) + 255) & ~(size_t)255;
-    const size_t u32_bytes = ((sizeof(uint32_t) * (size_t)total) + 255) & ~(size_t)255;
-    const size_t scan_tmp = scan_tmp_bytes(total);
-    if (int rc = ctx->ensure_scratch(4, 2 * dig_bytes + 2 * u32_bytes + 256 + scan_tmp)) return rc;
-    char *base = (char *)ctx->scratch[4];
-    uint64_t *d_qdig = (uint64_t *)base;
-    uint32_t *d_first = (uint32_t *)(base + dig_bytes);
-    uint32_t *d_count = (uint32_t *)(base + dig_bytes + u32_bytes);
-    uint64_t *d_where = (uint64_t *)(base + dig_bytes + 2 * u32_bytes);
-    void *d_scan_tmp = base + 2 * dig_bytes + 2 * u32_bytes + 256;
-    if (int rc = launch_band_digests(ctx, d_q_sig, sig_dtype, m, k, bands, r, d_qdig)) return rc;
-    const dim3 grid(grid_for(ctx, total));
-    hipLaunchKernelGGL(query_ranges_kernel, grid, dim3(256), 0, ctx->stream, d_qdig, m, bands, d_sorted_digests, n, d_first, d_count);
-    MHX_HIP_CHECK(hipGetLastError());
-    uint64_t *d_raw_total = nullptr;
-    if (int rc = device_exclusive_scan(ctx, CountsIn{d_count}, WhereOut{d_where}, total, d_scan_tmp, &d_raw_total)) return rc;
-    uint64_t raw_total = 0;
-    MHX_HIP_CHECK(hipMemcpyAsync(&raw_total, d_raw_total, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
-    const int64_t raw = (int64_t)raw_total;
-    if (raw == 0) return MHX_OK;
-    uint64_t *d_raw = nullptr;
-    if (int rc = lsh_raw_pairs_reserve(ctx, raw, &d_raw)) return rc;
-    const bool verify = d_idx_sig != nullptr;
-    if (sig_dtype == MHX_U32) {
-        if (verify)
-            hipLaunchKernelGGL((query_emit_kernel<uint32_t, true>), grid, dim3(256), 0, ctx->stream, d_first, d_count, d_where, m, bands, n,
-                               d_sorted_rows, (const uint32_t *)d_q_sig, (const uint32_t *)d_idx_sig, k, r, d_raw);
-        else
-            hipLaunchKernelGGL((query_emit_kernel<uint32_t, false>), grid, dim3(256), 0, ctx->stream, d_first, d_count, d_where, m, bands, n,
-                               d_sorted_rows, (const uint32_t *)d_q_sig, (const uint32_t *)d_idx_sig, k, r, d_raw);
-    } else {
-        if (verify)
-            hipLaunchKernelGGL((query_emit_kernel<uint64_t, true>), grid, dim3(256), 0, ctx->stream, d_first, d_count, d_where, m, bands, n,
-                               d_sorted_rows, (const uint64_t *)d_q_sig, (const uint64_t *)d_idx_sig, k, r, d_raw);
-        else
-            hipLaunchKernelGGL((query_emit_kernel<uint64_t, false>), grid, dim3(256), 0, ctx->stream, d_first, d_count, d_where, m, bands, n,
-                               d_sorted_rows, (const uint64_t *)d_q_sig, (const uint64_t *)d_idx_sig, k, r, d_raw);
-    }
-    MHX_HIP_CHECK(hipGetLastError());
-    return lsh_raw_pairs_finish(ctx, raw, d_pairs, capacity, n_pairs);
 }
 
 }  // namespace mhx

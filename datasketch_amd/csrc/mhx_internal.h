@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstdarg>
 #include <cstdint>
 #include <cstdio>
@@ -184,6 +185,7 @@ int launch_jaccard_pairs(mhx_ctx *ctx, const void *d_a, const void *d_b, int sig
                          int64_t m, int32_t *d_counts);
 int launch_weighted_dense(mhx_wgen *gen, const float *d_x, int values_are_logs, int64_t n_rows, int64_t *d_out,
                           uint8_t *d_nonempty);
+// lsh_kernels.hip builds sorted bands (launch_lsh_sort_bands); lsh_query_kernels.hip reads them (candidate pairs and the two queries)
 int launch_lsh_candidate_pairs(mhx_ctx *ctx, const uint64_t *d_sorted_digests, const uint32_t *d_sorted_rows, int64_t n,
                                int32_t bands, int64_t *d_pairs, int64_t capacity, int64_t *n_pairs, int64_t *n_raw);
 int launch_lsh_sort_bands(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n, int32_t k, int32_t bands, int32_t r,
@@ -191,11 +193,7 @@ int launch_lsh_sort_bands(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_
 int launch_lsh_query(mhx_ctx *ctx, const uint64_t *d_sorted_digests, const uint32_t *d_sorted_rows, int64_t n, int32_t bands,
                      int32_t r, const void *d_q_sig, const void *d_idx_sig, int sig_dtype, int32_t k, int64_t m,
                      int64_t *d_pairs, int64_t capacity, int64_t *n_pairs);
-// the tail of the query launchers (lsh_kernels.hip): room in scratch[3] for `raw` candidates (probe << 32 | row, ~0 = dropped),
-// which the caller's emit kernel fills; then sort, unique and unpack into (probe, row) pairs.  finish blocks (it reads the count).
-int lsh_raw_pairs_reserve(mhx_ctx *ctx, int64_t raw, uint64_t **d_raw);
-int lsh_raw_pairs_finish(mhx_ctx *ctx, int64_t raw, int64_t *d_pairs, int64_t capacity, int64_t *n_pairs);
-// lsh_ensemble_kernels.hip: the containment query over the partitions of a MinHashLSHEnsemble (mhx_lsh_ensemble_query_dev)
+// the containment query over the partitions of a MinHashLSHEnsemble (mhx_lsh_ensemble_query_dev)
 int launch_lsh_ensemble_query(mhx_ctx *ctx, const mhx_ensemble_level *levels, int32_t n_levels, const int64_t *start, int32_t n_parts,
                               const void *d_idx_sig, int sig_dtype, int32_t k, const void *d_q_sig, int64_t m, const uint8_t *d_choice,
                               const int32_t *params, int32_t n_params, int64_t *d_pairs, int64_t capacity, int64_t *n_pairs);
@@ -233,5 +231,13 @@ int launch_lsh_forest_query(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int6
                             int32_t *d_counts);
 
 int bbit_slot_size(int b);
+
+// grid of a grid-stride launch of 256-thread workgroups over `items`
+inline unsigned grid_for(const mhx_ctx *ctx, int64_t items, int blocks_per_cu = 16) {
+    return (unsigned)std::max<int64_t>(1, std::min<int64_t>((items + 255) / 256, (int64_t)ctx->num_cus * blocks_per_cu));
+}
+
+// pieces of a scratch slot start on 256-byte boundaries
+inline size_t pad256(size_t bytes) { return (bytes + 255) & ~(size_t)255; }
 
 }  // namespace mhx

@@ -61,12 +61,6 @@ def _optimal_param(threshold: float, num_perm: int, fp_weight: float, fn_weight:
     return opt
 
 
-def _starts(counts: np.ndarray) -> np.ndarray:
-    out = np.zeros(counts.size + 1, dtype=np.int64)
-    np.cumsum(counts, out=out[1:])
-    return out
-
-
 class _HostBands(HostRows):
     """The numpy back end: the signature slots and the sorted bands in host memory.  A merge is a stable ``argsort`` by digest
     of A||B, compaction a mask plus a remap, a query ``searchsorted`` per band with the band's words compared."""
@@ -105,33 +99,13 @@ class _HostBands(HostRows):
     def query(self, probes: np.ndarray):
         m, r = probes.shape[0], self.r
         pdig = lsh_bulk.band_digests(probes, self.b, r, gpu_mode="disable")
-        found_p, found_s = [], []
-        for j in range(self.b):
-            lo = np.searchsorted(self.dig[j], pdig[:, j], side="left")
-            cnt = np.searchsorted(self.dig[j], pdig[:, j], side="right") - lo
-            total = int(cnt.sum())
-            if not total:
-                continue
-            pid = np.repeat(np.arange(m, dtype=np.int64), cnt)
-            pos = np.arange(total, dtype=np.int64) + np.repeat(lo - _starts(cnt)[:-1], cnt)
-            slot = self.rows[j][pos].astype(np.int64)
-            same = np.all(self.sig[slot, j * r : (j + 1) * r] == probes[pid, j * r : (j + 1) * r], axis=1)
-            found_p.append(pid[same])
-            found_s.append(slot[same])
-        return _pairs_to_lists(found_p, found_s, m, self.n)
+        who = np.arange(m, dtype=np.int64)
+        hits = [lsh_bulk.band_hits(self.dig[j], self.rows[j], pdig[:, j], who, self.sig[:, j * r : (j + 1) * r],
+                                   probes[:, j * r : (j + 1) * r]) for j in range(self.b)]
+        return lsh_bulk._pairs_to_lists([p for p, _ in hits], [s for _, s in hits], m, self.n)
 
     def bands(self):
         return self.dig, self.rows
-
-
-def _pairs_to_lists(found_p, found_s, m: int, n: int):
-    """(offsets int64[m + 1], slots int64[...]) of unique (probe, slot) pairs, ascending."""
-    offsets = np.zeros(m + 1, dtype=np.int64)
-    if not found_p:
-        return offsets, np.empty(0, dtype=np.int64)
-    code = np.unique(np.concatenate(found_p) * max(n, 1) + np.concatenate(found_s))
-    np.cumsum(np.bincount(code // max(n, 1), minlength=m), out=offsets[1:])
-    return offsets, code % max(n, 1)
 
 
 class _DeviceBands(DeviceRows):
@@ -504,7 +478,7 @@ class MinHashLSH:
         live = kids >= 0
         nk = max(len(self._kid_key), 1)
         code = np.unique(probe[live] * nk + kids[live])
-        starts = _starts(np.bincount(code // nk, minlength=m)).tolist()
+        starts = lsh_bulk._starts(np.bincount(code // nk, minlength=m)).tolist()
         keys = list(map(self._kid_key.__getitem__, (code % nk).tolist()))
         if self.prepickle and not stored:
             keys = list(map(pickle.loads, keys))

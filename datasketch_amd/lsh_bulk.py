@@ -156,6 +156,38 @@ def band_digests(signatures, b: int, r: int, gpu_mode: str = "detect") -> np.nda
     return h
 
 
+def _starts(counts: np.ndarray) -> np.ndarray:
+    out = np.zeros(counts.size + 1, dtype=np.int64)
+    np.cumsum(counts, out=out[1:])
+    return out
+
+
+def band_hits(col: np.ndarray, rows: np.ndarray, want: np.ndarray, who: np.ndarray, sig_band: np.ndarray, probe_band: np.ndarray,
+              slot0: int = 0):
+    """The numpy back ends' lookup in ONE sorted band: ``col`` its ascending digests with ``rows`` beside them, ``want`` the
+    wanted digests of the probes ``who`` (ids into the probe matrix), ``sig_band`` / ``probe_band`` the band's columns of the
+    index and probe matrices, ``slot0`` the slot of row 0.  Every probe's bucket is the run between ``searchsorted`` left and
+    right; returns ``(probe ids, slots)`` of the bucket entries whose band words equal the probe's."""
+    lo = np.searchsorted(col, want, side="left")
+    cnt = np.searchsorted(col, want, side="right") - lo
+    total = int(cnt.sum())
+    pid = np.repeat(who, cnt)
+    pos = np.arange(total, dtype=np.int64) + np.repeat(lo - _starts(cnt)[:-1], cnt)
+    slot = slot0 + rows[pos].astype(np.int64)
+    same = np.all(sig_band[slot] == probe_band[pid], axis=1)
+    return pid[same], slot[same]
+
+
+def _pairs_to_lists(found_p, found_s, m: int, n: int):
+    """(offsets int64[m + 1], slots int64[...]) of unique (probe, slot) pairs, ascending."""
+    offsets = np.zeros(m + 1, dtype=np.int64)
+    if not found_p:
+        return offsets, np.empty(0, dtype=np.int64)
+    code = np.unique(np.concatenate(found_p) * max(n, 1) + np.concatenate(found_s))
+    np.cumsum(np.bincount(code // max(n, 1), minlength=m), out=offsets[1:])
+    return offsets, code % max(n, 1)
+
+
 def _is_dict_index(lsh) -> bool:
     """The reference's in-memory storage: ``keys`` a DictListStorage, every hashtable a DictSetStorage
     (ref: datasketch/storage.py:210-259), recognised by what they are made of."""

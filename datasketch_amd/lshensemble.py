@@ -10,7 +10,7 @@ Here the rows are sorted stably by size into ONE signature matrix (:mod:`_index_
 ``rows u32`` of ``B * N`` entries in which partition ``p`` owns ``[B * start[p], B * start[p + 1])`` -- inside that block band ``j``
 starts at ``j * n_p`` and is ascending by ``(digest, row)`` with rows local to the partition: byte for byte what
 ``mhx_lsh_sort_bands_dev_typed`` writes for the partition's rows, which is how the device back end builds it.  A batch of
-probes is answered in one call of ``mhx_lsh_ensemble_query_dev`` (csrc/lsh_ensemble_kernels.hip); which row of the table a
+probes is answered in one call of ``mhx_lsh_ensemble_query_dev`` (csrc/lsh_query_kernels.hip); which row of the table a
 (probe, partition) pair uses is floating point and is decided here, in numpy float64: the device gets a byte per pair.
 
 ``gpu_mode`` is the seam of ``MinHashLSH``: ``'always'`` / ``'detect'`` keep the index on an MI355X, ``'disable'`` (or
@@ -31,7 +31,6 @@ from scipy.integrate import quad
 
 from datasketch_amd import _native, lsh_bulk
 from datasketch_amd._index_rows import DeviceRows, HostRows
-from datasketch_amd.lsh import _pairs_to_lists, _starts
 
 __all__ = ["MinHashLSHEnsemble"]
 
@@ -185,19 +184,11 @@ class _HostEnsemble(HostRows):
                 who = np.flatnonzero(choice[:, p] == c)
                 for j in range(b):
                     at = bands * s0 + j * n_p
-                    col, want = self.dig[level][at : at + n_p], pdig[level][who, j]
-                    lo = np.searchsorted(col, want, side="left")
-                    cnt = np.searchsorted(col, want, side="right") - lo
-                    total = int(cnt.sum())
-                    if not total:
-                        continue
-                    pid = np.repeat(who, cnt)
-                    pos = np.arange(total, dtype=np.int64) + np.repeat(lo - _starts(cnt)[:-1], cnt)
-                    slot = s0 + self.rows[level][at + pos].astype(np.int64)
-                    same = np.all(self.sig[slot, j * r : (j + 1) * r] == probes[pid, j * r : (j + 1) * r], axis=1)
-                    found_p.append(pid[same])
-                    found_s.append(slot[same])
-        return _pairs_to_lists(found_p, found_s, m, self.n)
+                    pid, slot = lsh_bulk.band_hits(self.dig[level][at : at + n_p], self.rows[level][at : at + n_p], pdig[level][who, j], who,
+                                                   self.sig[:, j * r : (j + 1) * r], probes[:, j * r : (j + 1) * r], s0)
+                    found_p.append(pid)
+                    found_s.append(slot)
+        return lsh_bulk._pairs_to_lists(found_p, found_s, m, self.n)
 
     def level_buffers(self):
         return list(zip(self.dig, self.rows))

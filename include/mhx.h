@@ -561,11 +561,7 @@ MHX_API int mhx_lsh_forest_query_dev_typed(mhx_ctx *ctx, const void *d_sig, int 
  * is its bucket; a candidate is kept when the band's r words of probe and index row are equal.  d_pairs int64[capacity][2] =
  * (probe, slot = start[p] + row), ascending, unique; *n_pairs, capacity and the overflow behaviour as in mhx_lsh_query_dev.  The work is
  * the sum of the chosen b, not m * n_parts * bands.  At most MHX_ENSEMBLE_MAX_LEVELS levels and MHX_ENSEMBLE_MAX_PARAMS table rows.
- * Blocking.
- *
- * (Exported through MHX_API_EXT: the same visibility; its argument checks are tested beside the index, in
- * tests/test_gpu_lshensemble.py, and it is bound from _native._PROTOTYPES_EXT.) */
-#define MHX_API_EXT __attribute__((visibility("default")))
+ * Blocking. */
 #define MHX_ENSEMBLE_MAX_LEVELS 16
 #define MHX_ENSEMBLE_MAX_PARAMS 64
 typedef struct mhx_ensemble_level {
@@ -574,11 +570,11 @@ typedef struct mhx_ensemble_level {
     int32_t r;                 /* words per band */
     int32_t bands;             /* bands per partition block: r * bands <= row_words */
 } mhx_ensemble_level;
-MHX_API_EXT int mhx_lsh_ensemble_query_dev(mhx_ctx *ctx, const mhx_ensemble_level *levels, int32_t n_levels, const int64_t *start,
-                                           int32_t n_parts, const void *d_index_sig, int sig_dtype, int32_t row_words,
-                                           const void *d_query_sig, int64_t n_queries, const uint8_t *d_choice,
-                                           const int32_t *params, int32_t n_params, int64_t *d_pairs, int64_t capacity,
-                                           int64_t *n_pairs);
+MHX_API int mhx_lsh_ensemble_query_dev(mhx_ctx *ctx, const mhx_ensemble_level *levels, int32_t n_levels, const int64_t *start,
+                                       int32_t n_parts, const void *d_index_sig, int sig_dtype, int32_t row_words,
+                                       const void *d_query_sig, int64_t n_queries, const uint8_t *d_choice,
+                                       const int32_t *params, int32_t n_params, int64_t *d_pairs, int64_t capacity,
+                                       int64_t *n_pairs);
 
 /* ---- Multi-GPU: assemble the signature matrix (RCCL over xGMI) ----------------------------- */
 /* 128-byte RCCL unique id, created on rank 0 and distributed by the caller (env, file, socket). */

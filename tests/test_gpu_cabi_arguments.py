@@ -105,6 +105,10 @@ VALID = {
     "mhx_lsh_candidate_pairs": dict(ctx=CTX, sig=HOST, n=2, k=K, bands=2, r=4, pairs=HOST, capacity=4, n_pairs=OUT64, n_raw=OUT64),
     "mhx_lsh_query_dev": dict(ctx=CTX, d_sorted_digests=DEV, d_sorted_rows=DEV, n=2, bands=2, r=4, d_query_sig=DEV, d_index_sig=DEV, sig_dtype=0,
                               k=K, m=2, d_pairs=DEV, capacity=4, n_pairs=OUT64),
+    # (levels: a list of (d_digests, d_rows, r, bands) that Env.call lays out as mhx_ensemble_level records)
+    "mhx_lsh_ensemble_query_dev": dict(ctx=CTX, levels=[(DEV, DEV, 4, 2)], n_levels=1, start=i64(0, 2), n_parts=1, d_index_sig=DEV, sig_dtype=0,
+                                       row_words=K, d_query_sig=DEV, n_queries=2, d_choice=DEV, params=i32(0, 2), n_params=1, d_pairs=DEV,
+                                       capacity=4, n_pairs=OUT64),
     "mhx_jaccard_pairs_dev": dict(ctx=CTX, d_sig_a=DEV, d_sig_b=DEV, k=K, d_pairs=DEV, n_pairs=1, d_counts=DEV),
     "mhx_jaccard_pairs_dev_typed": dict(ctx=CTX, d_sig_a=DEV, d_sig_b=DEV, sig_dtype=0, k=K, d_pairs=DEV, n_pairs=1, d_counts=DEV),
     "mhx_jaccard_pairs": dict(ctx=CTX, sig=HOST, n=2, k=K, pairs=i64(0, 1), n_pairs=1, counts=HOST),
@@ -387,6 +391,34 @@ for changes in (dict(n=BIG), dict(m=BIG)):
 empty(E, dict(n=0), n_pairs=0)
 empty(E, dict(m=0), n_pairs=0)
 each(E, ("d_sorted_digests", "d_sorted_rows", "d_query_sig", "d_pairs"), DEVP, n_pairs=0)
+E = "mhx_lsh_ensemble_query_dev"
+case(E, dict(n_pairs=None), "n_pairs is NULL")
+sig_dtype(E, n_pairs=UNTOUCHED)
+for changes in (dict(row_words=0), dict(row_words=-16), dict(n_queries=-1), dict(capacity=-1), dict(n_parts=-1)):
+    case(E, changes, "bad shape", n_pairs=UNTOUCHED)
+for v in (0, 17):
+    case(E, dict(n_levels=v), "n_levels must be in [1, 16]", n_pairs=UNTOUCHED)
+for v in (0, 65):
+    case(E, dict(n_params=v), "n_params must be in [1, 64]", n_pairs=UNTOUCHED)
+each(E, ("levels", "start", "params"), HOSTP, n_pairs=UNTOUCHED)
+case(E, dict(start=i64(1, 1, 8, 308), n_parts=3), "start[0] must be 0", n_pairs=UNTOUCHED)
+case(E, dict(start=i64(0, 9, 8, 308), n_parts=3), "start must ascend", n_pairs=UNTOUCHED)
+for changes in (dict(start=i64(0, BIG)), dict(n_queries=BIG)):
+    case(E, changes, ROWS_32, n_pairs=UNTOUCHED)
+for level in ((DEV, DEV, 3, 6), (DEV, DEV, 0, 5), (DEV, DEV, 4, 0), (DEV, DEV, -4, -1)):  # more words than a row holds; no words; no bands
+    case(E, dict(levels=[level]), GEOMETRY, n_pairs=UNTOUCHED)
+for b in (3, 17, -1):
+    case(E, dict(params=i32(0, b)), f"params row 0: b = {b} is not in [0, 2], the bands of its level", n_pairs=UNTOUCHED)
+case(E, dict(levels=[(DEV, DEV, 1, 8), (DEV, DEV, 2, 4), (DEV, DEV, 3, 2)], n_levels=3, params=i32(0, 4, 2, 6), n_params=2),
+     "params row 1: b = 6 is not in [0, 2], the bands of its level", n_pairs=UNTOUCHED)
+for level in (3, 1, -1):
+    case(E, dict(params=i32(level, 1)), f"params row 0 names level {level} of 1", n_pairs=UNTOUCHED)
+case(E, dict(n_queries=0, d_query_sig=None, d_choice=None, d_index_sig=None, d_pairs=None, levels=[(None, None, 4, 2)]), None, n_pairs=0)
+case(E, dict(start=i64(0, 0), d_query_sig=None, d_choice=None, d_index_sig=None, d_pairs=None, levels=[(None, None, 4, 2)]), None, n_pairs=0)
+case(E, dict(n_parts=0, d_query_sig=None, d_choice=None, d_index_sig=None, d_pairs=None), None, n_pairs=0)
+for level in ((None, DEV, 4, 2), (DEV, None, 4, 2)):
+    case(E, dict(levels=[level]), DEVP, n_pairs=0)
+each(E, ("d_index_sig", "d_query_sig", "d_choice", "d_pairs"), DEVP, n_pairs=0)
 for E in ("mhx_jaccard_pairs_dev", "mhx_jaccard_pairs_dev_typed", "mhx_bbit_jaccard_pairs_dev"):
     case(E, dict(k=0), "bad shape")
     case(E, dict(n_pairs=-1), "bad shape")
@@ -566,6 +598,10 @@ class Env:
             if isinstance(v, np.ndarray):
                 keep.append(v)
                 v = v.ctypes.data
+            elif isinstance(v, list):  # levels
+                v = (_native.EnsembleLevel * len(v))(*[_native.EnsembleLevel(stand_for.get(d, d), stand_for.get(w, w), r, b) for d, w, r, b in v])
+                keep.append(v)
+                v = ctypes.addressof(v)
             elif isinstance(v, str) and v in (OUT64, OUT32):
                 obj = outs[name] = (ctypes.c_int64 if v == OUT64 else ctypes.c_int32)(UNTOUCHED)
                 v = ctypes.addressof(obj) if proto is ctypes.c_void_p else ctypes.byref(obj)

@@ -237,3 +237,19 @@ def test_two_million_rows_in_batches_removals_and_queries():
     for i in range(probes.shape[0]):
         assert sorted(got[i]) == sorted(live_keys[j] for j in rows[offsets[i] : offsets[i + 1]]), i
     assert sum(map(len, got)) > probes.shape[0]
+
+
+def test_bulk_query_with_more_band_searches_than_threads():
+    """40 000 probes x 32 bands = 1.28M (probe, band) searches: more than the 256 CUs x 16 workgroups x 256 threads the ranges and
+    emit kernels are launched with, so their grid-stride loops go round.  Against the numpy back end."""
+    rng = np.random.RandomState(11)
+    n, m, bands, r = 2000, 40_000, 32, 2
+    sig = rng.randint(0, 64, (n, bands * r)).astype(np.uint32)  # 4096 keys per band: about half the probes' bands meet a row
+    probes = rng.randint(0, 64, (m, bands * r)).astype(np.uint32)
+    host, device = L._HostBands(bands * r, bands, r, np.uint32), L._DeviceBands(_native.context(), bands * r, bands, r, np.uint32)
+    host.append(sig)
+    device.append(sig)
+    want, got = host.query(probes), device.query(probes)
+    print(f"{m * bands} searches, {want[1].size} (probe, row) pairs")
+    assert want[1].size > m
+    assert np.array_equal(got[0], want[0]) and np.array_equal(got[1], want[1])

@@ -851,6 +851,28 @@ def test_candidate_pairs_on_device(ctx, n, b, r, clusters):
     assert np.array_equal(LB.candidate_pairs(sig, b, r, gpu_mode="always"), want)
 
 
+@pytest.mark.parametrize("n", [2, 3, 4, 5, 65_536, 65_537])
+def test_candidate_pairs_at_the_sort_width_boundaries(ctx, n):
+    """The raw pairs are sorted on 32 + ceil(log2 n) bits: n around a power of two, with the pairs (0, n - 1) and (n - 2, n - 1) --
+    the largest row numbers in either word -- among the planted ones, and every pair planted in two bands (a duplicate to merge)."""
+    from datasketch_amd import lsh_bulk as LB
+
+    rng = np.random.RandomState(n)
+    b, r = 4, 2
+    sig = rng.randint(0, 2**32, (n, b * r), dtype=np.uint64)
+    sig[n - 1, : 2 * r] = sig[0, : 2 * r]              # (0, n - 1) in bands 0 and 1
+    sig[n - 2, 2 * r :] = sig[n - 1, 2 * r :]          # (n - 2, n - 1) in bands 2 and 3
+    for i in rng.randint(0, n, min(n, 200)):           # more pairs all over the row range
+        sig[i, :r] = sig[(i * 7 + 1) % n, :r]
+    want = LB.candidate_pairs(sig, b, r, gpu_mode="disable")
+    assert [0, n - 1] in want.tolist() and [max(n - 2, 0), n - 1] in want.tolist()
+    got, raw = ctx.lsh_candidate_pairs(sig, b, r)
+    print(f"n={n}: {len(want)} pairs, {raw} before deduplication")
+    assert np.array_equal(got, want) and raw > len(want)
+    tight, raw2 = ctx.lsh_candidate_pairs(sig, b, r, capacity=1)  # the second call, where the answer has more than one pair
+    assert np.array_equal(tight, want) and raw2 == raw
+
+
 @pytest.mark.parametrize("n,dim,s", [(1, 1, 1), (37, 100, 20), (300, 257, 64), (70, 4096, 128)])
 def test_weighted_dense_rows_are_compacted_on_device(ctx, n, dim, s):
     """A dense ndarray goes up as it is (mhx_weighted_minhash_many_dense builds the CSR form on the device): same
