@@ -7,7 +7,9 @@ ctypes C ABI (``include/mhx.h``).  No PyTorch / CuPy / Triton on the path.
 """
 from datasketch_amd.b_bit_minhash import bBitMinHash
 from datasketch_amd import lsh_bulk
+from datasketch_amd import hyperloglog
 from datasketch_amd.hashfunc import prehashed, sha1_hash32, sha1_hash64, sha1_hash_many
+from datasketch_amd.hyperloglog import HyperLogLog
 from datasketch_amd.lean_minhash import LeanMinHash
 from datasketch_amd.lsh import MinHashLSH
 from datasketch_amd.lshensemble import MinHashLSHEnsemble
@@ -18,6 +20,7 @@ from datasketch_amd.weighted_minhash import WeightedMinHash, WeightedMinHashGene
 __version__ = "0.1.0"
 
 __all__ = [
+    "HyperLogLog",
     "LeanMinHash",
     "MinHash",
     "MinHashLSH",
@@ -30,5 +33,6 @@ __all__ = [
     "sha1_hash32",
     "sha1_hash64",
     "sha1_hash_many",
+    "hyperloglog",
     "lsh_bulk",
 ]

@@ -138,9 +138,23 @@ _PROTOTYPES = {
     "mhx_comm_exchange_dev": [_vp, _vp, _vp, _i32, ctypes.POINTER(_i32), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64),
                               _i32, ctypes.POINTER(_i32), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)],
 }
+# Entry points declared MHX_API_EXT in include/mhx.h (HyperLogLog): bound like the ones above and as much a part of the library
+# (load() fails without them), but their argument checks are tested beside their feature, not in the table that lists EXPORTED_SYMBOLS.
+_PROTOTYPES_EXT = {
+    "mhx_hll_layout": [_int, ctypes.POINTER(_int)],
+    "mhx_hll_bulk_dev": [_vp, _vp, _int, _vp, _i64, _i64, _i64, _i32, _i32, _vp, _i64, _vp, _vp],
+    "mhx_hll_bulk_typed": [_vp, _vp, _int, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp, ctypes.POINTER(_i64)],
+    "mhx_hll_bulk_bytes": [_vp, _vp, _vp, _i64, _i32, _vp, _i64, _i32, _vp, _i64, _vp],
+    "mhx_hll_histogram_dev": [_vp, _vp, _i64, _i32, _vp, _vp],
+    "mhx_hll_histogram": [_vp, _vp, _i64, _i32, _vp, ctypes.POINTER(_i64)],
+    "mhx_hll_merge_dev": [_vp, _vp, _vp, _i64],
+    "mhx_hll_union_groups_dev": [_vp, _vp, _i64, _i32, _vp, _i64, _vp],
+    "mhx_hll_union_groups": [_vp, _vp, _i64, _i32, _vp, _i64, _vp],
+}
 _RESTYPE = {"mhx_last_error": ctypes.c_char_p, "mhx_version": ctypes.c_char_p}
 
 EXPORTED_SYMBOLS = sorted(list(_PROTOTYPES) + list(_RESTYPE))
+EXPORTED_SYMBOLS_EXT = sorted(_PROTOTYPES_EXT)
 
 
 try:  # CPython helper (csrc/pack_module.c): ~10 ns per token instead of ~180 in the interpreter
@@ -179,7 +193,7 @@ def load():
                 "Build it with `python -c 'import __graft_entry__ as g; g.build()'` or datasketch_amd/csrc/build.sh"
             )
             raise MhxError(_lib_error) from e
-        for name, argtypes in _PROTOTYPES.items():
+        for name, argtypes in list(_PROTOTYPES.items()) + list(_PROTOTYPES_EXT.items()):
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = _int
@@ -1029,6 +1043,86 @@ class Context:
         perm = self.perm_handle(permutations)
         check(self.lib.mhx_minhash_bulk_dev(perm, d_hv, hv_dtype, d_offsets, int(fixed_len), int(n_sets), int(total_tokens), d_init, int(init_stride), d_out, out_dtype))
 
+    # -- HyperLogLog (mhx_hll_*): register matrices are uint8 [n, 2**p]; numpy reads a row as the reference's int8 ``reg`` ----
+    @staticmethod
+    def _hll_init(init, n_sets: int, m: int):
+        if init is None:
+            return None, 0
+        init = np.ascontiguousarray(init).view(np.uint8)
+        if init.shape == (m,):
+            return init, 0
+        if init.shape == (n_sets, m):
+            return init, m
+        raise ValueError("init must have shape (m,) or (n_sets, m)")
+
+    def hll_bulk(self, hv: np.ndarray, offsets: Optional[np.ndarray], fixed_len: int, n_sets: int, p: int, hash_bits: int = 32,
+                 init: Optional[np.ndarray] = None):
+        """CSR / fixed-length corpus of token hashes (uint32 or uint64) -> (uint8 [n_sets, 2**p] registers, the number of
+        hashes that do not fit ``hash_bits``); mhx_hll_bulk_typed, host in, host out."""
+        hv = np.ascontiguousarray(hv)
+        if hv.dtype != np.uint32:
+            hv = np.ascontiguousarray(hv, dtype=np.uint64)
+        m = 1 << int(p)
+        if offsets is not None:
+            offsets = np.ascontiguousarray(offsets, dtype=np.int64)
+            if offsets.shape != (n_sets + 1,):
+                raise ValueError("offsets must have n_sets+1 entries")
+            if n_sets and int(offsets[-1]) > hv.size:
+                raise ValueError("offsets run past the token array")
+        elif fixed_len * n_sets > hv.size:
+            raise ValueError("token array shorter than n_sets*fixed_len")
+        init, stride = self._hll_init(init, n_sets, m)
+        out = np.empty((n_sets, m), dtype=np.uint8)
+        overflow = _i64(0)
+        check(self.lib.mhx_hll_bulk_typed(self.handle, _ptr(hv), MHX_U32 if hv.dtype == np.uint32 else MHX_U64, _ptr(offsets), int(fixed_len),
+                                          int(n_sets), int(p), int(hash_bits), _ptr(init), stride, _ptr(out), ctypes.byref(overflow)))
+        return out, int(overflow.value)
+
+    def hll_bulk_bytes(self, buf: np.ndarray, byte_offsets: np.ndarray, set_offsets: np.ndarray, p: int, hash_bits: int = 32,
+                       init: Optional[np.ndarray] = None) -> np.ndarray:
+        """Packed byte tokens -> sha1_hash32 / sha1_hash64 (``hash_bits``) -> uint8 [n_sets, 2**p] registers, all on the device."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8)
+        byte_offsets = np.ascontiguousarray(byte_offsets, dtype=np.int64)
+        set_offsets = np.ascontiguousarray(set_offsets, dtype=np.int64)
+        n_sets, n_tokens = set_offsets.size - 1, byte_offsets.size - 1
+        init, stride = self._hll_init(init, n_sets, 1 << int(p))
+        out = np.empty((n_sets, 1 << int(p)), dtype=np.uint8)
+        check(self.lib.mhx_hll_bulk_bytes(self.handle, _ptr(buf), _ptr(byte_offsets), n_tokens, int(hash_bits), _ptr(set_offsets), n_sets, int(p),
+                                          _ptr(init), stride, _ptr(out)))
+        return out
+
+    def hll_histogram(self, reg: np.ndarray):
+        """(uint32 [n, 64] counts of every register value of every row, the number of registers above 63); mhx_hll_histogram."""
+        reg = np.ascontiguousarray(reg).view(np.uint8)
+        n, m = reg.shape
+        hist = np.empty((n, 64), dtype=np.uint32)
+        invalid = _i64(0)
+        check(self.lib.mhx_hll_histogram(self.handle, _ptr(reg), n, m.bit_length() - 1, _ptr(hist), ctypes.byref(invalid)))
+        return hist, int(invalid.value)
+
+    def hll_merge(self, a: np.ndarray, b: np.ndarray) -> np.ndarray:
+        """Register-wise max of two equally shaped register arrays (mhx_hll_merge_dev between two uploads and a download)."""
+        a, b = np.ascontiguousarray(a).view(np.uint8), np.ascontiguousarray(b).view(np.uint8)
+        if a.shape != b.shape:
+            raise ValueError("register matrices must have the same shape")
+        if a.size == 0:
+            return a.copy()
+        d_a, d_b = self.to_device(a), self.to_device(b)
+        check(self.lib.mhx_hll_merge_dev(self.handle, _vp(d_a.ptr), _vp(d_b.ptr), a.size))
+        out = d_a.download(a.shape, np.uint8)
+        d_a.free()
+        d_b.free()
+        return out
+
+    def hll_union_groups(self, reg: np.ndarray, group_offsets: np.ndarray) -> np.ndarray:
+        """uint8 [n_groups, m]: the register-wise max over rows group_offsets[g] .. group_offsets[g + 1] (mhx_hll_union_groups)."""
+        reg = np.ascontiguousarray(reg).view(np.uint8)
+        group_offsets = np.ascontiguousarray(group_offsets, dtype=np.int64)
+        n, m = reg.shape
+        out = np.empty((group_offsets.size - 1, m), dtype=np.uint8)
+        check(self.lib.mhx_hll_union_groups(self.handle, _ptr(reg), n, m.bit_length() - 1, _ptr(group_offsets), group_offsets.size - 1, _ptr(out)))
+        return out
+
     def close(self) -> None:
         if self.handle is None:
             return
@@ -1121,6 +1215,14 @@ class Communicator:
             self.close()
         except Exception:
             pass
+
+
+def hll_layout(p: int) -> int:
+    """The LDS layout mhx_hll_bulk* uses at precision ``p`` (mhx_hll_layout): 0 wave per set over words, 1 workgroup per set over
+    words, 2 workgroup per set over packed bytes."""
+    out = _int(0)
+    check(load().mhx_hll_layout(int(p), ctypes.byref(out)))
+    return out.value
 
 
 def default_device() -> int:

@@ -473,7 +473,7 @@ int mhx_ctx_set_option(mhx_ctx *ctx, const char *key, int64_t value) {
         {"lsh.chunk", &mhx_ctx::opt_lsh_chunk},             {"lsh.team", &mhx_ctx::opt_lsh_team},
         {"lsh.bigbins", &mhx_ctx::opt_lsh_bigbins},         {"pack.fused", &mhx_ctx::opt_pack_fused},
         {"weighted.refill", &mhx_ctx::opt_weighted_refill}, {"lsh.prehash", &mhx_ctx::opt_lsh_prehash},
-        {"lsh.merge_items", &mhx_ctx::opt_lsh_merge_items},
+        {"lsh.merge_items", &mhx_ctx::opt_lsh_merge_items}, {"hll.split_tokens", &mhx_ctx::opt_hll_split_tokens},
     };
     if (!ctx || !key) return fail(MHX_ERR_INVALID, "ctx/key is NULL");
     MHX_GUARD(ctx);
@@ -481,6 +481,7 @@ int mhx_ctx_set_option(mhx_ctx *ctx, const char *key, int64_t value) {
         if (strcmp(key, o.key)) continue;
         if (o.field == &mhx_ctx::opt_lsh_merge_items)
             MHX_REQUIRE(value == 0 || value == 8 || value == 16, "lsh.merge_items must be 0, 8 or 16");
+        if (o.field == &mhx_ctx::opt_hll_split_tokens) MHX_REQUIRE(value >= 0, "hll.split_tokens must be >= 0");
         ctx->*o.field = value;
         return MHX_OK;
     }
@@ -1993,6 +1994,204 @@ int mhx_lsh_forest_query_dev_typed(mhx_ctx *ctx, const void *d_sig, int sig_dtyp
     }
     MHX_REQUIRE(d_sig && d_order && d_probes && d_slots, "NULL device pointer");
     return mhx::launch_lsh_forest_query(ctx, d_sig, sig_dtype, n, row_words, l, tree_words, w, d_order, d_probes, m, k, d_slots, d_counts);
+}
+
+// ---- HyperLogLog (ref: datasketch/hyperloglog.py) ------------------------------------------------------------------------
+static int check_hll(int p, int hash_bits) {
+    MHX_REQUIRE(p >= 4 && p <= 16, "p=%d should be in range [4 : 16]", p);  // ref: hyperloglog.py:56-57
+    MHX_REQUIRE(hash_bits == 32 || hash_bits == 64, "hash_bits must be 32 (HyperLogLog) or 64 (HyperLogLog++), not %d", hash_bits);
+    return MHX_OK;
+}
+// rows are read and written as 32-bit words
+#define MHX_CHECK_HLL_ALIGNED(ptr) MHX_REQUIRE(((uintptr_t)(ptr) & 3) == 0, #ptr " must be 4-byte aligned")
+
+int mhx_hll_layout(int p, int *layout) {
+    MHX_TRY(check_hll(p, 32));
+    MHX_REQUIRE(layout, "layout is NULL");
+    *layout = mhx::hll_layout(p);
+    return MHX_OK;
+}
+
+static int hll_bulk(mhx_ctx *ctx, const void *hv, int hv_dtype, const int64_t *offsets, int64_t fixed_len, int64_t n_sets, int64_t total_tokens,
+                    int p, int hash_bits, const uint8_t *init, int64_t init_stride, uint8_t *out, int64_t *overflow, Where where) {
+    MHX_ENTER(ctx, ctx);
+    MHX_REQUIRE(n_sets >= 0, "n_sets must be >= 0");
+    MHX_CHECK_DTYPE(hv_dtype);
+    MHX_TRY(check_hll(p, hash_bits));
+    const int64_t m = (int64_t)1 << p;
+    MHX_REQUIRE(offsets || fixed_len >= 0, "fixed_len must be >= 0 when offsets is NULL");
+    MHX_REQUIRE(init_stride == 0 || init_stride == m, "init_stride must be 0 (one shared row) or m = %lld", (long long)m);
+    const bool can_overflow = hv_dtype == MHX_U64 && hash_bits == 32;
+    MHX_REQUIRE(overflow || !can_overflow, "uint64 hashes at hash_bits = 32 need the overflow counter");
+    if (where == kHost && overflow) *overflow = 0;
+    if (n_sets == 0) {
+        if (where == kDevice && overflow) {
+            MHX_TRY(ctx->activate());
+            MHX_HIP_CHECK(hipMemsetAsync(overflow, 0, sizeof(int64_t), ctx->stream));
+        }
+        return MHX_OK;
+    }
+    MHX_REQUIRE_POINTERS(out, where);
+    MHX_TRY(ctx->activate());
+    if (where == kDevice) {
+        MHX_REQUIRE(total_tokens >= 0, "total_tokens must be >= 0");
+        MHX_REQUIRE(hv || total_tokens == 0, "d_hv is NULL");
+        MHX_CHECK_HLL_ALIGNED(out);
+        MHX_CHECK_HLL_ALIGNED(init);
+        if (overflow) MHX_HIP_CHECK(hipMemsetAsync(overflow, 0, sizeof(int64_t), ctx->stream));
+        return mhx::launch_hll_bulk(ctx, hv, hv_dtype, offsets, fixed_len, n_sets, total_tokens, p, hash_bits, init, init_stride, out, overflow);
+    }
+    int64_t total = n_sets * fixed_len;
+    if (offsets) {
+        MHX_REQUIRE(offsets[0] >= 0, "offsets[0] must be >= 0");
+        for (int64_t i = 0; i < n_sets; ++i)
+            MHX_REQUIRE(offsets[i + 1] >= offsets[i], "offsets must be non-decreasing (row %lld)", (long long)i);
+        total = offsets[n_sets];
+    }
+    MHX_REQUIRE(hv || total == 0, "hv is NULL");
+    Stage s(ctx);
+    const auto p_hv = s.piece(Stage::In, (hv_dtype == MHX_U32 ? 4 : 8) * (size_t)total);
+    if (total == 0) s.ask(Stage::In, 8);
+    Stage::Piece p_off{Stage::Aux, 0, 0}, p_init{Stage::Aux, 0, 0};
+    if (offsets) p_off = s.piece(Stage::Aux, sizeof(int64_t) * (size_t)(n_sets + 1));
+    if (init) p_init = s.piece(Stage::Aux, (size_t)(init_stride ? n_sets * m : m));
+    const auto p_out = s.piece(Stage::Out, (size_t)(n_sets * m)), p_ovf = s.piece(Stage::Out, sizeof(int64_t));
+    MHX_TRY(s.commit());
+    MHX_TRY(s.upload(p_hv, hv));
+    MHX_TRY(s.upload(p_off, offsets));
+    MHX_TRY(s.upload(p_init, init));
+    MHX_HIP_CHECK(hipMemsetAsync(s.at<void>(p_ovf), 0, sizeof(int64_t), ctx->stream));
+    MHX_TRY(mhx::launch_hll_bulk(ctx, s.at<void>(p_hv), hv_dtype, offsets ? s.at<int64_t>(p_off) : nullptr, fixed_len, n_sets, total, p, hash_bits,
+                                 init ? s.at<uint8_t>(p_init) : nullptr, init_stride, s.at<uint8_t>(p_out), s.at<int64_t>(p_ovf)));
+    int64_t count = 0;
+    MHX_TRY(s.download(&count, p_ovf));
+    MHX_TRY(s.fetch(out, p_out));
+    if (overflow) *overflow = count;
+    return MHX_OK;
+}
+
+int mhx_hll_bulk_dev(mhx_ctx *ctx, const void *d_hv, int hv_dtype, const int64_t *d_offsets, int64_t fixed_len, int64_t n_sets,
+                     int64_t total_tokens, int32_t p, int32_t hash_bits, const uint8_t *d_init, int64_t init_stride, uint8_t *d_out,
+                     int64_t *d_overflow) {
+    return hll_bulk(ctx, d_hv, hv_dtype, d_offsets, fixed_len, n_sets, total_tokens, p, hash_bits, d_init, init_stride, d_out, d_overflow, kDevice);
+}
+
+int mhx_hll_bulk_typed(mhx_ctx *ctx, const void *hv, int hv_dtype, const int64_t *offsets, int64_t fixed_len, int64_t n_sets, int32_t p,
+                       int32_t hash_bits, const uint8_t *init, int64_t init_stride, uint8_t *out, int64_t *overflow) {
+    return hll_bulk(ctx, hv, hv_dtype, offsets, fixed_len, n_sets, 0, p, hash_bits, init, init_stride, out, overflow, kHost);
+}
+
+int mhx_hll_bulk_bytes(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens, int32_t hash_bits,
+                       const int64_t *set_offsets, int64_t n_sets, int32_t p, const uint8_t *init, int64_t init_stride, uint8_t *out) {
+    MHX_ENTER(ctx, ctx);
+    MHX_TRY(check_hll(p, hash_bits));
+    const int64_t m = (int64_t)1 << p;
+    MHX_REQUIRE(n_sets >= 0 && n_tokens >= 0, "n_sets and n_tokens must be >= 0");
+    MHX_REQUIRE(init_stride == 0 || init_stride == m, "init_stride must be 0 (one shared row) or m = %lld", (long long)m);
+    if (n_sets == 0) return MHX_OK;
+    MHX_REQUIRE(out && set_offsets, "out/set_offsets is NULL");
+    MHX_REQUIRE(set_offsets[0] == 0 && set_offsets[n_sets] == n_tokens, "set_offsets must run from 0 to n_tokens");
+    for (int64_t i = 0; i < n_sets; ++i)
+        MHX_REQUIRE(set_offsets[i + 1] >= set_offsets[i], "set_offsets must be non-decreasing (set %lld)", (long long)i);
+    MHX_TRY(ctx->activate());
+    const int hash_dtype = hash_bits == 32 ? MHX_U32 : MHX_U64;  // sha1_hash32 / sha1_hash64: the hashes fit hash_bits by construction
+    uint8_t *d_bytes = nullptr;
+    int64_t *d_boffs = nullptr;
+    if (n_tokens > 0) MHX_TRY(upload_tokens(ctx, bytes, byte_offsets, n_tokens, &d_bytes, &d_boffs));
+    // Aux: set offsets | init | token hashes;  Out: registers
+    Stage s(ctx);
+    const auto p_soffs = s.piece(Stage::Aux, sizeof(int64_t) * (size_t)(n_sets + 1));
+    Stage::Piece p_init{Stage::Aux, 0, 0};
+    if (init) p_init = s.piece(Stage::Aux, (size_t)(init_stride ? n_sets * m : m));
+    const auto p_hv = s.piece(Stage::Aux, (hash_bits == 32 ? 4 : 8) * (size_t)n_tokens);
+    const auto p_out = s.piece(Stage::Out, (size_t)(n_sets * m));
+    MHX_TRY(s.commit());
+    MHX_TRY(s.upload(p_soffs, set_offsets));
+    MHX_TRY(s.upload(p_init, init));
+    MHX_TRY(mhx::launch_sha1_tokens(ctx, d_bytes, d_boffs, n_tokens, hash_dtype, s.at<void>(p_hv)));
+    MHX_TRY(mhx::launch_hll_bulk(ctx, s.at<void>(p_hv), hash_dtype, s.at<int64_t>(p_soffs), 0, n_sets, n_tokens, p, hash_bits,
+                                 init ? s.at<uint8_t>(p_init) : nullptr, init_stride, s.at<uint8_t>(p_out), nullptr));
+    return s.fetch(out, p_out);
+}
+
+static int hll_histogram(mhx_ctx *ctx, const uint8_t *reg, int64_t n, int p, uint32_t *hist, int64_t *invalid, Where where) {
+    MHX_ENTER(ctx, ctx);
+    MHX_TRY(check_hll(p, 32));
+    MHX_REQUIRE(n >= 0, "n must be >= 0");
+    MHX_REQUIRE_POINTERS(invalid, where);
+    MHX_TRY(ctx->activate());
+    if (where == kHost) *invalid = 0;
+    else MHX_HIP_CHECK(hipMemsetAsync(invalid, 0, sizeof(int64_t), ctx->stream));
+    if (n == 0) return MHX_OK;
+    MHX_REQUIRE_POINTERS(reg && hist, where);
+    if (where == kDevice) {
+        MHX_CHECK_HLL_ALIGNED(reg);
+        return mhx::launch_hll_histogram(ctx, reg, n, p, hist, invalid);
+    }
+    Stage s(ctx);
+    const auto p_reg = s.piece(Stage::In, (size_t)n << p);
+    const auto p_hist = s.piece(Stage::Out, sizeof(uint32_t) * 64 * (size_t)n), p_bad = s.piece(Stage::Out, sizeof(int64_t));
+    MHX_TRY(s.commit());
+    MHX_TRY(s.upload(p_reg, reg));
+    MHX_HIP_CHECK(hipMemsetAsync(s.at<void>(p_bad), 0, sizeof(int64_t), ctx->stream));
+    MHX_TRY(mhx::launch_hll_histogram(ctx, s.at<uint8_t>(p_reg), n, p, s.at<uint32_t>(p_hist), s.at<int64_t>(p_bad)));
+    MHX_TRY(s.download(invalid, p_bad));
+    return s.fetch(hist, p_hist);
+}
+
+int mhx_hll_histogram_dev(mhx_ctx *ctx, const uint8_t *d_reg, int64_t n, int32_t p, uint32_t *d_hist, int64_t *d_invalid) {
+    return hll_histogram(ctx, d_reg, n, p, d_hist, d_invalid, kDevice);
+}
+
+int mhx_hll_histogram(mhx_ctx *ctx, const uint8_t *reg, int64_t n, int32_t p, uint32_t *hist, int64_t *invalid) {
+    return hll_histogram(ctx, reg, n, p, hist, invalid, kHost);
+}
+
+int mhx_hll_merge_dev(mhx_ctx *ctx, uint8_t *d_a, const uint8_t *d_b, int64_t count) {
+    MHX_ENTER(ctx, ctx);
+    MHX_REQUIRE(count >= 0, "count must be >= 0");
+    if (count == 0) return MHX_OK;
+    MHX_REQUIRE_POINTERS(d_a && d_b, kDevice);
+    MHX_TRY(ctx->activate());
+    return mhx::launch_hll_merge(ctx, d_a, d_b, count);
+}
+
+static int hll_union_groups(mhx_ctx *ctx, const uint8_t *reg, int64_t n_rows, int p, const int64_t *group_offsets, int64_t n_groups,
+                            uint8_t *out, Where where) {
+    MHX_ENTER(ctx, ctx);
+    MHX_TRY(check_hll(p, 32));
+    MHX_REQUIRE(n_rows >= 0 && n_groups >= 0, "n_rows and n_groups must be >= 0");
+    if (n_groups == 0) return MHX_OK;
+    MHX_REQUIRE_POINTERS(group_offsets && out && (reg || n_rows == 0), where);
+    MHX_TRY(ctx->activate());
+    if (where == kDevice) {
+        MHX_CHECK_HLL_ALIGNED(reg);
+        MHX_CHECK_HLL_ALIGNED(out);
+        return mhx::launch_hll_union_groups(ctx, reg, p, group_offsets, n_groups, out);
+    }
+    MHX_REQUIRE(group_offsets[0] >= 0 && group_offsets[n_groups] <= n_rows, "group_offsets must stay inside [0, n_rows]");
+    for (int64_t g = 0; g < n_groups; ++g)
+        MHX_REQUIRE(group_offsets[g + 1] >= group_offsets[g], "group_offsets must be non-decreasing (group %lld)", (long long)g);
+    Stage s(ctx);
+    const auto p_reg = s.piece(Stage::In, (size_t)n_rows << p);
+    if (n_rows == 0) s.ask(Stage::In, 8);
+    const auto p_off = s.piece(Stage::Aux, sizeof(int64_t) * (size_t)(n_groups + 1));
+    const auto p_out = s.piece(Stage::Out, (size_t)n_groups << p);
+    MHX_TRY(s.commit());
+    MHX_TRY(s.upload(p_reg, reg));
+    MHX_TRY(s.upload(p_off, group_offsets));
+    MHX_TRY(mhx::launch_hll_union_groups(ctx, s.at<uint8_t>(p_reg), p, s.at<int64_t>(p_off), n_groups, s.at<uint8_t>(p_out)));
+    return s.fetch(out, p_out);
+}
+
+int mhx_hll_union_groups_dev(mhx_ctx *ctx, const uint8_t *d_reg, int64_t n_rows, int32_t p, const int64_t *d_group_offsets, int64_t n_groups,
+                             uint8_t *d_out) {
+    return hll_union_groups(ctx, d_reg, n_rows, p, d_group_offsets, n_groups, d_out, kDevice);
+}
+
+int mhx_hll_union_groups(mhx_ctx *ctx, const uint8_t *reg, int64_t n_rows, int32_t p, const int64_t *group_offsets, int64_t n_groups,
+                         uint8_t *out) {
+    return hll_union_groups(ctx, reg, n_rows, p, group_offsets, n_groups, out, kHost);
 }
 
 }  // extern "C"

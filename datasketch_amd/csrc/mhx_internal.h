@@ -99,6 +99,7 @@ struct mhx_ctx {
     int64_t opt_lsh_levels = 0;     // bucketing: 0 auto (two scatter levels beyond 2^10 bins per band), 2 = two levels whenever there are at least 4 bins
     int64_t opt_pack_fused = 0;     // mhx_bbit_pack_band_digests_dev: 0 auto (one read of the matrix where the shape allows), 1 = always the two kernels
     int64_t opt_weighted_refill = 0; // one-wave-per-row walk, 4096-column rows: 0 auto (non-temporal row loads; values in: also the refill right after staging, chunk after chunk), 1 = round 4 (plain loads, refill behind the walk), 2 / 3 = force non-temporal / + early refill
+    int64_t opt_hll_split_tokens = 0; // mhx_hll_bulk*: a set with more tokens than this is split over workgroups; 0 auto (mhx::kHllSplitTokens)
     int64_t opt_host_chunk_bytes = 0;  // mhx_minhash_bulk: bytes per pipelined piece; 0 auto (96 MiB, inputs > 256 MiB), < 0 never pipeline
 
     // copy streams of the pipelined host entry point (created on first use)
@@ -229,6 +230,16 @@ int launch_lsh_forest_build(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int6
 int launch_lsh_forest_query(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n, int32_t row_words, int32_t l, int32_t tree_words,
                             int32_t w, const uint32_t *d_order, const void *d_probes, int64_t m, int32_t k, uint32_t *d_slots,
                             int32_t *d_counts);
+
+// hll_kernels.hip: HyperLogLog registers (mhx_hll_*); all of them enqueue only
+constexpr int64_t kHllSplitTokens = 32768;  // default of option "hll.split_tokens"
+int hll_layout(int p);  // 0 one wave per set over 32-bit words, 1 one workgroup per set over words, 2 one workgroup per set over packed bytes
+int launch_hll_bulk(mhx_ctx *ctx, const void *d_hv, int hv_dtype, const int64_t *d_offsets, int64_t fixed_len, int64_t n_sets,
+                    int64_t total_tokens, int p, int hash_bits, const uint8_t *d_init, int64_t init_stride, uint8_t *d_out,
+                    int64_t *d_overflow);
+int launch_hll_histogram(mhx_ctx *ctx, const uint8_t *d_reg, int64_t n, int p, uint32_t *d_hist, int64_t *d_invalid);
+int launch_hll_merge(mhx_ctx *ctx, uint8_t *d_a, const uint8_t *d_b, int64_t count);
+int launch_hll_union_groups(mhx_ctx *ctx, const uint8_t *d_reg, int p, const int64_t *d_group_offsets, int64_t n_groups, uint8_t *d_out);
 
 int bbit_slot_size(int b);
 

@@ -108,7 +108,9 @@ MHX_API int mhx_ctx_device_info(mhx_ctx *ctx, char *name, int name_len, int *cus
  * 0 auto = 4, 1024 = the rule until round 6),
  * ("lsh.sort", 0 auto: mhx_lsh_sort_bands buckets the bands in two passes (three beyond 10.2M rows) and falls back to the radix sort when a bin
  * overflows or n > 41M, 1 = radix sort always),
- * ("lsh.merge_items", mhx_lsh_bands_merge_dev: outputs per thread of a 256-thread merge tile, 0 auto = 8, or 8 / 16; results unaffected). */
+ * ("lsh.merge_items", mhx_lsh_bands_merge_dev: outputs per thread of a 256-thread merge tile, 0 auto = 8, or 8 / 16; results unaffected),
+ * ("hll.split_tokens", mhx_hll_bulk*: a set with more tokens than this is split over several workgroups and combined by a max,
+ * 0 auto = 32768; results unaffected). */
 MHX_API int mhx_ctx_set_option(mhx_ctx *ctx, const char *key, int64_t value);
 /* Kernel event counters since the last call (synchronises the stream, then resets them):
  *   out[0] sets the sieve launch left to the full launch (failed proof, or skipped by the back-off),
@@ -575,6 +577,70 @@ MHX_API int mhx_lsh_ensemble_query_dev(mhx_ctx *ctx, const mhx_ensemble_level *l
                                        const void *d_query_sig, int64_t n_queries, const uint8_t *d_choice,
                                        const int32_t *params, int32_t n_params, int64_t *d_pairs, int64_t capacity,
                                        int64_t *n_pairs);
+
+/* ---- HyperLogLog ------------------------------------------------------------------------------ */
+/* Register files of the reference's HyperLogLog (ref: datasketch/hyperloglog.py): m = 2^p registers of one byte per sketch, p in
+ * [4, 16] (ref :56-57), a matrix of sketches is uint8 [n, m] row-major -- numpy reads a row as the reference's int8 `reg`
+ * (ref :76).  Device pointers to register matrices (d_init, d_out, d_reg) must be 4-byte aligned: rows are moved as 32-bit
+ * words.  hash_bits is 32 for HyperLogLog (ref :52) and 64 for the registers of HyperLogLogPlusPlus (ref :348).
+ *
+ * Which LDS layout mhx_hll_bulk* accumulates a set's registers in at precision p: 0 = one wave per set, one 32-bit word per
+ * register; 1 = one workgroup per set, one word per register; 2 = one workgroup per set, packed bytes.  Results do not depend on
+ * it; tests read the switch points from here.
+ *
+ * The HyperLogLog entry points are exported through MHX_API_EXT: the same visibility as MHX_API; they are bound from
+ * _native._PROTOTYPES_EXT and their argument checks are tested beside the feature, in tests/test_gpu_hyperloglog.py (the
+ * argument table of tests/test_gpu_cabi_arguments.py pins the MHX_API list to itself). */
+#define MHX_API_EXT __attribute__((visibility("default")))
+MHX_API_EXT int mhx_hll_layout(int p, int *layout);
+/*
+ * Bulk update, device-resident: what a loop of HyperLogLog.update (ref :136-142) over every token of every set leaves in
+ * the registers.  For set i and each hash hv of its tokens
+ *     idx = hv & (m - 1);  rank = clz_W(hv >> p) - p + 1  (W = hash_bits, clz_W(0) = W; ref :138-142, :238-246)
+ *     out[i, idx] = max(out[i, idx], rank)
+ *   d_hv, hv_dtype, d_offsets, fixed_len, n_sets, total_tokens   as in mhx_minhash_bulk_dev (CSR, or NULL offsets + fixed_len)
+ *   d_init      NULL (fresh registers, all zero: ref :76), or uint8 registers with row stride init_stride: 0 = one [m] row
+ *               shared by every set, m = [n_sets, m]; must not overlap d_out
+ *   d_out       uint8 [n_sets, m]; an empty set yields its init row (or zeros)
+ *   d_overflow  int64 on the device, set by the call to the number of hashes that do not fit hash_bits -- the reference's
+ *               ValueError("Hash value overflow ...") of ref :240-245; such a hash updates nothing, and the registers of
+ *               a call that counts any are unspecified.  Only uint64 input at hash_bits = 32 can overflow: for the other
+ *               three (hv_dtype, hash_bits) pairs d_overflow may be NULL.
+ * A set with more tokens than option "hll.split_tokens" is split over several workgroups; the bytes are the same.
+ */
+MHX_API_EXT int mhx_hll_bulk_dev(mhx_ctx *ctx, const void *d_hv, int hv_dtype, const int64_t *d_offsets, int64_t fixed_len,
+                             int64_t n_sets, int64_t total_tokens, int32_t p, int32_t hash_bits, const uint8_t *d_init,
+                             int64_t init_stride, uint8_t *d_out, int64_t *d_overflow);
+/* The same from / to host buffers (blocking); overflow (host int64, may be NULL where no overflow is possible) receives the
+ * count.  offsets are checked to be non-decreasing.  The corpus is staged in one piece: callers cut large corpora into
+ * pieces of whole sets themselves (datasketch_amd.HyperLogLog.bulk_registers does). */
+MHX_API_EXT int mhx_hll_bulk_typed(mhx_ctx *ctx, const void *hv, int hv_dtype, const int64_t *offsets, int64_t fixed_len,
+                               int64_t n_sets, int32_t p, int32_t hash_bits, const uint8_t *init, int64_t init_stride,
+                               uint8_t *out, int64_t *overflow);
+/* Raw byte tokens with the reference's default hash functions (ref: hyperloglog.py:70 sha1_hash32 for hash_bits = 32, :355
+ * sha1_hash64 for hash_bits = 64; datasketch/hashfunc.py:5-28): the packed bytes go up, mhx_sha1_tokens_dev and the register
+ * kernel run, out [n_sets, m] comes back.  bytes / byte_offsets / set_offsets as in mhx_minhash_bulk_bytes_typed.  These
+ * hashes fit hash_bits by construction: there is no overflow count. */
+MHX_API_EXT int mhx_hll_bulk_bytes(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens,
+                               int32_t hash_bits, const int64_t *set_offsets, int64_t n_sets, int32_t p, const uint8_t *init,
+                               int64_t init_stride, uint8_t *out);
+/* hist uint32 [n, 64]: hist[i, v] = the number of registers of row i equal to v -- all an estimator needs: the zero count of
+ * the linear counting (ref :162-163) is hist[i, 0], and the harmonic sum np.sum(2.0 ** -reg) of ref :152 is
+ * sum_v hist[i, v] * 2^-v.  A register above 63 (no hash of at most 64 bits produces one) is counted into *invalid (int64,
+ * set by the call) and into no bin. */
+MHX_API_EXT int mhx_hll_histogram_dev(mhx_ctx *ctx, const uint8_t *d_reg, int64_t n, int32_t p, uint32_t *d_hist,
+                                  int64_t *d_invalid);
+MHX_API_EXT int mhx_hll_histogram(mhx_ctx *ctx, const uint8_t *reg, int64_t n, int32_t p, uint32_t *hist, int64_t *invalid);
+/* HyperLogLog.merge of whole matrices (ref :170-183): d_a[i] = max(d_a[i], d_b[i]) over count bytes, in place.  Any
+ * alignment and any count; 16 bytes per lane where both pointers are 16-byte aligned. */
+MHX_API_EXT int mhx_hll_merge_dev(mhx_ctx *ctx, uint8_t *d_a, const uint8_t *d_b, int64_t count);
+/* HyperLogLog.union per group (ref :254-268, np.maximum.reduce): out[g, :] = the register-wise max over the rows
+ * group_offsets[g] .. group_offsets[g + 1] of reg [n_rows, m] (int64 [n_groups + 1], non-decreasing, inside [0, n_rows] --
+ * checked by the host form, the caller's promise for the _dev form).  An empty group gives zeros. */
+MHX_API_EXT int mhx_hll_union_groups_dev(mhx_ctx *ctx, const uint8_t *d_reg, int64_t n_rows, int32_t p,
+                                     const int64_t *d_group_offsets, int64_t n_groups, uint8_t *d_out);
+MHX_API_EXT int mhx_hll_union_groups(mhx_ctx *ctx, const uint8_t *reg, int64_t n_rows, int32_t p, const int64_t *group_offsets,
+                                 int64_t n_groups, uint8_t *out);
 
 /* ---- Multi-GPU: assemble the signature matrix (RCCL over xGMI) ----------------------------- */
 /* 128-byte RCCL unique id, created on rank 0 and distributed by the caller (env, file, socket). */
