@@ -12,6 +12,7 @@ from datasketch_amd.hashfunc import prehashed, sha1_hash32, sha1_hash64, sha1_ha
 from datasketch_amd.hyperloglog import HyperLogLog
 from datasketch_amd.lean_minhash import LeanMinHash
 from datasketch_amd.lsh import MinHashLSH
+from datasketch_amd.lsh_bloom import BloomTable, MinHashLSHBloom
 from datasketch_amd.lshensemble import MinHashLSHEnsemble
 from datasketch_amd.lshforest import MinHashLSHForest
 from datasketch_amd.minhash import MinHash
@@ -24,6 +25,8 @@ __all__ = [
     "LeanMinHash",
     "MinHash",
     "MinHashLSH",
+    "MinHashLSHBloom",
+    "BloomTable",
     "MinHashLSHEnsemble",
     "MinHashLSHForest",
     "WeightedMinHash",

@@ -151,10 +151,20 @@ _PROTOTYPES_EXT = {
     "mhx_hll_union_groups_dev": [_vp, _vp, _i64, _i32, _vp, _i64, _vp],
     "mhx_hll_union_groups": [_vp, _vp, _i64, _i32, _vp, _i64, _vp],
 }
+# Entry points declared MHX_API_BLOOM (MinHashLSHBloom): a third list for the same reason; the three-way check of
+# declared = bound = exported is in tests/test_lsh_bloom_host.py, the argument checks in tests/test_gpu_lsh_bloom.py.
+_PROTOTYPES_BLOOM = {
+    "mhx_bloom_insert_dev": [_vp, _vp, _int, _i64, _i32, _i32, _i32, _i32, _i64, _vp],
+    "mhx_bloom_query_dev": [_vp, _vp, _int, _i64, _i32, _i32, _i32, _i32, _i64, _vp, _vp, _int],
+    "mhx_bloom_insert": [_vp, _vp, _int, _i64, _i32, _i32, _i32, _i32, _i64, _vp],
+    "mhx_bloom_query": [_vp, _vp, _int, _i64, _i32, _i32, _i32, _i32, _i64, _vp, _vp, _int],
+    "mhx_bloom_union_dev": [_vp, _vp, _vp, _i32, _i64],
+}
 _RESTYPE = {"mhx_last_error": ctypes.c_char_p, "mhx_version": ctypes.c_char_p}
 
 EXPORTED_SYMBOLS = sorted(list(_PROTOTYPES) + list(_RESTYPE))
 EXPORTED_SYMBOLS_EXT = sorted(_PROTOTYPES_EXT)
+EXPORTED_SYMBOLS_BLOOM = sorted(_PROTOTYPES_BLOOM)
 
 
 try:  # CPython helper (csrc/pack_module.c): ~10 ns per token instead of ~180 in the interpreter
@@ -193,7 +203,7 @@ def load():
                 "Build it with `python -c 'import __graft_entry__ as g; g.build()'` or datasketch_amd/csrc/build.sh"
             )
             raise MhxError(_lib_error) from e
-        for name, argtypes in list(_PROTOTYPES.items()) + list(_PROTOTYPES_EXT.items()):
+        for name, argtypes in list(_PROTOTYPES.items()) + list(_PROTOTYPES_EXT.items()) + list(_PROTOTYPES_BLOOM.items()):
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = _int
@@ -1122,6 +1132,36 @@ class Context:
         out = np.empty((group_offsets.size - 1, m), dtype=np.uint8)
         check(self.lib.mhx_hll_union_groups(self.handle, _ptr(reg), n, m.bit_length() - 1, _ptr(group_offsets), group_offsets.size - 1, _ptr(out)))
         return out
+
+    # -- MinHashLSHBloom (mhx_bloom_*): the filter is a device array uint32 [bands, n_blocks, 16] the caller owns -------------
+    @staticmethod
+    def _bloom_sig(sig: np.ndarray):
+        sig = np.ascontiguousarray(sig)
+        if sig.dtype != np.uint32:
+            sig = np.ascontiguousarray(sig, dtype=np.uint64)
+        if sig.ndim != 2:
+            raise ValueError("signatures must be a 2-D array")
+        return sig, MHX_U32 if sig.dtype == np.uint32 else MHX_U64
+
+    def bloom_insert(self, sig: np.ndarray, d_filter: DeviceBuffer, bands: int, r: int, k: int, n_blocks: int) -> None:
+        """Host signatures [n, num_perm] (uint32 or uint64) into the device filter (mhx_bloom_insert)."""
+        sig, code = self._bloom_sig(sig)
+        check(self.lib.mhx_bloom_insert(self.handle, _ptr(sig), code, sig.shape[0], sig.shape[1], int(bands), int(r), int(k), int(n_blocks),
+                                        _vp(d_filter.ptr)))
+
+    def bloom_query(self, sig: np.ndarray, d_filter: DeviceBuffer, bands: int, r: int, k: int, n_blocks: int,
+                    then_insert: bool = False) -> np.ndarray:
+        """bool [n]: which rows collide with the filter in some band; ``then_insert`` inserts every row afterwards, the answers
+        referring to the filter before the call (mhx_bloom_query)."""
+        sig, code = self._bloom_sig(sig)
+        hit = np.zeros(sig.shape[0], dtype=np.uint8)
+        check(self.lib.mhx_bloom_query(self.handle, _ptr(sig), code, sig.shape[0], sig.shape[1], int(bands), int(r), int(k), int(n_blocks),
+                                       _vp(d_filter.ptr), _ptr(hit), 1 if then_insert else 0))
+        return hit.view(np.bool_)
+
+    def bloom_union(self, d_dst: DeviceBuffer, d_src: DeviceBuffer, bands: int, n_blocks: int) -> None:
+        """d_dst |= d_src over two device filters of equal geometry (mhx_bloom_union_dev; enqueued)."""
+        check(self.lib.mhx_bloom_union_dev(self.handle, _vp(d_dst.ptr), _vp(d_src.ptr), int(bands), int(n_blocks)))
 
     def close(self) -> None:
         if self.handle is None:

@@ -474,6 +474,7 @@ int mhx_ctx_set_option(mhx_ctx *ctx, const char *key, int64_t value) {
         {"lsh.bigbins", &mhx_ctx::opt_lsh_bigbins},         {"pack.fused", &mhx_ctx::opt_pack_fused},
         {"weighted.refill", &mhx_ctx::opt_weighted_refill}, {"lsh.prehash", &mhx_ctx::opt_lsh_prehash},
         {"lsh.merge_items", &mhx_ctx::opt_lsh_merge_items}, {"hll.split_tokens", &mhx_ctx::opt_hll_split_tokens},
+        {"bloom.lanes", &mhx_ctx::opt_bloom_lanes},
     };
     if (!ctx || !key) return fail(MHX_ERR_INVALID, "ctx/key is NULL");
     MHX_GUARD(ctx);
@@ -482,6 +483,7 @@ int mhx_ctx_set_option(mhx_ctx *ctx, const char *key, int64_t value) {
         if (o.field == &mhx_ctx::opt_lsh_merge_items)
             MHX_REQUIRE(value == 0 || value == 8 || value == 16, "lsh.merge_items must be 0, 8 or 16");
         if (o.field == &mhx_ctx::opt_hll_split_tokens) MHX_REQUIRE(value >= 0, "hll.split_tokens must be >= 0");
+        if (o.field == &mhx_ctx::opt_bloom_lanes) MHX_REQUIRE(value == 0 || value == 1 || value == 16, "bloom.lanes must be 0, 1 or 16");
         ctx->*o.field = value;
         return MHX_OK;
     }
@@ -2192,6 +2194,79 @@ int mhx_hll_union_groups_dev(mhx_ctx *ctx, const uint8_t *d_reg, int64_t n_rows,
 int mhx_hll_union_groups(mhx_ctx *ctx, const uint8_t *reg, int64_t n_rows, int32_t p, const int64_t *group_offsets, int64_t n_groups,
                          uint8_t *out) {
     return hll_union_groups(ctx, reg, n_rows, p, group_offsets, n_groups, out, kHost);
+}
+
+// ---- MinHashLSHBloom: per-band Bloom filters (ref: datasketch/lsh_bloom.py) ----------------------------------------------
+static int check_bloom(int32_t bands, int64_t n_blocks) {
+    MHX_REQUIRE(bands > 0 && bands <= (1 << 24), "bands must be in [1, 2^24]");
+    MHX_REQUIRE(n_blocks >= 1 && n_blocks < ((int64_t)1 << 32), "n_blocks must be in [1, 2^32-1]");  // the block is chosen by a 32 x 32 bit product
+    return MHX_OK;
+}
+// a filter is whole 64-byte blocks; lines are read 16 bytes at a time
+#define MHX_CHECK_BLOOM_ALIGNED(ptr) MHX_REQUIRE(((uintptr_t)(ptr) & 63) == 0, #ptr " must be 64-byte aligned")
+
+// insert, query, or query then insert (hit != NULL: the answers refer to the filter before the call).  The filter is the caller's
+// device array whatever `where` says; `where` is about the signatures and the answers.
+static int bloom_apply(mhx_ctx *ctx, const void *sig, int sig_dtype, int64_t n, int32_t num_perm, int32_t bands, int32_t r, int32_t k,
+                       int64_t n_blocks, uint32_t *d_filter, uint8_t *hit, bool query, bool insert, Where where) {
+    MHX_ENTER(ctx, ctx);
+    MHX_REQUIRE(n >= 0, "n must be >= 0");
+    MHX_CHECK_DTYPE(sig_dtype);
+    MHX_CHECK_BANDS(bands, r, num_perm);
+    MHX_TRY(check_bloom(bands, n_blocks));
+    MHX_REQUIRE(k >= 1 && k <= 32, "k must be in [1, 32]");
+    MHX_REQUIRE(d_filter, "d_filter is NULL");
+    MHX_CHECK_BLOOM_ALIGNED(d_filter);
+    if (n == 0) return MHX_OK;
+    MHX_REQUIRE_POINTERS(sig && (hit || !query), where);
+    MHX_TRY(ctx->activate());
+    const uint32_t nb = (uint32_t)n_blocks;
+    if (where == kDevice) {
+        if (query) MHX_TRY(mhx::launch_bloom_query(ctx, sig, sig_dtype, n, num_perm, bands, r, k, nb, d_filter, hit));
+        if (insert) MHX_TRY(mhx::launch_bloom_insert(ctx, sig, sig_dtype, n, num_perm, bands, r, k, nb, d_filter));
+        return MHX_OK;
+    }
+    // the signatures go up once, whatever follows
+    Stage s(ctx);
+    const auto p_sig = s.piece(Stage::In, (sig_dtype == MHX_U32 ? 4 : 8) * (size_t)n * (size_t)num_perm);
+    Stage::Piece p_hit{Stage::Out, 0, 0};
+    if (query) p_hit = s.piece(Stage::Out, (size_t)n);
+    MHX_TRY(s.commit());
+    MHX_TRY(s.upload(p_sig, sig));
+    if (query) MHX_TRY(mhx::launch_bloom_query(ctx, s.at<void>(p_sig), sig_dtype, n, num_perm, bands, r, k, nb, d_filter, s.at<uint8_t>(p_hit)));
+    if (insert) MHX_TRY(mhx::launch_bloom_insert(ctx, s.at<void>(p_sig), sig_dtype, n, num_perm, bands, r, k, nb, d_filter));
+    if (query) return s.fetch(hit, p_hit);
+    return s.synchronize();
+}
+
+int mhx_bloom_insert_dev(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n, int32_t num_perm, int32_t bands, int32_t r, int32_t k,
+                         int64_t n_blocks, uint32_t *d_filter) {
+    return bloom_apply(ctx, d_sig, sig_dtype, n, num_perm, bands, r, k, n_blocks, d_filter, nullptr, false, true, kDevice);
+}
+
+int mhx_bloom_query_dev(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n, int32_t num_perm, int32_t bands, int32_t r, int32_t k,
+                        int64_t n_blocks, uint32_t *d_filter, uint8_t *d_hit, int then_insert) {
+    return bloom_apply(ctx, d_sig, sig_dtype, n, num_perm, bands, r, k, n_blocks, d_filter, d_hit, true, then_insert != 0, kDevice);
+}
+
+int mhx_bloom_insert(mhx_ctx *ctx, const void *sig, int sig_dtype, int64_t n, int32_t num_perm, int32_t bands, int32_t r, int32_t k,
+                     int64_t n_blocks, uint32_t *d_filter) {
+    return bloom_apply(ctx, sig, sig_dtype, n, num_perm, bands, r, k, n_blocks, d_filter, nullptr, false, true, kHost);
+}
+
+int mhx_bloom_query(mhx_ctx *ctx, const void *sig, int sig_dtype, int64_t n, int32_t num_perm, int32_t bands, int32_t r, int32_t k,
+                    int64_t n_blocks, uint32_t *d_filter, uint8_t *hit, int then_insert) {
+    return bloom_apply(ctx, sig, sig_dtype, n, num_perm, bands, r, k, n_blocks, d_filter, hit, true, then_insert != 0, kHost);
+}
+
+int mhx_bloom_union_dev(mhx_ctx *ctx, uint32_t *d_dst, const uint32_t *d_src, int32_t bands, int64_t n_blocks) {
+    MHX_ENTER(ctx, ctx);
+    MHX_TRY(check_bloom(bands, n_blocks));
+    MHX_REQUIRE_POINTERS(d_dst && d_src, kDevice);
+    MHX_CHECK_BLOOM_ALIGNED(d_dst);
+    MHX_CHECK_BLOOM_ALIGNED(d_src);
+    MHX_TRY(ctx->activate());
+    return mhx::launch_bloom_union(ctx, d_dst, d_src, (int64_t)bands * n_blocks * 16);
 }
 
 }  // extern "C"

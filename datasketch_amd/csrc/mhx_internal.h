@@ -100,6 +100,7 @@ struct mhx_ctx {
     int64_t opt_pack_fused = 0;     // mhx_bbit_pack_band_digests_dev: 0 auto (one read of the matrix where the shape allows), 1 = always the two kernels
     int64_t opt_weighted_refill = 0; // one-wave-per-row walk, 4096-column rows: 0 auto (non-temporal row loads; values in: also the refill right after staging, chunk after chunk), 1 = round 4 (plain loads, refill behind the walk), 2 / 3 = force non-temporal / + early refill
     int64_t opt_hll_split_tokens = 0; // mhx_hll_bulk*: a set with more tokens than this is split over workgroups; 0 auto (mhx::kHllSplitTokens)
+    int64_t opt_bloom_lanes = 0;      // mhx_bloom_*: lanes per (row, band): 0 auto (insert 16: one lane per word of the block; query 1), 1 or 16 = both operations that way
     int64_t opt_host_chunk_bytes = 0;  // mhx_minhash_bulk: bytes per pipelined piece; 0 auto (96 MiB, inputs > 256 MiB), < 0 never pipeline
 
     // copy streams of the pipelined host entry point (created on first use)
@@ -240,6 +241,13 @@ int launch_hll_bulk(mhx_ctx *ctx, const void *d_hv, int hv_dtype, const int64_t 
 int launch_hll_histogram(mhx_ctx *ctx, const uint8_t *d_reg, int64_t n, int p, uint32_t *d_hist, int64_t *d_invalid);
 int launch_hll_merge(mhx_ctx *ctx, uint8_t *d_a, const uint8_t *d_b, int64_t count);
 int launch_hll_union_groups(mhx_ctx *ctx, const uint8_t *d_reg, int p, const int64_t *d_group_offsets, int64_t n_groups, uint8_t *d_out);
+
+// bloom_kernels.hip: the per-band Bloom filters of MinHashLSHBloom (mhx_bloom_*), uint32 [bands][n_blocks][16]; all enqueue only
+int launch_bloom_insert(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n, int32_t num_perm, int32_t bands, int32_t r, int32_t k,
+                        uint32_t n_blocks, uint32_t *d_filter);
+int launch_bloom_query(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n, int32_t num_perm, int32_t bands, int32_t r, int32_t k,
+                       uint32_t n_blocks, uint32_t *d_filter, uint8_t *d_hit);
+int launch_bloom_union(mhx_ctx *ctx, uint32_t *d_dst, const uint32_t *d_src, int64_t words);
 
 int bbit_slot_size(int b);
 

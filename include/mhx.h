@@ -110,7 +110,9 @@ MHX_API int mhx_ctx_device_info(mhx_ctx *ctx, char *name, int name_len, int *cus
  * overflows or n > 41M, 1 = radix sort always),
  * ("lsh.merge_items", mhx_lsh_bands_merge_dev: outputs per thread of a 256-thread merge tile, 0 auto = 8, or 8 / 16; results unaffected),
  * ("hll.split_tokens", mhx_hll_bulk*: a set with more tokens than this is split over several workgroups and combined by a max,
- * 0 auto = 32768; results unaffected). */
+ * 0 auto = 32768; results unaffected),
+ * ("bloom.lanes", mhx_bloom_*: lanes per (row, band), 0 auto = 16 for the insert (one lane per word of the block) and 1 for the query, the faster
+ * mapping of each; 1 / 16 = both operations that way; results unaffected). */
 MHX_API int mhx_ctx_set_option(mhx_ctx *ctx, const char *key, int64_t value);
 /* Kernel event counters since the last call (synchronises the stream, then resets them):
  *   out[0] sets the sieve launch left to the full launch (failed proof, or skipped by the back-off),
@@ -641,6 +643,36 @@ MHX_API_EXT int mhx_hll_union_groups_dev(mhx_ctx *ctx, const uint8_t *d_reg, int
                                      const int64_t *d_group_offsets, int64_t n_groups, uint8_t *d_out);
 MHX_API_EXT int mhx_hll_union_groups(mhx_ctx *ctx, const uint8_t *reg, int64_t n_rows, int32_t p, const int64_t *group_offsets,
                                  int64_t n_groups, uint8_t *out);
+
+/* ---- MinHashLSHBloom: per-band Bloom filters ---------------------------------------------------- */
+/* The index of the reference's MinHashLSHBloom (ref: datasketch/lsh_bloom.py) as one device array d_filter
+ * uint32 [bands][n_blocks][16], 64-byte aligned: every band owns a cache-line-blocked Bloom filter of n_blocks blocks of 512 bits
+ * (16 little-endian 32-bit words), and all the k bits of a key lie in one block.  For row i and band j of a signature matrix
+ * [n, num_perm] of sig_dtype (MHX_U32 / MHX_U64; columns from bands * r on are ignored):
+ *     s = the sum of the band's r values in uint64, wrapping mod 2^64;  x = s mod (2^61 - 1)          (ref :105, :117)
+ *     splitmix64 seeded with x: state = x; per draw state += 0x9E3779B97F4A7C15, z = state,
+ *         z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9, z = (z ^ z >> 27) * 0x94D049BB133111EB, out = z ^ z >> 31
+ *     block = ((out_0 >> 32) * n_blocks) >> 32                       (hence n_blocks in [1, 2^32 - 1])
+ *     pos_i = (out_{1 + i / 7} >> 9 * (i % 7)) & 511 for i < k (k in [1, 32]); word pos >> 5, bit pos & 31; positions may repeat
+ * The bit layout is this library's own: the reference leaves it to pybloomfilter, whose files are not read.
+ * The entry points are exported through MHX_API_BLOOM (the same visibility as MHX_API), bound from _native._PROTOTYPES_BLOOM and
+ * their argument checks are tested beside the feature, in tests/test_gpu_lsh_bloom.py. */
+#define MHX_API_BLOOM __attribute__((visibility("default")))
+/* d_filter |= the masks of every (row, band).  A word whose bits are all set already is read, not written.  Enqueued. */
+MHX_API_BLOOM int mhx_bloom_insert_dev(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n, int32_t num_perm, int32_t bands,
+                                       int32_t r, int32_t k, int64_t n_blocks, uint32_t *d_filter);
+/* d_hit uint8 [n]: 1 where some band's mask is wholly in that band's filter (MinHashLSHBloom.query, ref :363-372).  then_insert != 0:
+ * a second launch on the same stream inserts every row afterwards -- the answers refer to the filter before the call (rows of one
+ * call do not see each other): the streaming near-duplicate step.  Enqueued. */
+MHX_API_BLOOM int mhx_bloom_query_dev(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n, int32_t num_perm, int32_t bands,
+                                      int32_t r, int32_t k, int64_t n_blocks, uint32_t *d_filter, uint8_t *d_hit, int then_insert);
+/* The same with host signatures (uploaded once) and host answers; d_filter stays a device array.  Blocking. */
+MHX_API_BLOOM int mhx_bloom_insert(mhx_ctx *ctx, const void *sig, int sig_dtype, int64_t n, int32_t num_perm, int32_t bands, int32_t r,
+                                   int32_t k, int64_t n_blocks, uint32_t *d_filter);
+MHX_API_BLOOM int mhx_bloom_query(mhx_ctx *ctx, const void *sig, int sig_dtype, int64_t n, int32_t num_perm, int32_t bands, int32_t r,
+                                  int32_t k, int64_t n_blocks, uint32_t *d_filter, uint8_t *hit, int then_insert);
+/* d_dst |= d_src over the bands * n_blocks * 16 words of two filters of equal geometry (merging shards).  Enqueued. */
+MHX_API_BLOOM int mhx_bloom_union_dev(mhx_ctx *ctx, uint32_t *d_dst, const uint32_t *d_src, int32_t bands, int64_t n_blocks);
 
 /* ---- Multi-GPU: assemble the signature matrix (RCCL over xGMI) ----------------------------- */
 /* 128-byte RCCL unique id, created on rank 0 and distributed by the caller (env, file, socket). */
