@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("MHX_LIBRARY") or os.path.join(_HERE, "libmhx.so")  # 
 
 MHX_OK, MHX_ERR_NO_DEVICE, MHX_ERR_INVALID, MHX_ERR_HIP, MHX_ERR_OOM, MHX_ERR_UNSUPPORTED, MHX_ERR_COMM = range(7)
 MHX_U64, MHX_U32 = 0, 1
+MHX_TOPK_MAX = 64  # include/mhx.h: the longest list of the top-k Jaccard entries
 COMM_ID_BYTES = 128
 ROW_MAJOR, BAND_MAJOR = 0, 1  # layouts of a band-digest matrix on the device (include/mhx.h)
 
@@ -160,11 +161,20 @@ _PROTOTYPES_BLOOM = {
     "mhx_bloom_query": [_vp, _vp, _int, _i64, _i32, _i32, _i32, _i32, _i64, _vp, _vp, _int],
     "mhx_bloom_union_dev": [_vp, _vp, _vp, _i32, _i64],
 }
+# Entry points declared MHX_API_TOPK (exact top-k Jaccard neighbours): a fourth list for the same reason; declared = bound =
+# exported is checked in tests/test_nearest_neighbors_host.py, the argument checks in tests/test_gpu_jaccard_topk.py.
+_PROTOTYPES_TOPK = {
+    "mhx_jaccard_topk_dev": [_vp, _vp, _i64, _vp, _i64, _int, _i32, _vp, _i32, _i32, _vp, _vp],
+    "mhx_jaccard_topk": [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _vp],
+    "mhx_bbit_jaccard_topk_dev": [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _vp],
+    "mhx_bbit_jaccard_topk": [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp],
+}
 _RESTYPE = {"mhx_last_error": ctypes.c_char_p, "mhx_version": ctypes.c_char_p}
 
 EXPORTED_SYMBOLS = sorted(list(_PROTOTYPES) + list(_RESTYPE))
 EXPORTED_SYMBOLS_EXT = sorted(_PROTOTYPES_EXT)
 EXPORTED_SYMBOLS_BLOOM = sorted(_PROTOTYPES_BLOOM)
+EXPORTED_SYMBOLS_TOPK = sorted(_PROTOTYPES_TOPK)
 
 
 try:  # CPython helper (csrc/pack_module.c): ~10 ns per token instead of ~180 in the interpreter
@@ -203,7 +213,7 @@ def load():
                 "Build it with `python -c 'import __graft_entry__ as g; g.build()'` or datasketch_amd/csrc/build.sh"
             )
             raise MhxError(_lib_error) from e
-        for name, argtypes in list(_PROTOTYPES.items()) + list(_PROTOTYPES_EXT.items()) + list(_PROTOTYPES_BLOOM.items()):
+        for name, argtypes in list(_PROTOTYPES.items()) + list(_PROTOTYPES_EXT.items()) + list(_PROTOTYPES_BLOOM.items()) + list(_PROTOTYPES_TOPK.items()):
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = _int
@@ -943,6 +953,36 @@ class Context:
         return self._threshold_retry(lambda p, c, cap, found: self.lib.mhx_bbit_jaccard_threshold_pairs(
             self.handle, _ptr(a), a.shape[0], _ptr(b), n_b, int(num_perm), int(bits), int(min_count), p, c, cap, found),
             capacity if capacity is not None else max(a.shape[0], 1 << 12))
+
+    def jaccard_topk(self, a: np.ndarray, b: Optional[np.ndarray], k: int, min_count: int = 0):
+        """(rows int64 [n_a, k], counts int32 [n_a, k]): per row of A the k rows of B with the most equal positions, by
+        (count descending, row ascending), padded with -1 (mhx_jaccard_topk); b=None: A among itself, never a row itself."""
+        a, b = self._all_pairs_args(a, b, np.shape(a)[-1])
+        n_b = a.shape[0] if b is None else b.shape[0]
+        rows, counts = np.empty((a.shape[0], int(k)), dtype=np.int64), np.empty((a.shape[0], int(k)), dtype=np.int32)
+        check(self.lib.mhx_jaccard_topk(self.handle, _ptr(a), a.shape[0], _ptr(b), n_b, a.shape[1], int(min_count), int(k), _ptr(rows),
+                                        _ptr(counts)))
+        return rows, counts
+
+    def bbit_jaccard_topk(self, a: np.ndarray, b: Optional[np.ndarray], num_perm: int, bits: int, k: int, min_count: int = 0):
+        """(rows, counts) as :meth:`jaccard_topk`, by agreeing b-bit positions of packed rows (mhx_bbit_jaccard_topk)."""
+        a, b = self._all_pairs_args(a, b, self._bbit_width(num_perm, bits))
+        n_b = a.shape[0] if b is None else b.shape[0]
+        rows, counts = np.empty((a.shape[0], int(k)), dtype=np.int64), np.empty((a.shape[0], int(k)), dtype=np.int32)
+        check(self.lib.mhx_bbit_jaccard_topk(self.handle, _ptr(a), a.shape[0], _ptr(b), n_b, int(num_perm), int(bits), int(min_count),
+                                             int(k), _ptr(rows), _ptr(counts)))
+        return rows, counts
+
+    def jaccard_topk_dev(self, d_a: int, n_a: int, d_b: Optional[int], n_b: int, sig_dtype: int, num_perm: int,
+                         d_b_live_bits: Optional[int], min_count: int, k: int, d_rows: int, d_counts: int) -> None:
+        """mhx_jaccard_topk_dev: rows int64 [n_a, k] / counts int32 [n_a, k] on the device; enqueued."""
+        check(self.lib.mhx_jaccard_topk_dev(self.handle, _vp(d_a), int(n_a), _vp(d_b), int(n_b), int(sig_dtype), int(num_perm),
+                                            _vp(d_b_live_bits), int(min_count), int(k), _vp(d_rows), _vp(d_counts)))
+
+    def bbit_jaccard_topk_dev(self, d_a: int, n_a: int, d_b: Optional[int], n_b: int, num_perm: int, bits: int,
+                              d_b_live_bits: Optional[int], min_count: int, k: int, d_rows: int, d_counts: int) -> None:
+        check(self.lib.mhx_bbit_jaccard_topk_dev(self.handle, _vp(d_a), int(n_a), _vp(d_b), int(n_b), int(num_perm), int(bits),
+                                                 _vp(d_b_live_bits), int(min_count), int(k), _vp(d_rows), _vp(d_counts)))
 
     def jaccard_matrix_dev(self, d_a: int, n_a: int, d_b: Optional[int], n_b: int, sig_dtype: int, num_perm: int, d_counts: int,
                            ldc: int) -> None:

@@ -281,3 +281,25 @@ def similar_pairs(blocks_a, blocks_b, num_perm: int, b: int, threshold: float = 
     else:
         pairs, counts = _pairs_from_blocks(_agree_blocks(a, bb, slot, num_perm), c, bb is None)
     return pairs, _estimate(counts, num_perm, c1, denom)
+
+
+def nearest_neighbors(blocks_a, blocks_b, num_perm: int, b: int, k: int = 10, threshold=None, r: float = 0.0, r_b=None,
+                      gpu_mode: str = "always"):
+    """The ``k`` packed rows of ``blocks_b`` nearest to every packed row of ``blocks_a``: ``(rows int64 [M, k], estimates
+    float64 [M, k])``, ranked by agreeing b-bit positions (descending, ties by the smaller row) and reported as the
+    ``bBitMinHash.jaccard`` estimate of that count, as :func:`similar_pairs` does; padding ``-1`` / ``nan``.
+    ``blocks_b=None``: the rows of ``blocks_a`` among themselves, never a row itself.  ``threshold``: only rows whose estimate
+    is ``>= threshold``.  Exact -- every pair is compared, the ``M x N`` matrix is never formed.  ``1 <= k <= 64``."""
+    from datasketch_amd.lsh_bulk import _check_topk, _min_count, _topk_from_blocks
+
+    a, bb, b, num_perm, slot, c1, denom = _all_pairs_setup(blocks_a, blocks_b, num_perm, b, r, r_b)
+    k = _check_topk(k)
+    n_b = a.shape[0] if bb is None else bb.shape[0]
+    c = 0 if threshold is None else _min_count(_estimate(np.arange(num_perm + 1), num_perm, c1, denom), float(threshold))
+    if a.shape[0] == 0 or n_b == 0 or c > num_perm:
+        rows = counts = np.full((a.shape[0], k), -1, dtype=np.int64)
+    elif _use_device(gpu_mode):
+        rows, counts = _native.context().bbit_jaccard_topk(a, bb, num_perm, b, k, c)
+    else:
+        rows, counts = _topk_from_blocks(_agree_blocks(a, bb, slot, num_perm), a.shape[0], k, c, bb is None)
+    return rows, np.where(rows >= 0, _estimate(counts, num_perm, c1, denom), np.nan)

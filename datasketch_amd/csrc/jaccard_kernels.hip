@@ -19,32 +19,12 @@
 // tiles to recompute them, while a threshold query's output is small next to its n^2 work.
 #include <rocprim/device/device_radix_sort.hpp>
 
-#include "mhx_internal.h"
+#include "jaccard_tile.h"
 
 namespace mhx {
 namespace {
 
-constexpr int kTile = 128;         // rows of A and of B per workgroup tile
-constexpr int kChunk = 16;         // 32-bit words per row and LDS stage
-constexpr int kLdsRow = kTile + 4; // [word][row] stride in words: 16-byte aligned, successive words 4 banks apart
-constexpr int kThreads = 256;
-constexpr int kStage = kChunk * kTile / kThreads;  // words of A (and of B) one thread stages per chunk
-
-// Kind of row: dense uint32 (SLOT 0, !WIDE), dense uint64 (SLOT 0, WIDE), b-bit packed blocks (SLOT = slot width).
-template <int SLOT>
-__device__ __forceinline__ uint32_t slot_low_bits() {
-    return SLOT == 1 ? 0xFFFFFFFFu : SLOT == 2 ? 0x55555555u : SLOT == 4 ? 0x11111111u : SLOT == 8 ? 0x01010101u
-         : SLOT == 16 ? 0x00010001u : 0x00000001u;
-}
-
-// number of slots of width SLOT that differ between x and y (the slots never straddle a 32-bit word)
-template <int SLOT>
-__device__ __forceinline__ uint32_t differing_slots(uint32_t x, uint32_t y) {
-    uint32_t z = x ^ y;
-#pragma unroll
-    for (int sh = 1; sh < SLOT; sh <<= 1) z |= z >> sh;
-    return (uint32_t)__builtin_popcount(z & slot_low_bits<SLOT>());
-}
+using namespace jtile;  // the tile geometry, shared with the top-k strip kernel
 
 struct TileSpace {
     int64_t tiles_m, tiles_n;
@@ -103,102 +83,7 @@ __global__ __launch_bounds__(kThreads, 2) void jaccard_tile_kernel(const uint32_
         space.locate(t, ti, tj);
         const int64_t i0 = ti * kTile, j0 = tj * kTile;
 
-        // staging: thread tid moves word (tid & 15) of the chunk for rows (tid >> 4) + 16 e of the A and the B tile
-        const int srow = tid >> 4, sw = tid & 15;
-        uint32_t ok_a = 0, ok_b = 0;  // bit e: row srow + 16 e exists
-#pragma unroll
-        for (int e = 0; e < kStage; ++e) {
-            ok_a |= (i0 + srow + 16 * e < n_a ? 1u : 0u) << e;
-            ok_b |= (j0 + srow + 16 * e < n_b ? 1u : 0u) << e;
-        }
-        const int64_t step = 16 * (int64_t)W;  // elements between the rows a thread stages
-        uint32_t ra[kStage], rb[kStage], rah[WIDE ? kStage : 1], rbh[WIDE ? kStage : 1];
-        auto fetch = [&](int c) {
-            const int w = c * kChunk + sw;
-            const uint32_t va = w < W ? ok_a : 0u, vb = w < W ? ok_b : 0u;
-            if (WIDE) {
-                const uint64_t *pa = reinterpret_cast<const uint64_t *>(a) + (i0 + srow) * W + w;
-                const uint64_t *pb = reinterpret_cast<const uint64_t *>(b) + (j0 + srow) * W + w;
-#pragma unroll
-                for (int e = 0; e < kStage; ++e) {
-                    const uint64_t x = (va >> e) & 1u ? pa[e * step] : 0ull;
-                    const uint64_t y = (vb >> e) & 1u ? pb[e * step] : (uint64_t)pad_b;
-                    ra[e] = (uint32_t)x;
-                    rah[e] = (uint32_t)(x >> 32);
-                    rb[e] = (uint32_t)y;
-                    rbh[e] = (uint32_t)(y >> 32);
-                }
-            } else {
-                const uint32_t *pa = a + (i0 + srow) * W + w;
-                const uint32_t *pb = b + (j0 + srow) * W + w;
-#pragma unroll
-                for (int e = 0; e < kStage; ++e) {
-                    ra[e] = (va >> e) & 1u ? pa[e * step] : 0u;
-                    rb[e] = (vb >> e) & 1u ? pb[e * step] : pad_b;
-                }
-            }
-        };
-
-        uint32_t acc[8][8];
-#pragma unroll
-        for (int r = 0; r < 8; ++r)
-#pragma unroll
-            for (int c = 0; c < 8; ++c) acc[r][c] = 0;
-
-        fetch(0);
-        for (int c = 0; c < chunks; ++c) {
-            __syncthreads();  // the previous chunk's reads are done
-            int high = 0;
-#pragma unroll
-            for (int e = 0; e < kStage; ++e) {
-                As[sw][srow + 16 * e] = ra[e];
-                Bs[sw][srow + 16 * e] = rb[e];
-                if (WIDE) {
-                    Ah[sw][srow + 16 * e] = rah[e];
-                    Bh[sw][srow + 16 * e] = rbh[e];
-                    high |= (rah[e] | rbh[e]) != 0;
-                }
-            }
-            if (WIDE) high = __syncthreads_or(high);
-            else __syncthreads();
-            if (c + 1 < chunks) fetch(c + 1);  // in flight while this chunk is counted
-            const int kn = min(kChunk, W - c * kChunk);  // words of this chunk (b = 1, K = 128 rows are 4 words)
-
-            if (!WIDE || !high) {  // (uint64 chunks whose high words are all zero take the 32-bit comparison)
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-                for (int kk = 0; kk < kn; ++kk) {
-                    uint32_t x[8], y[8];
-                    *reinterpret_cast<uint4 *>(&x[0]) = *reinterpret_cast<const uint4 *>(&As[kk][ty * 4]);
-                    *reinterpret_cast<uint4 *>(&x[4]) = *reinterpret_cast<const uint4 *>(&As[kk][64 + ty * 4]);
-                    *reinterpret_cast<uint4 *>(&y[0]) = *reinterpret_cast<const uint4 *>(&Bs[kk][tx * 4]);
-                    *reinterpret_cast<uint4 *>(&y[4]) = *reinterpret_cast<const uint4 *>(&Bs[kk][64 + tx * 4]);
-#pragma unroll
-                    for (int r = 0; r < 8; ++r)
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) {
-                            if (SLOT == 0) acc[r][q] += x[r] == y[q] ? 1u : 0u;
-                            else acc[r][q] += differing_slots<SLOT == 0 ? 1 : SLOT>(x[r], y[q]);
-                        }
-                }
-            } else {
-#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
-                for (int kk = 0; kk < kn; ++kk) {
-                    uint32_t x[8], y[8], xh[8], yh[8];
-                    *reinterpret_cast<uint4 *>(&x[0]) = *reinterpret_cast<const uint4 *>(&As[kk][ty * 4]);
-                    *reinterpret_cast<uint4 *>(&x[4]) = *reinterpret_cast<const uint4 *>(&As[kk][64 + ty * 4]);
-                    *reinterpret_cast<uint4 *>(&y[0]) = *reinterpret_cast<const uint4 *>(&Bs[kk][tx * 4]);
-                    *reinterpret_cast<uint4 *>(&y[4]) = *reinterpret_cast<const uint4 *>(&Bs[kk][64 + tx * 4]);
-                    *reinterpret_cast<uint4 *>(&xh[0]) = *reinterpret_cast<const uint4 *>(&Ah[kk][ty * 4]);
-                    *reinterpret_cast<uint4 *>(&xh[4]) = *reinterpret_cast<const uint4 *>(&Ah[kk][64 + ty * 4]);
-                    *reinterpret_cast<uint4 *>(&yh[0]) = *reinterpret_cast<const uint4 *>(&Bh[kk][tx * 4]);
-                    *reinterpret_cast<uint4 *>(&yh[4]) = *reinterpret_cast<const uint4 *>(&Bh[kk][64 + tx * 4]);
-#pragma unroll
-                    for (int r = 0; r < 8; ++r)
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) acc[r][q] += ((x[r] ^ y[q]) | (xh[r] ^ yh[q])) == 0 ? 1u : 0u;
-                }
-            }
-        }
+#include "jaccard_tile_count.inc"
 
         // sub-tile element (r, q) is pair (i0 + rowof(r), j0 + rowof(q))
         auto rowof = [](int t4, int r) { return (r < 4 ? 0 : 64) + t4 * 4 + (r & 3); };
@@ -278,20 +163,6 @@ __global__ __launch_bounds__(256) void unpack_threshold_pairs_kernel(const uint6
         pairs[2 * p + 1] = (int64_t)(key & 0xFFFFFFFFull);
         counts[p] = vals[p];
     }
-}
-
-// words per row and kernel selection shared by the two launchers.  b < 0: dense rows of sig_dtype; else b-bit blocks.
-struct Shape {
-    int slot;   // 0 dense
-    bool wide;  // dense uint64
-    int32_t W;
-};
-
-Shape shape_of(int sig_dtype, int32_t k, int32_t b) {
-    if (b < 0) return Shape{0, sig_dtype == MHX_U64, k};
-    const int slot = bbit_slot_size(b);
-    const int per = 64 / slot;
-    return Shape{slot, false, 2 * ((k + per - 1) / per)};
 }
 
 template <bool EMIT>

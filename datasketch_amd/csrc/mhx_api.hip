@@ -474,7 +474,8 @@ int mhx_ctx_set_option(mhx_ctx *ctx, const char *key, int64_t value) {
         {"lsh.bigbins", &mhx_ctx::opt_lsh_bigbins},         {"pack.fused", &mhx_ctx::opt_pack_fused},
         {"weighted.refill", &mhx_ctx::opt_weighted_refill}, {"lsh.prehash", &mhx_ctx::opt_lsh_prehash},
         {"lsh.merge_items", &mhx_ctx::opt_lsh_merge_items}, {"hll.split_tokens", &mhx_ctx::opt_hll_split_tokens},
-        {"bloom.lanes", &mhx_ctx::opt_bloom_lanes},
+        {"bloom.lanes", &mhx_ctx::opt_bloom_lanes},         {"jaccard.topk_path", &mhx_ctx::opt_jaccard_topk_path},
+        {"jaccard.topk_segments", &mhx_ctx::opt_jaccard_topk_segments},
     };
     if (!ctx || !key) return fail(MHX_ERR_INVALID, "ctx/key is NULL");
     MHX_GUARD(ctx);
@@ -484,6 +485,8 @@ int mhx_ctx_set_option(mhx_ctx *ctx, const char *key, int64_t value) {
             MHX_REQUIRE(value == 0 || value == 8 || value == 16, "lsh.merge_items must be 0, 8 or 16");
         if (o.field == &mhx_ctx::opt_hll_split_tokens) MHX_REQUIRE(value >= 0, "hll.split_tokens must be >= 0");
         if (o.field == &mhx_ctx::opt_bloom_lanes) MHX_REQUIRE(value == 0 || value == 1 || value == 16, "bloom.lanes must be 0, 1 or 16");
+        if (o.field == &mhx_ctx::opt_jaccard_topk_path) MHX_REQUIRE(value >= 0 && value <= 2, "jaccard.topk_path must be 0, 1 or 2");
+        if (o.field == &mhx_ctx::opt_jaccard_topk_segments) MHX_REQUIRE(value >= 0, "jaccard.topk_segments must be >= 0");
         ctx->*o.field = value;
         return MHX_OK;
     }
@@ -1877,6 +1880,48 @@ static int all_pairs_threshold(mhx_ctx *ctx, const void *a, int64_t n_a, const v
     return s.synchronize();
 }
 
+// The k best rows of B per row of A.  Host form: A staged once (In), B streams through Aux in row blocks whose lists the merge
+// kernel folds into the running ones (Offsets), the unpacked lists come back through Out
+static int all_pairs_topk(mhx_ctx *ctx, const void *a, int64_t n_a, const void *b, int64_t n_b, int sig_dtype, int32_t k, int32_t bb,
+                          const uint32_t *live_bits, int32_t min_count, int32_t topk, int64_t *rows, int32_t *counts, Where where) {
+    MHX_ENTER(ctx, ctx);
+    MHX_TRY(check_all_pairs(n_a, n_b, sig_dtype, k, bb));
+    MHX_REQUIRE(topk >= 1 && topk <= MHX_TOPK_MAX, "k must be in [1, %d]", MHX_TOPK_MAX);
+    const bool self = b == nullptr;
+    if (self) n_b = n_a;
+    if (n_a == 0) return MHX_OK;
+    MHX_REQUIRE_POINTERS(a && rows && counts, where);
+    MHX_TRY(ctx->activate());
+    if (where == kDevice)
+        return mhx::launch_jaccard_topk(ctx, a, n_a, self ? a : b, n_b, sig_dtype, k, bb, live_bits, min_count, topk, self, nullptr, 0, nullptr,
+                                        rows, counts);
+    const size_t row_bytes = sizeof(uint64_t) * (size_t)(bb < 0 ? k : num_blocks(k, bb));
+    const size_t list_bytes = (size_t)n_a * (size_t)topk;
+    const size_t block_bytes = ctx->opt_host_chunk_bytes > 0 ? (size_t)ctx->opt_host_chunk_bytes : (size_t)256 << 20;
+    const int64_t block = self ? n_b : std::max<int64_t>(1, std::min<int64_t>(n_b, (int64_t)(block_bytes / row_bytes)));
+    Stage s(ctx);
+    const auto p_a = s.piece(Stage::In, row_bytes * (size_t)n_a);
+    const auto p_b = self ? Stage::Piece{} : s.piece(Stage::Aux, row_bytes * (size_t)block);
+    const auto p_keys = s.piece(Stage::Offsets, sizeof(uint64_t) * list_bytes);
+    const auto p_rows = s.piece(Stage::Out, sizeof(int64_t) * list_bytes);
+    const auto p_counts = s.piece(Stage::Out, sizeof(int32_t) * list_bytes);
+    MHX_TRY(s.commit());
+    MHX_TRY(s.upload(p_a, a));
+    int64_t j0 = 0;
+    do {  // (once, with nothing to compare, when B is empty: the padding)
+        const int64_t m = std::min<int64_t>(block, n_b - j0);
+        const bool first = j0 == 0, last = j0 + m >= n_b;
+        if (!self) MHX_TRY(s.upload(p_b, (const char *)b + (size_t)j0 * row_bytes, row_bytes * (size_t)m));  // (stream order: behind the previous block's kernels)
+        MHX_TRY(mhx::launch_jaccard_topk(ctx, s.at<void>(p_a), n_a, self ? s.at<void>(p_a) : s.at<void>(p_b), m, sig_dtype, k, bb, nullptr,
+                                         min_count, topk, self, first ? nullptr : s.at<uint64_t>(p_keys), (uint32_t)j0,
+                                         s.at<uint64_t>(p_keys), last ? s.at<int64_t>(p_rows) : nullptr,
+                                         last ? s.at<int32_t>(p_counts) : nullptr));
+        j0 += m;
+    } while (j0 < n_b);
+    MHX_TRY(s.download(rows, p_rows));
+    return s.fetch(counts, p_counts);
+}
+
 int mhx_jaccard_matrix_dev(mhx_ctx *ctx, const void *d_a, int64_t n_a, const void *d_b, int64_t n_b, int sig_dtype, int32_t num_perm,
                            int32_t *d_counts, int64_t ldc) {
     return all_pairs_matrix(ctx, d_a, n_a, d_b, n_b, sig_dtype, num_perm, -1, d_counts, ldc, kDevice);
@@ -1921,6 +1966,28 @@ int mhx_bbit_jaccard_threshold_pairs(mhx_ctx *ctx, const uint64_t *a, int64_t n_
     if (n_pairs) *n_pairs = 0;
     MHX_CHECK_B(b);
     return all_pairs_threshold(ctx, a, n_a, b_blocks, n_b, MHX_U64, num_perm, b, min_count, pairs, counts, capacity, n_pairs, kHost);
+}
+
+int mhx_jaccard_topk_dev(mhx_ctx *ctx, const void *d_a, int64_t n_a, const void *d_b, int64_t n_b, int sig_dtype, int32_t num_perm,
+                         const uint32_t *d_b_live_bits, int32_t min_count, int32_t k, int64_t *d_rows, int32_t *d_counts) {
+    return all_pairs_topk(ctx, d_a, n_a, d_b, n_b, sig_dtype, num_perm, -1, d_b_live_bits, min_count, k, d_rows, d_counts, kDevice);
+}
+
+int mhx_jaccard_topk(mhx_ctx *ctx, const uint64_t *a, int64_t n_a, const uint64_t *b, int64_t n_b, int32_t num_perm, int32_t min_count,
+                     int32_t k, int64_t *rows, int32_t *counts) {
+    return all_pairs_topk(ctx, a, n_a, b, n_b, MHX_U64, num_perm, -1, nullptr, min_count, k, rows, counts, kHost);
+}
+
+int mhx_bbit_jaccard_topk_dev(mhx_ctx *ctx, const uint64_t *d_a, int64_t n_a, const uint64_t *d_b, int64_t n_b, int32_t num_perm, int32_t b,
+                              const uint32_t *d_b_live_bits, int32_t min_count, int32_t k, int64_t *d_rows, int32_t *d_counts) {
+    MHX_CHECK_B(b);
+    return all_pairs_topk(ctx, d_a, n_a, d_b, n_b, MHX_U64, num_perm, b, d_b_live_bits, min_count, k, d_rows, d_counts, kDevice);
+}
+
+int mhx_bbit_jaccard_topk(mhx_ctx *ctx, const uint64_t *a, int64_t n_a, const uint64_t *b_blocks, int64_t n_b, int32_t num_perm, int32_t b,
+                          int32_t min_count, int32_t k, int64_t *rows, int32_t *counts) {
+    MHX_CHECK_B(b);
+    return all_pairs_topk(ctx, a, n_a, b_blocks, n_b, MHX_U64, num_perm, b, nullptr, min_count, k, rows, counts, kHost);
 }
 
 int mhx_lsh_bands_merge_dev(mhx_ctx *ctx, const uint64_t *d_dig_a, const uint32_t *d_rows_a, int64_t n_a, const uint64_t *d_dig_b,

@@ -101,7 +101,9 @@ struct mhx_ctx {
     int64_t opt_weighted_refill = 0; // one-wave-per-row walk, 4096-column rows: 0 auto (non-temporal row loads; values in: also the refill right after staging, chunk after chunk), 1 = round 4 (plain loads, refill behind the walk), 2 / 3 = force non-temporal / + early refill
     int64_t opt_hll_split_tokens = 0; // mhx_hll_bulk*: a set with more tokens than this is split over workgroups; 0 auto (mhx::kHllSplitTokens)
     int64_t opt_bloom_lanes = 0;      // mhx_bloom_*: lanes per (row, band): 0 auto (insert 16: one lane per word of the block; query 1), 1 or 16 = both operations that way
-    int64_t opt_host_chunk_bytes = 0;  // mhx_minhash_bulk: bytes per pipelined piece; 0 auto (96 MiB, inputs > 256 MiB), < 0 never pipeline
+    int64_t opt_jaccard_topk_path = 0;     // mhx_*jaccard_topk*: 0 auto (dense rows and few probes: the stream kernel), 1 strip kernel, 2 stream kernel wherever it exists (dense rows; b-bit rows always take the strip kernel) (A/B, tests)
+    int64_t opt_jaccard_topk_segments = 0; // mhx_*jaccard_topk*: segments B is cut into: 0 auto (enough to fill the machine), n >= 1 = n, clamped to the number of 128-row tiles of B (tests)
+    int64_t opt_host_chunk_bytes = 0;  // mhx_minhash_bulk: bytes per pipelined piece; 0 auto (96 MiB, inputs > 256 MiB), < 0 never pipeline; mhx_*jaccard_topk (host forms): > 0 = bytes of B per row block, else 256 MiB
 
     // copy streams of the pipelined host entry point (created on first use)
     hipStream_t copy_in = nullptr;
@@ -214,6 +216,15 @@ int launch_jaccard_matrix(mhx_ctx *ctx, const void *d_a, int64_t n_a, const void
 int launch_jaccard_threshold(mhx_ctx *ctx, const void *d_a, int64_t n_a, const void *d_b, int64_t n_b, int sig_dtype, int32_t k,
                              int32_t b, int32_t min_count, int64_t *d_pairs, int32_t *d_counts, int64_t capacity,
                              int64_t *n_pairs);
+
+// jaccard_topk_kernels.hip: per row of A the topk best rows of B by (count descending, row ascending), as packed keys
+// (count << 32 | 0xFFFFFFFF - row; 0 = no entry).  self: B is A and row i is no candidate of itself.  d_live: live-bit map of B
+// or nullptr.  The lists of this call (rows numbered from row_offset) are merged with d_have [n_a][topk] (or nullptr); the result
+// goes to d_keys_out as keys and / or to d_rows, d_counts unpacked (padding -1); any of them may be nullptr, d_keys_out may
+// be d_have.  n_a > 0; n_b == 0 or min_count > num_perm launch the merge alone.  Partial lists live in scratch[4].  Enqueues only.
+int launch_jaccard_topk(mhx_ctx *ctx, const void *d_a, int64_t n_a, const void *d_b, int64_t n_b, int sig_dtype, int32_t num_perm,
+                        int32_t b, const uint32_t *d_live, int32_t min_count, int32_t topk, bool self, const uint64_t *d_have,
+                        uint32_t row_offset, uint64_t *d_keys_out, int64_t *d_rows, int32_t *d_counts);
 
 // lsh_index_kernels.hip: the update path of a live index held as sorted bands (mhx_lsh_bands_merge_dev, mhx_lsh_bands_compact_dev,
 // mhx_rows_compact_dev).  The compactions are blocking: they read their totals back.

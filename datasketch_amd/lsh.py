@@ -500,6 +500,56 @@ class MinHashLSH:
             return [[] for _ in range(m)]
         return self._answers(mat, m)
 
+    def nearest_bulk(self, signatures, k: int, threshold: Optional[float] = None) -> List[list]:
+        """Per row of an ``[M, K]`` matrix of probes the ``k`` keys nearest by ``MinHash.jaccard``: a list of up to ``k``
+        ``(key, jaccard)``, best first, ties by the earlier insertion; keys as :meth:`query` returns them.  Exact -- every live
+        row of the index is compared, no banding in front.  ``threshold``: only keys whose Jaccard is ``>= threshold``.  A key
+        inserted more than once is reported once, with its nearest row: the scan asks for ``k`` + (live rows - live keys)
+        rows, which must not exceed 64.  Pending inserts are flushed first; removed rows are masked, not compacted."""
+        mat, words = lsh_bulk._words_matrix(signatures)
+        if words != 1 or self._words == 2:
+            raise ValueError("nearest neighbours are defined for MinHash signatures, not WeightedMinHash ones")
+        m, kw = mat.shape
+        if kw != self.h:
+            raise ValueError("Expecting minhash with length %d, got %d" % (self.h, kw))
+        k = lsh_bulk._check_topk(k)
+        self._sync()
+        n = self._n_flushed
+        if self._backend is None or n == 0 or m == 0:
+            return [[] for _ in range(m)]
+        kids = self._slot_kid[:n]
+        live = kids >= 0
+        want = k + int(np.count_nonzero(live)) - len(self._kid)
+        if want > _native.MHX_TOPK_MAX:
+            raise ValueError("k plus the rows of keys inserted more than once is %d: it must not exceed %d" % (want, _native.MHX_TOPK_MAX))
+        backend = self._backend
+        if lsh_bulk.needs_widening(backend.dtype, mat):
+            backend.widen()  # a probe value no uint32 row can hold: compare on the full width
+        rows, counts = lsh_bulk.rows_nearest(backend, np.ascontiguousarray(mat, dtype=backend.dtype), want, threshold,
+                                             None if self._n_dead == 0 else live)
+        out = []
+        for row, count in zip(rows.tolist(), counts.tolist()):
+            seen, best = set(), []
+            for slot, c in zip(row, count):
+                if slot < 0 or len(best) == k:
+                    break
+                kid = int(kids[slot])
+                if kid not in seen:
+                    seen.add(kid)
+                    key = self._kid_key[kid]
+                    best.append((pickle.loads(key) if self.prepickle else key, c / float(self.h)))
+            out.append(best)
+        return out
+
+    def nearest(self, minhash, k: int, threshold: Optional[float] = None) -> list:
+        """``[(key, jaccard)]`` of the up to ``k`` keys nearest to ``minhash``, best first (:meth:`nearest_bulk` of one probe)."""
+        if len(minhash) != self.h:
+            raise ValueError("Expecting minhash with length %d, got %d" % (self.h, len(minhash)))
+        hv = np.asarray(minhash.hashvalues)
+        if hv.ndim != 1:
+            raise ValueError("nearest neighbours are defined for MinHash signatures, not WeightedMinHash ones")
+        return self.nearest_bulk(hv.reshape(1, -1), k, threshold)[0]
+
     def add_to_query_buffer(self, minhash) -> None:
         if len(minhash) != self.h:
             raise ValueError("Expecting minhash with length %d, got %d" % (self.h, len(minhash)))

@@ -21,7 +21,9 @@ Python round trips:
 * :func:`jaccard_pairs` -- ``MinHash.jaccard`` for a list of pairs (ref: datasketch/minhash.py:299-324);
 * :func:`jaccard_matrix` / :func:`similar_pairs` -- ``MinHash.jaccard`` of every row of A against every row of B
   (or of A against itself), as a dense matrix or as the pairs at or above a threshold: exhaustive near-duplicate
-  search with no LSH banding in front, so no pair is missed by design.
+  search with no LSH banding in front, so no pair is missed by design;
+* :func:`nearest_neighbors` -- per row of A the ``k`` rows of B with the largest ``MinHash.jaccard``, by an exact scan
+  that never forms the matrix (:meth:`SortedBandsIndex.nearest`, ``MinHashLSH.nearest_bulk``: the same against an index).
 
 Every helper except :func:`jaccard_pairs` also takes a WeightedMinHash matrix ``[N, S, 2]`` int64
 (``WeightedMinHashGenerator.minhash_many_arrays``): its band keys are the reference's too
@@ -35,7 +37,7 @@ from typing import Hashable, Iterable, List, Optional, Sequence
 import numpy as np
 
 from datasketch_amd import _native
-from datasketch_amd._index_rows import DeviceRows
+from datasketch_amd._index_rows import DeviceRows, HostRows
 
 _FNV_OFFSET = np.uint64(0xCBF29CE484222325)
 _FNV_PRIME = np.uint64(0x100000001B3)
@@ -443,6 +445,17 @@ class SortedBandsIndex:
         return self.ctx.lsh_query_dev(self._d_dig.ptr, self._d_rows.ptr, self.n, self.b, self.r, self._rows.d_sig.ptr, self._rows.code,
                                       self.k, q, capacity)
 
+    def nearest(self, signatures, k: int, threshold: Optional[float] = None):
+        """``(rows int64 [M, k], jaccard float64 [M, k])``: the ``k`` indexed rows nearest to every probe by ``MinHash.jaccard``,
+        as :func:`nearest_neighbors` -- an exact scan of the resident matrix, only the probes are uploaded."""
+        q = np.asarray(signatures)
+        if q.ndim != 2 or q.shape[1] != self.k:
+            raise ValueError("Expecting minhash with length %d, got %d" % (self.k, q.shape[-1]))
+        q = self._as_index_dtype(q)
+        k = _check_topk(k)
+        rows, counts = rows_nearest(self._rows, q, k, threshold)
+        return rows, _jaccard_of(rows, counts, self.k)
+
 
 def sorted_bands(signatures, b: int, r: int, gpu_mode: str = "detect"):
     """``(digests [b, N] uint64 ascending per band, rows [b, N] uint32 in the same order)``: every LSH
@@ -621,3 +634,93 @@ def similar_pairs(a, b=None, threshold: float = 0.5, gpu_mode: str = "detect"):
     else:
         pairs, counts = _pairs_from_blocks(_equal_counts_blocks(sa, sb), c, sb is None)
     return pairs, counts.astype(np.float64) / float(k)
+
+
+def _check_topk(k) -> int:
+    k = int(k)
+    if k < 1 or k > _native.MHX_TOPK_MAX:
+        raise ValueError("k must be in [1, %d]" % _native.MHX_TOPK_MAX)
+    return k
+
+
+def _topk_from_blocks(blocks, n_a: int, k: int, min_count: int, self_join: bool, live: Optional[np.ndarray] = None):
+    """numpy top-k of all-pairs counts, block of A rows by block: ``(rows int64 [n_a, k], counts int64 [n_a, k])``, the best
+    ``k`` columns of every row by (count descending, column ascending) -- the sort of the keys ``count << 32 | 0xFFFFFFFF - j``
+    the device kernels keep -- padded with -1.  ``live``: bool per column, dead columns are no candidates."""
+    rows = np.full((n_a, k), -1, dtype=np.int64)
+    counts = np.full((n_a, k), -1, dtype=np.int64)
+    low = np.uint64(0xFFFFFFFF)
+    for i0, c in blocks:
+        m, n_b = c.shape
+        key = (c.astype(np.uint64) << np.uint64(32)) | (low - np.arange(n_b, dtype=np.uint64))[None, :]
+        ok = c >= min_count
+        if live is not None:
+            ok &= live[None, :]
+        if self_join:
+            ok[np.arange(m), i0 + np.arange(m)] = False
+        key[~ok] = 0
+        kk = min(k, n_b)
+        if kk < n_b:
+            key = np.partition(key, n_b - kk, axis=1)[:, n_b - kk :]
+        top = np.sort(key, axis=1)[:, ::-1]
+        have = top != 0
+        rows[i0 : i0 + m, :kk] = np.where(have, (low - (top & low)).astype(np.int64), -1)
+        counts[i0 : i0 + m, :kk] = np.where(have, (top >> np.uint64(32)).astype(np.int64), -1)
+    return rows, counts
+
+
+def _jaccard_of(rows: np.ndarray, counts: np.ndarray, k: int) -> np.ndarray:
+    return np.where(rows >= 0, counts.astype(np.float64) / float(k), np.nan)
+
+
+def _topk_matrix(sa: np.ndarray, sb: Optional[np.ndarray], k: int, threshold, use_gpu: bool, live: Optional[np.ndarray] = None):
+    """(rows, counts) of the best ``k`` rows of ``sb`` (``None``: ``sa`` itself, never a row itself) per row of ``sa``."""
+    num_perm = sa.shape[1]
+    n_b = sa.shape[0] if sb is None else sb.shape[0]
+    c = 0 if threshold is None else _min_count(np.arange(num_perm + 1, dtype=np.float64) / float(max(num_perm, 1)), float(threshold))
+    if sa.shape[0] == 0 or n_b == 0 or num_perm == 0 or c > num_perm:
+        return np.full((sa.shape[0], k), -1, dtype=np.int64), np.full((sa.shape[0], k), -1, dtype=np.int64)
+    if use_gpu and live is None:
+        return _native.context().jaccard_topk(sa, sb, k, c)
+    return _topk_from_blocks(_equal_counts_blocks(sa, sb), sa.shape[0], k, c, sb is None, live)
+
+
+def nearest_neighbors(a, b=None, k: int = 10, threshold: Optional[float] = None, gpu_mode: str = "detect"):
+    """The ``k`` nearest rows of ``b`` for every row of ``a`` by ``MinHash.jaccard`` (ref: datasketch/minhash.py:299-324):
+    ``(rows int64 [M, k], jaccard float64 [M, k])``, best first, ties by the smaller row; a row with fewer than ``k``
+    candidates is padded with ``-1`` / ``nan``.  Exact: every pair is compared (on the device without forming the ``M x N``
+    matrix), which is this package's answer to the reference's HNSW use case.  ``b=None``: the rows of ``a`` among themselves,
+    a row is never its own neighbour.  ``threshold``: only rows whose Jaccard is ``>= threshold`` (as :func:`similar_pairs`
+    takes it).  Inputs as :func:`jaccard_matrix`; ``1 <= k <= 64``."""
+    sa, sb = _all_pairs_inputs(a, b)
+    k = _check_topk(k)
+    rows, counts = _topk_matrix(sa, sb, k, threshold, _use_gpu(gpu_mode))
+    return rows, _jaccard_of(rows, counts, sa.shape[1])
+
+
+def live_bits(live: np.ndarray) -> np.ndarray:
+    """The live-bit map the device entry points take: bit ``row & 31`` of uint32 word ``row >> 5``, ``ceil(n / 32)`` words."""
+    words = np.zeros((live.size + 31) // 32 * 4, dtype=np.uint8)
+    packed = np.packbits(live, bitorder="little")
+    words[: packed.size] = packed
+    return words.view(np.uint32)
+
+
+def rows_nearest(store, probes: np.ndarray, k: int, threshold, live: Optional[np.ndarray] = None):
+    """(rows, counts) of the ``k`` best rows of an index's signature matrix (``DeviceRows`` / ``HostRows``) per probe (of the
+    store's dtype); ``live``: bool per row, dead rows are no candidates."""
+    m, num_perm, n = probes.shape[0], store.kw, store.n
+    c = 0 if threshold is None else _min_count(np.arange(num_perm + 1, dtype=np.float64) / float(num_perm), float(threshold))
+    if isinstance(store, HostRows):
+        if m == 0 or n == 0 or c > num_perm:
+            return np.full((m, k), -1, dtype=np.int64), np.full((m, k), -1, dtype=np.int64)
+        return _topk_from_blocks(_equal_counts_blocks(probes, store.sig), m, k, c, False, live)
+    if m == 0:
+        return np.empty((0, k), dtype=np.int64), np.empty((0, k), dtype=np.int64)
+    ctx = store.ctx
+    d_q = ctx.to_device(probes)
+    d_bits = None if live is None or n == 0 else ctx.to_device(live_bits(live))
+    d_rows, d_counts = ctx.alloc(8 * m * k), ctx.alloc(4 * m * k)
+    ctx.jaccard_topk_dev(d_q.ptr, m, store.d_sig.ptr if n else d_q.ptr, n, store.code, num_perm, None if d_bits is None else d_bits.ptr,
+                         c, k, d_rows.ptr, d_counts.ptr)
+    return d_rows.download((m, k), np.int64), d_counts.download((m, k), np.int32).astype(np.int64)

@@ -484,6 +484,26 @@ MHX_API int mhx_jaccard_threshold_pairs_dev(mhx_ctx *ctx, const void *d_a, int64
 MHX_API int mhx_jaccard_threshold_pairs(mhx_ctx *ctx, const uint64_t *a, int64_t n_a, const uint64_t *b, int64_t n_b,
                                         int32_t num_perm, int32_t min_count, int64_t *pairs, int32_t *counts, int64_t capacity,
                                         int64_t *n_pairs);
+/* Top-k form: for every row i of A the k rows j of B with the most agreeing positions, best first by (count descending, row
+ * ascending) -- a strict total order, so the answer is unique -- rows int64[n_a, k], counts int32[n_a, k]; a row with fewer
+ * than k candidates is padded with row = -1, count = -1.  The n_a x n_b matrix is never formed.  d_b == NULL: the rows of A
+ * among themselves (n_b is then n_a), j == i is no candidate.  d_b_live_bits (may be NULL): bit (row & 31) of word row >> 5
+ * set = row of B is a candidate, ceil(n_b / 32) words, as mhx_rows_compact_dev.  min_count > 0: rows with fewer agreeing
+ * positions are no candidates (min_count > num_perm: only the padding is written).  1 <= k <= MHX_TOPK_MAX, else
+ * MHX_ERR_INVALID.  n_a == 0 writes nothing, n_b == 0 only the padding.  Keeps the partial lists (8 bytes x n_a x k x the
+ * number of segments B is cut into, at most one per 128 rows of B) as scratch in the context until mhx_ctx_release_scratch.
+ * Enqueued on the ctx stream. */
+#define MHX_TOPK_MAX 64
+/* (exported through MHX_API_TOPK, the same visibility as MHX_API, and bound from _native._PROTOTYPES_TOPK: a list of their own, as
+ * MHX_API_EXT and MHX_API_BLOOM below, whose argument checks are tested beside the feature) */
+#define MHX_API_TOPK __attribute__((visibility("default")))
+MHX_API_TOPK int mhx_jaccard_topk_dev(mhx_ctx *ctx, const void *d_a, int64_t n_a, const void *d_b, int64_t n_b, int sig_dtype,
+                                 int32_t num_perm, const uint32_t *d_b_live_bits, int32_t min_count, int32_t k, int64_t *d_rows,
+                                 int32_t *d_counts);
+/* Host form (uint64 rows, b == NULL: A among itself): A is staged once, B streams through the device in row blocks whose
+ * lists are merged into the running ones, so B need not fit on the device beside A.  Blocking. */
+MHX_API_TOPK int mhx_jaccard_topk(mhx_ctx *ctx, const uint64_t *a, int64_t n_a, const uint64_t *b, int64_t n_b, int32_t num_perm,
+                             int32_t min_count, int32_t k, int64_t *rows, int32_t *counts);
 /* The b-bit twins on packed rows (mhx_bbit_pack*: [n, num_blocks] uint64, num_blocks as mhx_bbit_num_blocks): counts = the
  * positions of num_perm whose b-bit values agree, the `intersection` of bBitMinHash.jaccard (ref:
  * datasketch/b_bit_minhash.py:53-72), counted as num_perm minus the slots that differ (XOR, fold, popcount).  The estimate
@@ -498,6 +518,11 @@ MHX_API int mhx_bbit_jaccard_threshold_pairs_dev(mhx_ctx *ctx, const uint64_t *d
 MHX_API int mhx_bbit_jaccard_threshold_pairs(mhx_ctx *ctx, const uint64_t *a, int64_t n_a, const uint64_t *b_blocks, int64_t n_b,
                                              int32_t num_perm, int32_t b, int32_t min_count, int64_t *pairs, int32_t *counts,
                                              int64_t capacity, int64_t *n_pairs);
+MHX_API_TOPK int mhx_bbit_jaccard_topk_dev(mhx_ctx *ctx, const uint64_t *d_a, int64_t n_a, const uint64_t *d_b, int64_t n_b,
+                                      int32_t num_perm, int32_t b, const uint32_t *d_b_live_bits, int32_t min_count, int32_t k,
+                                      int64_t *d_rows, int32_t *d_counts);
+MHX_API_TOPK int mhx_bbit_jaccard_topk(mhx_ctx *ctx, const uint64_t *a, int64_t n_a, const uint64_t *b_blocks, int64_t n_b,
+                                  int32_t num_perm, int32_t b, int32_t min_count, int32_t k, int64_t *rows, int32_t *counts);
 
 /* ---- Live LSH index: the update path of sorted bands ------------------------------------- */
 /* The index of datasketch_amd.MinHashLSH (ref: datasketch/lsh.py:326-347 insert, :509-528 remove) is the layout of
