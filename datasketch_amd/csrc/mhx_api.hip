@@ -390,7 +390,7 @@ int mhx_ctx_create(int device, mhx_ctx **out) {
     MHX_HIP_CHECK(hipGetDeviceProperties(&prop, device));
     mhx_ctx *ctx = new mhx_ctx();
     ctx->device = device;
-    ctx->num_cus = prop.multiProcessorCount;
+    ctx->num_cus = ctx->hw_cus = prop.multiProcessorCount;
     ctx->lds_per_block = (int64_t)prop.sharedMemPerBlock;
     ctx->hbm_bytes = (int64_t)prop.totalGlobalMem;
     snprintf(ctx->name, sizeof(ctx->name), "%s (%s)", prop.name, prop.gcnArchName);
@@ -448,7 +448,7 @@ int mhx_ctx_device_info(mhx_ctx *ctx, char *name, int name_len, int *cus, int64_
         strncpy(name, ctx->name, (size_t)name_len - 1);
         name[name_len - 1] = 0;
     }
-    if (cus) *cus = ctx->num_cus;
+    if (cus) *cus = ctx->hw_cus;
     if (hbm_bytes) *hbm_bytes = ctx->hbm_bytes;
     return MHX_OK;
 }
@@ -475,7 +475,7 @@ int mhx_ctx_set_option(mhx_ctx *ctx, const char *key, int64_t value) {
         {"weighted.refill", &mhx_ctx::opt_weighted_refill}, {"lsh.prehash", &mhx_ctx::opt_lsh_prehash},
         {"lsh.merge_items", &mhx_ctx::opt_lsh_merge_items}, {"hll.split_tokens", &mhx_ctx::opt_hll_split_tokens},
         {"bloom.lanes", &mhx_ctx::opt_bloom_lanes},         {"jaccard.topk_path", &mhx_ctx::opt_jaccard_topk_path},
-        {"jaccard.topk_segments", &mhx_ctx::opt_jaccard_topk_segments},
+        {"jaccard.topk_segments", &mhx_ctx::opt_jaccard_topk_segments}, {"debug.cus", &mhx_ctx::opt_debug_cus},
     };
     if (!ctx || !key) return fail(MHX_ERR_INVALID, "ctx/key is NULL");
     MHX_GUARD(ctx);
@@ -487,7 +487,11 @@ int mhx_ctx_set_option(mhx_ctx *ctx, const char *key, int64_t value) {
         if (o.field == &mhx_ctx::opt_bloom_lanes) MHX_REQUIRE(value == 0 || value == 1 || value == 16, "bloom.lanes must be 0, 1 or 16");
         if (o.field == &mhx_ctx::opt_jaccard_topk_path) MHX_REQUIRE(value >= 0 && value <= 2, "jaccard.topk_path must be 0, 1 or 2");
         if (o.field == &mhx_ctx::opt_jaccard_topk_segments) MHX_REQUIRE(value >= 0, "jaccard.topk_segments must be >= 0");
+        if (o.field == &mhx_ctx::opt_debug_cus)
+            MHX_REQUIRE(value >= 0 && value <= ctx->hw_cus, "debug.cus must be 0 (the device's %d CUs) or in [1, %d], got %lld", ctx->hw_cus, ctx->hw_cus,
+                        (long long)value);
         ctx->*o.field = value;
+        if (o.field == &mhx_ctx::opt_debug_cus) ctx->num_cus = value ? (int)value : ctx->hw_cus;
         return MHX_OK;
     }
     return fail(MHX_ERR_INVALID, "unknown option '%s'", key);

@@ -61,7 +61,8 @@ struct mhx_ctx {
     std::recursive_mutex mu;
     int device = 0;
     hipStream_t stream = nullptr;
-    int num_cus = 0;
+    int num_cus = 0;     // what every launcher sizes its grid, chunks and segments from: hw_cus, or option "debug.cus"
+    int hw_cus = 0;      // the device's own count (mhx_ctx_device_info)
     int64_t lds_per_block = 64 << 10;  // what a workgroup may ask for (160 KB on gfx950)
     int64_t hbm_bytes = 0;
     char name[128] = {0};
@@ -77,6 +78,7 @@ struct mhx_ctx {
     int64_t opt_minhash_ties = 0;   // 0 auto (the second launch tries the tie-tolerant sieve before the dedup pass), 1 dedup pass only
     int64_t opt_minhash_split = 0;  // 0 auto, 1 force wave-per-set, 2 force split-sets (atomic combine)
     int64_t opt_blocks_per_cu = 0;  // 0 auto
+    int64_t opt_debug_cus = 0;      // tests only: 0 = the device's own CU count, 1 .. hw_cus = launchers see that many (num_cus follows)
     int64_t opt_minhash_prefetch = 1; // warm L2 with the next set's tokens (vector load per set): 1 auto (CSR, or fixed length < 256), 0 never, 2 always
     int64_t opt_minhash_alias = -1; // profiling only: >= 0 makes set i read the tokens of set (i & mask)
     int64_t opt_weighted_path = 0;  // 0 auto (dense rows: bound-ordered walk; CSR: reciprocal-multiply quotient + row blocks), 1 IEEE division for every element, 2 every element evaluated (dense rows compacted to CSR: the round-2 path)

@@ -76,6 +76,9 @@ MHX_API int mhx_ctx_device_info(mhx_ctx *ctx, char *name, int name_len, int *cus
  * 1 wave per set, 2 split sets over waves), ("minhash.packed", 0 auto: several sets per wave when
  * num_perm <= 96, 1 = always one set per wave, 2 = several sets per wave up to num_perm 128), ("minhash.ties", 0 auto: the second launch tries the
  * tie-tolerant sieve before the dedup pass, 1 = dedup pass only), ("blocks_per_cu", n), ("minhash.prefetch", 0/1/2: never / auto / always),
+ * ("debug.cus", tests only: 0 = the device's own compute-unit count, 1 .. that count = every launcher sizes its grid, chunks and segments as if
+ * the device had so many (a grid can only shrink, so that small shapes reach the later trips of the grid-stride loops); any other value is
+ * MHX_ERR_INVALID; results unaffected, mhx_ctx_device_info keeps reporting the device's count),
  * ("minhash.alias", profiling only: >= 0 makes set i read the tokens of set i & mask),
  * ("minhash.p3", 0 auto: three permutations per lane where that walks the fewest slots -- num_perm 129..192, 257..384, 513..576 --, 1 = never three), ("minhash.share", 0 auto: with three or four
  * permutations per lane, lane groups share a last slot that holds at most 32 permutations -- num_perm 129..160, 193..224 --, 1 = off),

@@ -211,6 +211,8 @@ case("mhx_ctx_set_option", dict(key=b"lsh.sort "), "unknown option 'lsh.sort '")
 case("mhx_ctx_set_option", dict(key=b""), "unknown option ''")
 for v in (1, -8, 12, 32):
     case("mhx_ctx_set_option", dict(key=b"lsh.merge_items", value=v), "lsh.merge_items must be 0, 8 or 16")
+case("mhx_ctx_set_option", dict(key=b"debug.cus", value=-1), re.compile(r"debug\.cus must be 0 \(the device's \d+ CUs\) or in \[1, \d+\], got -1"))
+case("mhx_ctx_set_option", dict(key=b"debug.cus", value=0), None)
 case("mhx_ctx_minhash_flags", dict(n_sets=-1), "NULL flags")
 case("mhx_ctx_minhash_flags", dict(flags=None), "NULL flags")
 for a in (3, 24, -6, 8192, -8192):
@@ -564,7 +566,9 @@ OPTIONS = {
     "blocks_per_cu": 0, "minhash.alias": -1, "minhash.prefetch": 1, "weighted.path": 0, "weighted.direct": 0, "weighted.split": 0,
     "weighted.tail": 0, "weighted.debug": 0, "weighted.kernel": 0, "weighted.plan": 0, "weighted.rescue": 0, "weighted.min_dim": 0,
     "host.chunk_bytes": 0, "lsh.sort_bits": 0, "lsh.gather": 0, "lsh.sort": 0, "lsh.levels": 0, "lsh.chunk": 0, "lsh.team": 0, "lsh.bigbins": 0,
-    "pack.fused": 0, "weighted.refill": 0, "lsh.prehash": 0, "lsh.merge_items": 0,
+    "pack.fused": 0, "weighted.refill": 0, "lsh.prehash": 0, "lsh.merge_items": 0, "hll.split_tokens": 0, "bloom.lanes": 0,
+    "jaccard.topk_path": 0, "jaccard.topk_segments": 0,
+    "debug.cus": 0,  # tests only: 0 = the device's own CU count, 1 .. that count = what every launcher sizes its grid from
 }
 
 
@@ -657,3 +661,30 @@ def test_every_option_key_is_known(env):
     assert env.lib.mhx_ctx_set_option(env.ctx.handle, b"lsh.merge_items", 16) == OK
     assert env.lib.mhx_ctx_set_option(env.ctx.handle, b"lsh.merge_items", 8) == OK
     assert env.lib.mhx_ctx_set_option(env.ctx.handle, b"lsh.merge_items", 0) == OK
+
+
+def test_debug_cus_takes_zero_to_the_device_count_and_device_info_keeps_the_hardware_count(env):
+    """debug.cus: 0 and every value up to the device's CU count are accepted, -1 and the count + 1 are MHX_ERR_INVALID with a
+    message that names the key (the option cannot be read back through the C ABI, so what a refused call leaves in it is not
+    observable here: the calls after it only show that the context still computes); mhx_ctx_device_info reports the hardware whatever the option holds.
+    On a context of its own, so that nothing here reaches the context the other modules share."""
+    ctx = _native.Context(env.ctx.device)
+    try:
+        cus = ctx.info()["compute_units"]
+        assert cus == env.ctx.info()["compute_units"] and cus >= 1
+        for value in (1, 3 if cus >= 3 else 1, cus, 0):
+            assert ctx.lib.mhx_ctx_set_option(ctx.handle, b"debug.cus", value) == OK, value
+            assert ctx.info()["compute_units"] == cus, value
+        assert ctx.lib.mhx_ctx_set_option(ctx.handle, b"debug.cus", 1) == OK
+        for value in (-1, cus + 1, 1 << 40):
+            assert ctx.lib.mhx_ctx_set_option(ctx.handle, b"debug.cus", value) == INVALID, value
+            assert _native.last_error() == f"debug.cus must be 0 (the device's {cus} CUs) or in [1, {cus}], got {value}"
+            assert ctx.info()["compute_units"] == cus
+        # after the refused values the context still works, at whatever count it holds and at the device's own
+        x = np.arange(70_000, dtype=np.uint64)
+        y = x[::-1].copy()
+        one = ctx.minhash_merge(x, y)
+        assert ctx.lib.mhx_ctx_set_option(ctx.handle, b"debug.cus", 0) == OK
+        assert np.array_equal(one, np.minimum(x, y)) and np.array_equal(ctx.minhash_merge(x, y), one)
+    finally:
+        ctx.close()
