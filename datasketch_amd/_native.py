@@ -169,12 +169,22 @@ _PROTOTYPES_TOPK = {
     "mhx_bbit_jaccard_topk_dev": [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i32, _i32, _vp, _vp],
     "mhx_bbit_jaccard_topk": [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp],
 }
+# Entry points declared MHX_API_CC (connected components / near-duplicate clusters): a fifth list for the same reason; declared =
+# bound = exported is checked in tests/test_clusters_host.py, the argument checks in tests/test_gpu_clusters.py.
+_PROTOTYPES_CC = {
+    "mhx_cc_init_dev": [_vp, _vp, _i64],
+    "mhx_cc_link_pairs_dev": [_vp, _vp, _i64, _vp, _i64, _vp, _i32, _vp],
+    "mhx_cc_link_bands_dev": [_vp, _vp, _i64, _vp, _vp, _i64, _i32, _vp],
+    "mhx_cc_finish_dev": [_vp, _vp, _i64],
+    "mhx_cc_pairs": [_vp, _vp, _i64, _vp, _i32, _i64, _vp, ctypes.POINTER(_i64)],
+}
 _RESTYPE = {"mhx_last_error": ctypes.c_char_p, "mhx_version": ctypes.c_char_p}
 
 EXPORTED_SYMBOLS = sorted(list(_PROTOTYPES) + list(_RESTYPE))
 EXPORTED_SYMBOLS_EXT = sorted(_PROTOTYPES_EXT)
 EXPORTED_SYMBOLS_BLOOM = sorted(_PROTOTYPES_BLOOM)
 EXPORTED_SYMBOLS_TOPK = sorted(_PROTOTYPES_TOPK)
+EXPORTED_SYMBOLS_CC = sorted(_PROTOTYPES_CC)
 
 
 try:  # CPython helper (csrc/pack_module.c): ~10 ns per token instead of ~180 in the interpreter
@@ -213,7 +223,8 @@ def load():
                 "Build it with `python -c 'import __graft_entry__ as g; g.build()'` or datasketch_amd/csrc/build.sh"
             )
             raise MhxError(_lib_error) from e
-        for name, argtypes in list(_PROTOTYPES.items()) + list(_PROTOTYPES_EXT.items()) + list(_PROTOTYPES_BLOOM.items()) + list(_PROTOTYPES_TOPK.items()):
+        for name, argtypes in (list(_PROTOTYPES.items()) + list(_PROTOTYPES_EXT.items()) + list(_PROTOTYPES_BLOOM.items())
+                               + list(_PROTOTYPES_TOPK.items()) + list(_PROTOTYPES_CC.items())):
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = _int
@@ -1037,6 +1048,22 @@ class Context:
         check(self.lib.mhx_lsh_sort_bands_dev_typed(self.handle, _vp(d_sig), int(code), int(n), int(k), int(b), int(r), _vp(d_dig),
                                                     _vp(d_rows)))
 
+    def lsh_candidate_pairs_dev(self, d_dig: int, d_rows: int, n: int, b: int, capacity: Optional[int] = None):
+        """mhx_lsh_candidate_pairs_dev over resident sorted bands: (device buffer of int64 [found, 2] pairs i < j, ascending and
+        unique, found).  The pairs stay on the device; ``capacity`` is the first guess, a larger answer costs one more call."""
+        def call(cap, found):
+            d_pairs = self.alloc(max(cap, 1) * 16)
+            check(self.lib.mhx_lsh_candidate_pairs_dev(self.handle, _vp(d_dig), _vp(d_rows), int(n), int(b), _vp(d_pairs.ptr), cap, found,
+                                                       None))
+            return d_pairs
+
+        return self._capacity_retry(call, capacity if capacity is not None else max(4 * int(n), 1 << 16))
+
+    def jaccard_pairs_dev(self, d_sig_a: int, d_sig_b: int, code: int, k: int, d_pairs: int, n_pairs: int, d_counts: int) -> None:
+        """mhx_jaccard_pairs_dev_typed: int32 counts of equal positions of the listed rows of resident matrices; enqueued."""
+        check(self.lib.mhx_jaccard_pairs_dev_typed(self.handle, _vp(d_sig_a), _vp(d_sig_b), int(code), int(k), _vp(d_pairs), int(n_pairs),
+                                                   _vp(d_counts)))
+
     def lsh_query_dev(self, d_dig: int, d_rows: int, n: int, b: int, r: int, d_sig: int, code: int, k: int, probes: np.ndarray,
                       capacity: Optional[int] = None):
         """mhx_lsh_query_dev for a host matrix of probes (of the index's dtype) against resident sorted bands and their [n, k]
@@ -1202,6 +1229,44 @@ class Context:
     def bloom_union(self, d_dst: DeviceBuffer, d_src: DeviceBuffer, bands: int, n_blocks: int) -> None:
         """d_dst |= d_src over two device filters of equal geometry (mhx_bloom_union_dev; enqueued)."""
         check(self.lib.mhx_bloom_union_dev(self.handle, _vp(d_dst.ptr), _vp(d_src.ptr), int(bands), int(n_blocks)))
+
+    # -- connected components (mhx_cc_*): labels is a device array uint32 [n]; init, any number of link calls, finish ------------
+    def cc_init_dev(self, d_labels: Optional[int], n: int) -> None:
+        """mhx_cc_init_dev: labels[i] = i; enqueued."""
+        check(self.lib.mhx_cc_init_dev(self.handle, _vp(d_labels), int(n)))
+
+    def cc_link_pairs_dev(self, d_labels: Optional[int], n: int, d_pairs: Optional[int], n_pairs: int, d_counts: Optional[int] = None,
+                          min_count: int = 0, d_invalid: Optional[int] = None) -> None:
+        """mhx_cc_link_pairs_dev: unite the ends of every pair of int64 [n_pairs, 2] (with ``d_counts``: of those whose count is
+        ``>= min_count``); pairs outside ``[0, n)`` are skipped and added to the int64 at ``d_invalid``; enqueued."""
+        check(self.lib.mhx_cc_link_pairs_dev(self.handle, _vp(d_labels), int(n), _vp(d_pairs), int(n_pairs), _vp(d_counts), int(min_count),
+                                             _vp(d_invalid)))
+
+    def cc_link_bands_dev(self, d_labels: Optional[int], n: int, d_dig: Optional[int], d_rows: Optional[int], n_sigs: int, bands: int,
+                          d_invalid: Optional[int] = None) -> None:
+        """mhx_cc_link_bands_dev: unite every row of sorted bands u64[bands][n_sigs] / u32[bands][n_sigs] with its predecessor
+        where their digests are equal; enqueued."""
+        check(self.lib.mhx_cc_link_bands_dev(self.handle, _vp(d_labels), int(n), _vp(d_dig), _vp(d_rows), int(n_sigs), int(bands),
+                                             _vp(d_invalid)))
+
+    def cc_finish_dev(self, d_labels: Optional[int], n: int) -> None:
+        """mhx_cc_finish_dev: labels[i] = the smallest row of i's component; enqueued."""
+        check(self.lib.mhx_cc_finish_dev(self.handle, _vp(d_labels), int(n)))
+
+    def cc_pairs(self, pairs: np.ndarray, n: int, counts: Optional[np.ndarray] = None, min_count: int = 0):
+        """(labels uint32 [n], invalid): the smallest row of every row's connected component under the edges ``pairs`` int64
+        [M, 2] (with ``counts``: those whose count is ``>= min_count``), and how many edges had an end outside ``[0, n)`` and
+        were skipped (mhx_cc_pairs; host in, host out)."""
+        pairs = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+        if counts is not None:
+            counts = np.ascontiguousarray(counts, dtype=np.int32)
+            if counts.shape != (pairs.shape[0],):
+                raise ValueError("counts must have one entry per pair")
+        labels = np.empty(int(n), dtype=np.uint32)
+        invalid = _i64(0)
+        check(self.lib.mhx_cc_pairs(self.handle, _ptr(pairs) if pairs.shape[0] else None, pairs.shape[0], _ptr(counts), int(min_count), int(n),
+                                    _ptr(labels) if labels.size else None, ctypes.byref(invalid)))
+        return labels, int(invalid.value)
 
     def close(self) -> None:
         if self.handle is None:

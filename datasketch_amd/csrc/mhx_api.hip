@@ -2340,4 +2340,85 @@ int mhx_bloom_union_dev(mhx_ctx *ctx, uint32_t *d_dst, const uint32_t *d_src, in
     return mhx::launch_bloom_union(ctx, d_dst, d_src, (int64_t)bands * n_blocks * 16);
 }
 
+// ---- Near-duplicate clusters: connected components (cc_kernels.hip) -----------------------------------------------------------
+// rows are numbered in 32 bits and a label is a row number
+#define MHX_CHECK_CC_ROWS(n) MHX_REQUIRE((n) >= 0 && (n) < ((int64_t)1 << 32), "n must be in [0, 2^32-1]")
+
+// init (finish == false) or finish over labels[n]
+static int cc_sweep(mhx_ctx *ctx, uint32_t *d_labels, int64_t n, bool finish) {
+    MHX_ENTER(ctx, ctx);
+    MHX_CHECK_CC_ROWS(n);
+    if (n == 0) return MHX_OK;
+    MHX_REQUIRE_POINTERS(d_labels, kDevice);
+    MHX_TRY(ctx->activate());
+    return finish ? mhx::launch_cc_finish(ctx, d_labels, n) : mhx::launch_cc_init(ctx, d_labels, n);
+}
+
+static int cc_link_pairs(mhx_ctx *ctx, uint32_t *d_labels, int64_t n, const int64_t *d_pairs, int64_t n_pairs, const int32_t *d_counts,
+                         int32_t min_count, int64_t *d_invalid) {
+    MHX_ENTER(ctx, ctx);
+    MHX_CHECK_CC_ROWS(n);
+    MHX_REQUIRE(n_pairs >= 0, "n_pairs must be >= 0");
+    if (n_pairs == 0) return MHX_OK;
+    MHX_REQUIRE_POINTERS(d_pairs && (d_labels || n == 0), kDevice);
+    MHX_TRY(ctx->activate());
+    return mhx::launch_cc_link_pairs(ctx, d_labels, n, d_pairs, n_pairs, d_counts, min_count, d_invalid);
+}
+
+static int cc_link_bands(mhx_ctx *ctx, uint32_t *d_labels, int64_t n, const uint64_t *d_sorted_digests, const uint32_t *d_sorted_rows,
+                         int64_t n_sigs, int32_t bands, int64_t *d_invalid) {
+    MHX_ENTER(ctx, ctx);
+    MHX_CHECK_CC_ROWS(n);
+    MHX_REQUIRE(n_sigs >= 0 && bands >= 0, "n_sigs and bands must be >= 0");
+    MHX_REQUIRE(bands == 0 || n_sigs <= INT64_MAX / bands, "bands * n_sigs does not fit 63 bits");
+    if (n_sigs == 0 || bands == 0) return MHX_OK;
+    MHX_REQUIRE_POINTERS(d_sorted_digests && d_sorted_rows && (d_labels || n == 0), kDevice);
+    MHX_TRY(ctx->activate());
+    return mhx::launch_cc_link_bands(ctx, d_labels, n, d_sorted_digests, d_sorted_rows, n_sigs, bands, d_invalid);
+}
+
+int mhx_cc_init_dev(mhx_ctx *ctx, uint32_t *d_labels, int64_t n) { return cc_sweep(ctx, d_labels, n, false); }
+
+int mhx_cc_link_pairs_dev(mhx_ctx *ctx, uint32_t *d_labels, int64_t n, const int64_t *d_pairs, int64_t n_pairs, const int32_t *d_counts,
+                          int32_t min_count, int64_t *d_invalid) {
+    return cc_link_pairs(ctx, d_labels, n, d_pairs, n_pairs, d_counts, min_count, d_invalid);
+}
+
+int mhx_cc_link_bands_dev(mhx_ctx *ctx, uint32_t *d_labels, int64_t n, const uint64_t *d_sorted_digests, const uint32_t *d_sorted_rows,
+                          int64_t n_sigs, int32_t bands, int64_t *d_invalid) {
+    return cc_link_bands(ctx, d_labels, n, d_sorted_digests, d_sorted_rows, n_sigs, bands, d_invalid);
+}
+
+int mhx_cc_finish_dev(mhx_ctx *ctx, uint32_t *d_labels, int64_t n) { return cc_sweep(ctx, d_labels, n, true); }
+
+// the host form: pairs (In) and counts (Aux) up, the three cores on the staged arrays, labels | invalid (Out) back
+int mhx_cc_pairs(mhx_ctx *ctx, const int64_t *pairs, int64_t n_pairs, const int32_t *counts, int32_t min_count, int64_t n, uint32_t *labels,
+                 int64_t *invalid) {
+    MHX_ENTER(ctx, ctx);
+    MHX_CHECK_CC_ROWS(n);
+    MHX_REQUIRE(n_pairs >= 0, "n_pairs must be >= 0");
+    if (invalid) *invalid = 0;
+    if (n == 0 && n_pairs == 0) return MHX_OK;
+    MHX_REQUIRE_POINTERS((labels || n == 0) && (pairs || n_pairs == 0), kHost);
+    MHX_TRY(ctx->activate());
+    Stage s(ctx);
+    Stage::Piece p_pairs{Stage::In, 0, 0}, p_counts{Stage::Aux, 0, 0};
+    if (n_pairs) p_pairs = s.piece(Stage::In, sizeof(int64_t) * 2 * (size_t)n_pairs);
+    if (n_pairs && counts) p_counts = s.piece(Stage::Aux, sizeof(int32_t) * (size_t)n_pairs);
+    // (an empty labels piece keeps its place in front of the counter: nothing is launched over it)
+    const auto p_labels = s.piece(Stage::Out, sizeof(uint32_t) * (size_t)n), p_bad = s.piece(Stage::Out, sizeof(int64_t));
+    MHX_TRY(s.commit());
+    if (n_pairs) MHX_TRY(s.upload(p_pairs, pairs));
+    if (n_pairs && counts) MHX_TRY(s.upload(p_counts, counts));
+    MHX_HIP_CHECK(hipMemsetAsync(s.at<void>(p_bad), 0, sizeof(int64_t), ctx->stream));
+    uint32_t *d_labels = s.at<uint32_t>(p_labels);
+    MHX_TRY(cc_sweep(ctx, d_labels, n, false));
+    MHX_TRY(cc_link_pairs(ctx, d_labels, n, n_pairs ? s.at<int64_t>(p_pairs) : nullptr, n_pairs,
+                          n_pairs && counts ? s.at<int32_t>(p_counts) : nullptr, min_count, s.at<int64_t>(p_bad)));
+    MHX_TRY(cc_sweep(ctx, d_labels, n, true));
+    if (invalid) MHX_TRY(s.download(invalid, p_bad));
+    if (n) return s.fetch(labels, p_labels);
+    return s.synchronize();
+}
+
 }  // extern "C"

@@ -262,6 +262,15 @@ int launch_bloom_query(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int64_t n
                        uint32_t n_blocks, uint32_t *d_filter, uint8_t *d_hit);
 int launch_bloom_union(mhx_ctx *ctx, uint32_t *d_dst, const uint32_t *d_src, int64_t words);
 
+// cc_kernels.hip: connected components by a lock-free union-find over uint32 labels[n] (mhx_cc_*); all of them enqueue only and
+// launch nothing for an empty range.  d_counts / d_invalid may be nullptr.
+int launch_cc_init(mhx_ctx *ctx, uint32_t *d_labels, int64_t n);
+int launch_cc_link_pairs(mhx_ctx *ctx, uint32_t *d_labels, int64_t n, const int64_t *d_pairs, int64_t n_pairs, const int32_t *d_counts,
+                         int32_t min_count, int64_t *d_invalid);
+int launch_cc_link_bands(mhx_ctx *ctx, uint32_t *d_labels, int64_t n, const uint64_t *d_sorted_digests, const uint32_t *d_sorted_rows,
+                         int64_t n_sigs, int32_t bands, int64_t *d_invalid);
+int launch_cc_finish(mhx_ctx *ctx, uint32_t *d_labels, int64_t n);
+
 int bbit_slot_size(int b);
 
 // grid of a grid-stride launch of 256-thread workgroups over `items`

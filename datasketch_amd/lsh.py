@@ -107,6 +107,9 @@ class _HostBands(HostRows):
     def bands(self):
         return self.dig, self.rows
 
+    def clusters(self, threshold, extra) -> np.ndarray:
+        return lsh_bulk.bands_clusters_host(self.sig, self.dig, self.rows, threshold, extra)
+
 
 class _DeviceBands(DeviceRows):
     """The device back end: the ``[capacity, K]`` signature matrix and the sorted bands ``digests u64[b][n]`` / ``rows u32[b][n]``
@@ -176,6 +179,9 @@ class _DeviceBands(DeviceRows):
         if self.n == 0:
             return np.empty((self.b, 0), dtype=np.uint64), np.empty((self.b, 0), dtype=np.uint32)
         return self.d_dig.download((self.b, self.n), np.uint64), self.d_rows.download((self.b, self.n), np.uint32)
+
+    def clusters(self, threshold, extra) -> np.ndarray:
+        return lsh_bulk.rows_clusters(self, self.d_dig.ptr, self.d_rows.ptr, self.b, self.kw, threshold, extra)
 
 
 class MinHashLSH:
@@ -549,6 +555,35 @@ class MinHashLSH:
         if hv.ndim != 1:
             raise ValueError("nearest neighbours are defined for MinHash signatures, not WeightedMinHash ones")
         return self.nearest_bulk(hv.reshape(1, -1), k, threshold)[0]
+
+    def duplicate_clusters(self, threshold: Optional[float] = None, min_size: int = 2) -> List[list]:
+        """The near-duplicate clusters of the indexed keys: lists of keys (as :meth:`query` returns them) of at least
+        ``min_size`` keys each (``min_size=1`` includes the keys that are alone).  ``threshold=None``: keys are one cluster when
+        a chain of shared band keys joins them -- the connected components of what :meth:`query` reports for the keys
+        themselves.  With a ``threshold`` two rows that share a band key are joined only when their ``MinHash.jaccard`` estimate
+        is ``>= threshold`` (MinHash signatures only), as ``lsh_bulk.duplicate_clusters`` does.  A key inserted more than once
+        joins the clusters of all its rows.  Clusters come ordered by their first inserted key, the keys inside a cluster in
+        insertion order (by slot).  Calls :meth:`compact` first: removed keys are gone before anything is linked."""
+        if threshold is not None and self._words == 2:
+            raise ValueError("a threshold is defined for MinHash signatures, not WeightedMinHash ones")
+        min_size = int(min_size)
+        if min_size < 1:
+            raise ValueError("min_size must be at least 1")
+        self.compact()
+        n = self._n_flushed
+        if self._backend is None or n == 0:
+            return []
+        extra = [(int(self._kid_slot[kid]), s) for kid, slots in self._extra.items() for s in slots]
+        labels = self._backend.clusters(threshold, np.asarray(extra, dtype=np.int64).reshape(-1, 2))
+        kids = self._slot_kid[:n]
+        first = np.flatnonzero(self._kid_slot[kids] == np.arange(n))  # one slot per key: its first
+        order = first[np.argsort(labels[first], kind="stable")]       # by (cluster's smallest slot, slot)
+        sizes = np.unique(labels[order], return_counts=True)[1]
+        keys = list(map(self._kid_key.__getitem__, kids[order].tolist()))
+        if self.prepickle:
+            keys = list(map(pickle.loads, keys))
+        starts = lsh_bulk._starts(sizes).tolist()
+        return [keys[a:b] for a, b in zip(starts[:-1], starts[1:]) if b - a >= min_size]
 
     def add_to_query_buffer(self, minhash) -> None:
         if len(minhash) != self.h:

@@ -23,7 +23,10 @@ Python round trips:
   (or of A against itself), as a dense matrix or as the pairs at or above a threshold: exhaustive near-duplicate
   search with no LSH banding in front, so no pair is missed by design;
 * :func:`nearest_neighbors` -- per row of A the ``k`` rows of B with the largest ``MinHash.jaccard``, by an exact scan
-  that never forms the matrix (:meth:`SortedBandsIndex.nearest`, ``MinHashLSH.nearest_bulk``: the same against an index).
+  that never forms the matrix (:meth:`SortedBandsIndex.nearest`, ``MinHashLSH.nearest_bulk``: the same against an index);
+* :func:`connected_components` / :func:`duplicate_clusters` -- the step after the pairs: the near-duplicate clusters as
+  ``labels[i]`` = the smallest row of ``i``'s connected component, by a lock-free union-find on the device that reads listed
+  pairs or the sorted bands themselves (:meth:`SortedBandsIndex.clusters`, ``MinHashLSH.duplicate_clusters``).
 
 Every helper except :func:`jaccard_pairs` also takes a WeightedMinHash matrix ``[N, S, 2]`` int64
 (``WeightedMinHashGenerator.minhash_many_arrays``): its band keys are the reference's too
@@ -456,6 +459,11 @@ class SortedBandsIndex:
         rows, counts = rows_nearest(self._rows, q, k, threshold)
         return rows, _jaccard_of(rows, counts, self.k)
 
+    def clusters(self, threshold: Optional[float] = None) -> np.ndarray:
+        """``labels int64 [N]`` as :func:`duplicate_clusters` gives them, over the resident matrix and bands: nothing is
+        uploaded, only the labels come down."""
+        return rows_clusters(self._rows, self._d_dig.ptr, self._d_rows.ptr, self.b, self.k, threshold)
+
 
 def sorted_bands(signatures, b: int, r: int, gpu_mode: str = "detect"):
     """``(digests [b, N] uint64 ascending per band, rows [b, N] uint32 in the same order)``: every LSH
@@ -479,8 +487,12 @@ def candidate_pairs(signatures, b: int, r: int, gpu_mode: str = "detect") -> np.
     _check_params(sig.shape[1], b, r)
     if _use_gpu(gpu_mode) and sig.shape[0]:
         return _native.context().lsh_candidate_pairs(sig, b, r)[0]
-    dig, rows = sorted_bands(sig, b, r, gpu_mode=gpu_mode)
-    n = dig.shape[1]
+    return _pairs_of_bands(*sorted_bands(sig, b, r, gpu_mode=gpu_mode))
+
+
+def _pairs_of_bands(dig: np.ndarray, rows: np.ndarray) -> np.ndarray:
+    """The numpy form of mhx_lsh_candidate_pairs_dev: the unique pairs ``i < j`` of rows inside one run of equal digests."""
+    b, n = dig.shape
     found: List[np.ndarray] = []
     for j in range(b):
         s, order = dig[j], rows[j].astype(np.int64)
@@ -724,3 +736,141 @@ def rows_nearest(store, probes: np.ndarray, k: int, threshold, live: Optional[np
     ctx.jaccard_topk_dev(d_q.ptr, m, store.d_sig.ptr if n else d_q.ptr, n, store.code, num_perm, None if d_bits is None else d_bits.ptr,
                          c, k, d_rows.ptr, d_counts.ptr)
     return d_rows.download((m, k), np.int64), d_counts.download((m, k), np.int32).astype(np.int64)
+
+
+# ---- near-duplicate clusters: the connected components of a pair graph ------------------------------------------------------
+def _components_host(u: np.ndarray, v: np.ndarray, n: int) -> np.ndarray:
+    """int64 [n]: the smallest row of every row's component under the edges ``(u[i], v[i])`` (all inside ``[0, n)``)."""
+    if n == 0:
+        return np.empty(0, dtype=np.int64)
+    from scipy.sparse import coo_matrix
+    from scipy.sparse.csgraph import connected_components as graph_components
+
+    graph = coo_matrix((np.ones(u.size, dtype=np.bool_), (u, v)), shape=(n, n))
+    count, comp = graph_components(graph, directed=False)
+    smallest = np.full(count, n, dtype=np.int64)
+    np.minimum.at(smallest, comp, np.arange(n, dtype=np.int64))
+    return smallest[comp]
+
+
+def _run_edges(dig: np.ndarray, rows: np.ndarray):
+    """Every row of sorted bands with its predecessor where their digests are equal: what mhx_cc_link_bands_dev links."""
+    same = dig[:, 1:] == dig[:, :-1]
+    return rows[:, :-1][same].astype(np.int64), rows[:, 1:][same].astype(np.int64)
+
+
+def _check_rows(n) -> int:
+    n = int(n)
+    if n < 0 or n >> 32:
+        raise ValueError("n must be in [0, 2^32 - 1]")
+    return n
+
+
+def connected_components(pairs, n: int, keep=None, gpu_mode: str = "detect") -> np.ndarray:
+    """``labels int64 [n]``: ``labels[i]`` is the smallest row of the connected component of row ``i`` in the graph whose edges
+    are ``pairs`` (``[M, 2]``, any order; duplicates, ``i > j`` and ``i == j`` are fine) -- the near-duplicate clusters of the
+    pairs :func:`candidate_pairs`, :func:`similar_pairs` or a thresholded :func:`jaccard_pairs` report.  ``keep``: optional bool
+    mask ``[M]``, only those pairs are edges.  ``labels == np.arange(n)`` marks the one row to keep per cluster;
+    ``np.unique(labels, return_inverse=True)`` gives dense cluster ids.  An edge with an end outside ``[0, n)`` raises
+    ``ValueError``.  On the device: a lock-free union-find (mhx_cc_pairs); on the host scipy's ``connected_components``."""
+    _check_gpu_mode(gpu_mode)
+    n = _check_rows(n)
+    pairs = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+    if keep is not None:
+        keep = np.ascontiguousarray(keep, dtype=np.bool_)
+        if keep.shape != (pairs.shape[0],):
+            raise ValueError("keep must have one entry per pair")
+    if _use_gpu(gpu_mode):
+        labels, invalid = _native.context().cc_pairs(pairs, n, None if keep is None else keep.astype(np.int32), 1)
+        if invalid:
+            raise ValueError("%d pairs have an index out of range [0, %d)" % (invalid, n))
+        return labels.astype(np.int64)
+    if keep is not None:
+        pairs = pairs[keep]
+    if pairs.size and (pairs.min() < 0 or pairs.max() >= n):
+        raise ValueError("%d pairs have an index out of range [0, %d)" % (int(np.count_nonzero(((pairs < 0) | (pairs >= n)).any(axis=1))), n))
+    return _components_host(pairs[:, 0], pairs[:, 1], n)
+
+
+def _threshold_count(num_perm: int, threshold: float) -> int:
+    """The smallest count ``c`` with ``float(c) / float(num_perm) >= threshold`` (:func:`jaccard_pairs`' own quotient)."""
+    return _min_count(np.arange(num_perm + 1, dtype=np.float64) / float(num_perm), float(threshold))
+
+
+def bands_clusters_host(sig: np.ndarray, dig: np.ndarray, rows: np.ndarray, threshold, extra=None) -> np.ndarray:
+    """The numpy twin of :func:`rows_clusters`: ``sig`` the ``[n, K]`` matrix, ``dig`` / ``rows`` its sorted bands."""
+    n = sig.shape[0]
+    if threshold is None:
+        u, v = _run_edges(dig, rows)
+    else:
+        pairs = _pairs_of_bands(dig, rows)
+        counts = np.count_nonzero(sig[pairs[:, 0]] == sig[pairs[:, 1]], axis=1)
+        pairs = pairs[counts >= _threshold_count(sig.shape[1], threshold)]
+        u, v = pairs[:, 0], pairs[:, 1]
+    if extra is not None and len(extra):
+        extra = np.asarray(extra, dtype=np.int64).reshape(-1, 2)
+        u, v = np.concatenate([u, extra[:, 0]]), np.concatenate([v, extra[:, 1]])
+    return _components_host(u, v, n)
+
+
+def rows_clusters(store, d_dig: int, d_rows: int, b: int, num_perm: int, threshold, extra=None) -> np.ndarray:
+    """``labels int64 [n]`` of a resident signature matrix (``DeviceRows``) and its resident sorted bands.  ``threshold=None``:
+    init, link bands, finish -- no pair is formed.  Else: candidate pairs on the device, their counts, link pairs with the
+    threshold's count, finish.  ``extra``: further edges ``[E, 2]`` from the host, linked by one more call.  Only the labels
+    come down."""
+    ctx, n = store.ctx, store.n
+    if n == 0:
+        return np.empty(0, dtype=np.int64)
+    d_labels = ctx.alloc(4 * n)
+    d_bad = ctx.to_device(np.zeros(1, dtype=np.int64))
+    ctx.cc_init_dev(d_labels.ptr, n)
+    if threshold is None:
+        ctx.cc_link_bands_dev(d_labels.ptr, n, d_dig, d_rows, n, b, d_bad.ptr)
+    else:
+        d_pairs, found = ctx.lsh_candidate_pairs_dev(d_dig, d_rows, n, b)
+        if found:
+            d_counts = ctx.alloc(4 * found)
+            ctx.jaccard_pairs_dev(store.d_sig.ptr, store.d_sig.ptr, store.code, num_perm, d_pairs.ptr, found, d_counts.ptr)
+            ctx.cc_link_pairs_dev(d_labels.ptr, n, d_pairs.ptr, found, d_counts.ptr, _threshold_count(num_perm, threshold), d_bad.ptr)
+    if extra is not None and len(extra):
+        extra = np.ascontiguousarray(extra, dtype=np.int64).reshape(-1, 2)
+        d_extra = ctx.to_device(extra)
+        ctx.cc_link_pairs_dev(d_labels.ptr, n, d_extra.ptr, extra.shape[0], None, 0, d_bad.ptr)
+    ctx.cc_finish_dev(d_labels.ptr, n)
+    labels = d_labels.download((n,), np.uint32)  # (blocking: everything enqueued above is done)
+    invalid = int(d_bad.download((1,), np.int64)[0])
+    if invalid:
+        raise _native.MhxError("%d edges name rows outside [0, %d): the bands do not belong to this matrix" % (invalid, n))
+    return labels.astype(np.int64)
+
+
+def duplicate_clusters(signatures, b: int, r: int, threshold: Optional[float] = None, gpu_mode: str = "detect") -> np.ndarray:
+    """Near-duplicate clusters of a signature matrix: ``labels int64 [N]``, ``labels[i]`` the smallest row of the cluster of row
+    ``i``.  ``labels == np.arange(N)`` marks the one row to keep per cluster; ``np.unique(labels, return_inverse=True)`` gives
+    dense cluster ids.
+
+    ``threshold=None``: the connected components of the candidate graph, ``connected_components(candidate_pairs(signatures, b,
+    r), N)`` -- rows are one cluster when a chain of shared band keys joins them.  On the device no pair is ever formed: inside
+    a band's sorted run of equal digests every row is linked to its predecessor, ``b * N`` implicit edges at most, so a bucket
+    of 10^5 identical rows costs 10^5 links and not 5 * 10^9 pairs.  WeightedMinHash matrices ``[N, S, 2]`` are taken too.
+
+    With a ``threshold`` only the candidate pairs whose ``MinHash.jaccard`` estimate reaches it are edges:
+    ``connected_components(pairs[jaccard_pairs(signatures, pairs) >= threshold], N)`` with ``pairs = candidate_pairs(...)``;
+    on the device the pairs and their counts stay there and only the labels come down.  (WeightedMinHash matrices: ``ValueError``.)"""
+    _check_gpu_mode(gpu_mode)
+    if threshold is not None and np.ndim(signatures) == 3:
+        raise ValueError("a threshold is defined for MinHash signatures, not WeightedMinHash ones")
+    mat, words = _words_matrix(signatures)
+    n, k = mat.shape
+    _check_params(k, b, r * words)
+    if n == 0:
+        return np.empty(0, dtype=np.int64)
+    if not _use_gpu(gpu_mode):
+        dig, rows = sorted_bands(mat, b, r * words, gpu_mode="disable")
+        return bands_clusters_host(mat, dig, rows, threshold)
+    ctx = _native.context()
+    store = DeviceRows(ctx, k, mat.dtype)
+    store.upload(mat)
+    d_dig, d_rows = ctx.alloc(n * b * 8), ctx.alloc(n * b * 4)
+    ctx.lsh_sort_bands_dev(store.d_sig.ptr, store.code, n, k, b, r * words, d_dig.ptr, d_rows.ptr)
+    return rows_clusters(store, d_dig.ptr, d_rows.ptr, b, k, threshold)

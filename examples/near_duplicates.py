@@ -7,7 +7,9 @@
    packed by csrc/pack_module.c, hashed and permuted on the device);
 2. ``lsh_bulk.candidate_pairs`` -- the pairs a ``MinHashLSH(params=(b, r))`` would report for each other
    (band digests, one radix sort, run detection, sort + unique on the device);
-3. ``lsh_bulk.jaccard_pairs``   -- ``MinHash.jaccard`` of every candidate pair, then a threshold.
+3. ``lsh_bulk.jaccard_pairs``   -- ``MinHash.jaccard`` of every candidate pair, then a threshold;
+4. ``lsh_bulk.duplicate_clusters`` -- the clusters those pairs form (connected components; on the device the pairs never
+   leave it) as ``labels[i]`` = the first document of ``i``'s cluster: ``labels == arange(n)`` are the documents to keep.
 
 The same objects still drop into the reference's own index: the last lines insert a few rows into a
 ``datasketch.MinHashLSH`` (if that package is importable) through ``lsh_bulk.insert_bulk`` and query it.
@@ -69,6 +71,12 @@ def main(argv=None) -> dict:
     print(f"{len(docs)} documents -> signatures {t1 - t0:.3f} s, {len(pairs)} candidate pairs {t2 - t1:.3f} s, "
           f"{len(keep)} pairs with estimated Jaccard >= {args.threshold} in {t3 - t2:.3f} s; "
           f"{recall:.1%} of the {len(truth)} planted near-duplicates found")
+    labels = lsh_bulk.duplicate_clusters(sig, args.bands, args.rows, threshold=args.threshold, gpu_mode=args.gpu_mode)
+    t4 = time.perf_counter()
+    kept_rows = int(np.count_nonzero(labels == np.arange(len(docs))))
+    sizes = np.bincount(labels, minlength=len(docs))
+    print(f"{int(np.count_nonzero(sizes > 1))} clusters of more than one document in {t4 - t3:.3f} s; "
+          f"{kept_rows} of {len(docs)} documents kept (one per cluster)")
     try:  # the reference's index still works on these rows
         from datasketch import MinHashLSH
     except ImportError:
@@ -77,7 +85,7 @@ def main(argv=None) -> dict:
         lsh = MinHashLSH(num_perm=args.num_perm, params=(args.bands, args.rows))
         lsh_bulk.insert_bulk(lsh, range(min(2000, len(docs))), sig[:2000], gpu_mode=args.gpu_mode)
         print("datasketch.MinHashLSH.query(doc 0) ->", sorted(lsh.query(MinHash(seed=1, hashvalues=sig[0])))[:5])
-    return {"signatures": sig, "pairs": pairs, "kept": keep, "recall": recall}
+    return {"signatures": sig, "pairs": pairs, "kept": keep, "recall": recall, "labels": labels}
 
 
 if __name__ == "__main__":

@@ -702,6 +702,38 @@ MHX_API_BLOOM int mhx_bloom_query(mhx_ctx *ctx, const void *sig, int sig_dtype, 
 /* d_dst |= d_src over the bands * n_blocks * 16 words of two filters of equal geometry (merging shards).  Enqueued. */
 MHX_API_BLOOM int mhx_bloom_union_dev(mhx_ctx *ctx, uint32_t *d_dst, const uint32_t *d_src, int32_t bands, int64_t n_blocks);
 
+/* ---- Near-duplicate clusters: connected components ----------------------------------------------- */
+/* The last step of deduplication (no counterpart in the reference): the rows 0 .. n-1 are the vertices, the edges are listed pairs
+ * and / or the runs of equal digests of sorted bands, and d_labels uint32[n] receives for every row the SMALLEST row number of its
+ * connected component -- one answer whatever order the edges come in.  labels[i] == i marks the one row to keep per cluster.
+ *
+ * The call sequence is mhx_cc_init_dev, then any number of link calls of either kind, then mhx_cc_finish_dev, all on one array.
+ * Between init and finish the contents of d_labels are opaque (a parent forest of the union-find; only labels[i] <= i is promised),
+ * and a link call on an array that init has not filled is undefined.  n in [0, 2^32 - 1]; n == 0, n_pairs == 0 and bands * n_sigs
+ * == 0 launch nothing and need no pointers.  All four are enqueued on the ctx stream.
+ *
+ * d_invalid (may be NULL): an int64 on the device that the link calls ADD to -- the caller zeroes it once -- the number of edges
+ * with an endpoint outside [0, n).  Such an edge is never followed, counted or not.
+ *
+ * The entry points are exported through MHX_API_CC (the same visibility as MHX_API), bound from _native._PROTOTYPES_CC and their
+ * argument checks are tested beside the feature, in tests/test_gpu_clusters.py. */
+#define MHX_API_CC __attribute__((visibility("default")))
+MHX_API_CC int mhx_cc_init_dev(mhx_ctx *ctx, uint32_t *d_labels, int64_t n);
+/* d_pairs int64[n_pairs][2] in any order; duplicates, i > j and i == j are allowed.  d_counts (may be NULL) int32[n_pairs]: pair p
+ * takes part only if d_counts[p] >= min_count -- the output of mhx_jaccard_pairs_dev* as it is, with no compaction pass. */
+MHX_API_CC int mhx_cc_link_pairs_dev(mhx_ctx *ctx, uint32_t *d_labels, int64_t n, const int64_t *d_pairs, int64_t n_pairs,
+                                     const int32_t *d_counts, int32_t min_count, int64_t *d_invalid);
+/* Sorted bands as mhx_lsh_sort_bands* writes them, digests uint64[bands][n_sigs] and rows uint32[bands][n_sigs]: position p > 0 of
+ * band j links rows[j][p - 1] and rows[j][p] when digests[j][p] == digests[j][p - 1].  That gives the components of
+ * mhx_lsh_candidate_pairs_dev's graph from at most bands * n_sigs implicit edges: a bucket of L rows costs L - 1 links, not
+ * L (L - 1) / 2 pairs.  The last entry of a band and the first of the next are never compared.  A row >= n is an invalid edge. */
+MHX_API_CC int mhx_cc_link_bands_dev(mhx_ctx *ctx, uint32_t *d_labels, int64_t n, const uint64_t *d_sorted_digests,
+                                     const uint32_t *d_sorted_rows, int64_t n_sigs, int32_t bands, int64_t *d_invalid);
+MHX_API_CC int mhx_cc_finish_dev(mhx_ctx *ctx, uint32_t *d_labels, int64_t n);
+/* Host form, blocking: init + link pairs + finish.  labels uint32[n]; *invalid (may be NULL) is set by the call. */
+MHX_API_CC int mhx_cc_pairs(mhx_ctx *ctx, const int64_t *pairs, int64_t n_pairs, const int32_t *counts, int32_t min_count, int64_t n,
+                            uint32_t *labels, int64_t *invalid);
+
 /* ---- Multi-GPU: assemble the signature matrix (RCCL over xGMI) ----------------------------- */
 /* 128-byte RCCL unique id, created on rank 0 and distributed by the caller (env, file, socket). */
 #define MHX_COMM_ID_BYTES 128
