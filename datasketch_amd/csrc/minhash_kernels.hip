@@ -404,11 +404,45 @@ __device__ __forceinline__ bool finish_block(const Two (&rows)[P], const uint32_
         const uint32_t myrow = rows[q].k1 & 15u;
         const uint32_t *rowp = tile + myrow * STRIDE;  // per-lane LDS address
         const uint32_t limit = PARTIAL ? (myrow == last_row ? last_cols : 16u) : 16u;
+        if constexpr (P <= 2) {
+            uint32_t w[kRowTokens];
 #pragma unroll
-        for (int c = 0; c < kRowTokens; ++c) {
-            uint32_t m = (uint32_t)((uint64_t)rowp[c * WPT] * sp.a_lo[q] + sp.b8[q]);
-            if (PARTIAL) m = (uint32_t)c < limit ? m : kMaxHash;
-            cols[q].add(tag16(m, (uint32_t)c));
+            for (int c = 0; c < kRowTokens; ++c) w[c] = rowp[c * WPT];
+            const auto key = [&](int c) {
+                uint32_t m = sieve_key(w[c], sp.a_lo[q], sp.b8[q]);
+                if (PARTIAL) m = (uint32_t)c < limit ? m : kMaxHash;
+                return tag16(m, (uint32_t)c);
+            };
+            // The two smallest of the 16 tagged keys by a network: 20 instructions instead of the 32 of 16 Two::add.
+            // Five triples give their (smallest, middle) each -- v_min3_u32 + v_med3_u32; the row's second smallest key
+            // is never the largest of its triple, so the two smallest of the row are the two smallest of
+            // L = {five smallest, key 15} and Mid = {five middles}: k1 = min L, k2 = min(second smallest of L, min Mid).
+            // The second smallest of L the same way: two triples (a1, a2), (b1, b2) -> min(max(a1, b1), a2, b2).
+            // min3 / med3 order multisets, so equal keys (the 2^32-1 of masked cells) come out as they do from Two::add.
+            uint32_t lo[5], mid[5];
+#pragma unroll
+            for (int i = 0; i < 5; ++i) {
+                const uint32_t x = key(3 * i), y = key(3 * i + 1), z = key(3 * i + 2);
+                lo[i] = umin3(x, y, z);
+                mid[i] = umed3(x, y, z);
+                asm volatile("" : "+v"(lo[i]), "+v"(mid[i]));  // a triple at a time: left alone, all 16 products are formed first
+                __builtin_amdgcn_sched_barrier(0);
+            }
+            const uint32_t last = key(15);
+            const uint32_t a1 = umin3(lo[0], lo[1], lo[2]), a2 = umed3(lo[0], lo[1], lo[2]);
+            const uint32_t b1 = umin3(lo[3], lo[4], last), b2 = umed3(lo[3], lo[4], last);
+            cols[q].k1 = min(a1, b1);
+            cols[q].k2 = min(umin3(max(a1, b1), a2, b2), umin3(umin3(mid[0], mid[1], mid[2]), mid[3], mid[4]));
+            asm volatile("" : "+v"(cols[q].k2));  // here, not sunk to its use below with the ten values it is made of kept live
+        } else {
+            // three and four permutations per lane keep the fold: the network's ten partial results are 7 more VGPRs at
+            // its peak, which there is one wave per SIMD fewer (66 -> 73, 80 -> 87; the packed kernel 72 -> 79)
+#pragma unroll
+            for (int c = 0; c < kRowTokens; ++c) {
+                uint32_t m = (uint32_t)((uint64_t)rowp[c * WPT] * sp.a_lo[q] + sp.b8[q]);
+                if (PARTIAL) m = (uint32_t)c < limit ? m : kMaxHash;
+                cols[q].add(tag16(m, (uint32_t)c));
+            }
         }
         const uint32_t j1 = cols[q].k1 & 15u;
         best[q] = WPT == 2 ? *reinterpret_cast<const uint64_t *>(rowp + 2 * j1) : (uint64_t)rowp[j1];
