@@ -26,6 +26,7 @@ from oracle import oracle as O  # noqa: E402
 
 _i64 = ctypes.c_int64
 CASES = 0
+BETWEEN = None  # tests/poison_cases.py: called with the name of every finished case, before the next one starts
 
 
 def _done(name):
@@ -33,6 +34,8 @@ def _done(name):
     CASES += 1
     if os.environ.get("GUARD_VERBOSE"):
         print("ok", name, flush=True)
+    if BETWEEN is not None:
+        BETWEEN(name)
 
 
 _KEEP = []  # GUARD_KEEP=1: nothing is freed before the process ends (no virtual address is ever mapped twice)
