@@ -178,6 +178,15 @@ _PROTOTYPES_CC = {
     "mhx_cc_finish_dev": [_vp, _vp, _i64],
     "mhx_cc_pairs": [_vp, _vp, _i64, _vp, _i32, _i64, _vp, ctypes.POINTER(_i64)],
 }
+# Entry points declared MHX_API_SHINGLE (shingles hashed in place): a sixth list for the same reason; declared = bound = exported is
+# checked in tests/test_shingle_host.py, the argument checks in tests/test_gpu_shingles.py.
+_PROTOTYPES_SHINGLE = {
+    "mhx_shingle_window_offsets": [_vp, _i64, _i64, _vp],
+    "mhx_sha1_windows_dev": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _int, _vp],
+    "mhx_sha1_windows": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _vp],
+    "mhx_minhash_bulk_windows_typed": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _vp, _i64, _vp, _int],
+    "mhx_hll_bulk_windows": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp],
+}
 _RESTYPE = {"mhx_last_error": ctypes.c_char_p, "mhx_version": ctypes.c_char_p}
 
 EXPORTED_SYMBOLS = sorted(list(_PROTOTYPES) + list(_RESTYPE))
@@ -185,6 +194,7 @@ EXPORTED_SYMBOLS_EXT = sorted(_PROTOTYPES_EXT)
 EXPORTED_SYMBOLS_BLOOM = sorted(_PROTOTYPES_BLOOM)
 EXPORTED_SYMBOLS_TOPK = sorted(_PROTOTYPES_TOPK)
 EXPORTED_SYMBOLS_CC = sorted(_PROTOTYPES_CC)
+EXPORTED_SYMBOLS_SHINGLE = sorted(_PROTOTYPES_SHINGLE)
 
 
 try:  # CPython helper (csrc/pack_module.c): ~10 ns per token instead of ~180 in the interpreter
@@ -224,7 +234,7 @@ def load():
             )
             raise MhxError(_lib_error) from e
         for name, argtypes in (list(_PROTOTYPES.items()) + list(_PROTOTYPES_EXT.items()) + list(_PROTOTYPES_BLOOM.items())
-                               + list(_PROTOTYPES_TOPK.items()) + list(_PROTOTYPES_CC.items())):
+                               + list(_PROTOTYPES_TOPK.items()) + list(_PROTOTYPES_CC.items()) + list(_PROTOTYPES_SHINGLE.items())):
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = _int
@@ -301,6 +311,16 @@ def gpu_detected() -> bool:
 
 def _ptr(arr: Optional[np.ndarray]):
     return None if arr is None else arr.ctypes.data
+
+
+def window_offsets(doc_offsets, width: int) -> np.ndarray:
+    """mhx_shingle_window_offsets: the first shingle of every document (pure host logic: the library, no device)."""
+    doc_offsets = np.ascontiguousarray(doc_offsets, dtype=np.int64).reshape(-1)
+    if doc_offsets.size < 1:
+        raise ValueError("doc_offsets has documents + 1 entries")
+    out = np.empty(doc_offsets.size, dtype=np.int64)
+    check(load().mhx_shingle_window_offsets(_ptr(doc_offsets), doc_offsets.size - 1, int(width), _ptr(out)))
+    return out
 
 
 class WeightedFeed:
@@ -655,6 +675,68 @@ class Context:
         out = np.empty((n_sets, k), dtype=np.uint64)
         check(self.lib.mhx_minhash_bulk_bytes_typed(perm, _ptr(buf), _ptr(byte_offsets), n_tokens, MHX_U32 if bits == 32 else MHX_U64,
                                                     _ptr(set_offsets), n_sets, _ptr(init), stride, _ptr(out)))
+        return out
+
+    @staticmethod
+    def _windows_corpus(buf, item_offsets, doc_offsets):
+        """The three arrays of a shingle corpus as the C ABI takes them, and (n_items, n_docs)."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
+        doc_offsets = np.ascontiguousarray(doc_offsets, dtype=np.int64).reshape(-1)
+        if doc_offsets.size < 1:
+            raise ValueError("doc_offsets has documents + 1 entries")
+        if item_offsets is None:
+            return buf, None, doc_offsets, buf.size, doc_offsets.size - 1
+        item_offsets = np.ascontiguousarray(item_offsets, dtype=np.int64).reshape(-1)
+        if item_offsets.size < 1 or int(item_offsets[-1]) > buf.size:
+            raise ValueError("item_offsets has items + 1 entries and ends inside buf")
+        return buf, item_offsets, doc_offsets, item_offsets.size - 1, doc_offsets.size - 1
+
+    def sha1_windows(self, buf, doc_offsets, width: int, item_offsets=None, bits: int = 32):
+        """(sha1_hash32 / sha1_hash64 of every shingle of a corpus, set_offsets): mhx_sha1_windows (host in, host out)."""
+        if bits not in (32, 64):
+            raise ValueError("bits must be 32 or 64")
+        buf, item_offsets, doc_offsets, n_items, n_docs = self._windows_corpus(buf, item_offsets, doc_offsets)
+        set_offsets = window_offsets(doc_offsets, width)
+        out = np.empty(int(set_offsets[-1]), dtype=np.uint32 if bits == 32 else np.uint64)
+        check(self.lib.mhx_sha1_windows(self.handle, _ptr(buf), _ptr(item_offsets), n_items, _ptr(doc_offsets), n_docs, int(width),
+                                        MHX_U32 if bits == 32 else MHX_U64, _ptr(out)))
+        return out, set_offsets
+
+    def sha1_windows_dev(self, d_bytes: Optional[int], d_item_offsets: Optional[int], d_doc_offsets: Optional[int], d_set_offsets: Optional[int],
+                         n_docs: int, n_windows: int, width: int, out_dtype: int, d_out: Optional[int]) -> None:
+        """mhx_sha1_windows_dev: one hash per window into ``d_out``; the device arrays are trusted; enqueued."""
+        check(self.lib.mhx_sha1_windows_dev(self.handle, _vp(d_bytes), _vp(d_item_offsets), _vp(d_doc_offsets), _vp(d_set_offsets), int(n_docs),
+                                            int(n_windows), int(width), out_dtype, _vp(d_out)))
+
+    def minhash_bulk_windows(self, permutations, buf, doc_offsets, width: int, item_offsets=None, init: Optional[np.ndarray] = None,
+                             bits: int = 32, out_dtype=np.uint64) -> np.ndarray:
+        """Text -> shingles -> sha1_hash32 / sha1_hash64 -> [n_docs, K] signatures, all on the device (mhx_minhash_bulk_windows_typed)."""
+        if bits not in (32, 64):
+            raise ValueError("bits must be 32 or 64")
+        perm = self.perm_handle(permutations)
+        k = len(permutations[0])
+        buf, item_offsets, doc_offsets, n_items, n_docs = self._windows_corpus(buf, item_offsets, doc_offsets)
+        stride = 0
+        if init is not None:
+            init = np.ascontiguousarray(init, dtype=np.uint64)
+            if init.shape == (n_docs, k):
+                stride = k
+            elif init.shape != (k,):
+                raise ValueError("init must have shape (K,) or (n_docs, K)")
+        out = np.empty((n_docs, k), dtype=out_dtype)
+        check(self.lib.mhx_minhash_bulk_windows_typed(perm, _ptr(buf), _ptr(item_offsets), n_items, _ptr(doc_offsets), n_docs, int(width),
+                                                      MHX_U32 if bits == 32 else MHX_U64, _ptr(init), stride, _ptr(out),
+                                                      MHX_U32 if np.dtype(out_dtype) == np.uint32 else MHX_U64))
+        return out
+
+    def hll_bulk_windows(self, buf, doc_offsets, width: int, p: int, item_offsets=None, hash_bits: int = 32,
+                         init: Optional[np.ndarray] = None) -> np.ndarray:
+        """Text -> shingles -> sha1_hash32 / sha1_hash64 (``hash_bits``) -> uint8 [n_docs, 2**p] registers, all on the device."""
+        buf, item_offsets, doc_offsets, n_items, n_docs = self._windows_corpus(buf, item_offsets, doc_offsets)
+        init, stride = self._hll_init(init, n_docs, 1 << int(p))
+        out = np.empty((n_docs, 1 << int(p)), dtype=np.uint8)
+        check(self.lib.mhx_hll_bulk_windows(self.handle, _ptr(buf), _ptr(item_offsets), n_items, _ptr(doc_offsets), n_docs, int(width),
+                                            int(hash_bits), int(p), _ptr(init), stride, _ptr(out)))
         return out
 
     def minhash_update_batch(self, permutations, hv: np.ndarray, hashvalues: np.ndarray) -> np.ndarray:

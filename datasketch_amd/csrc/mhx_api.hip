@@ -2267,6 +2267,163 @@ int mhx_hll_union_groups(mhx_ctx *ctx, const uint8_t *reg, int64_t n_rows, int32
     return hll_union_groups(ctx, reg, n_rows, p, group_offsets, n_groups, out, kHost);
 }
 
+// ---- shingles: the windows of a document hashed in place (datasketch_amd/shingle.py is the definition) ---------------------
+static int check_windows(int64_t n_docs, int64_t width) {
+    MHX_REQUIRE(width >= 1, "width must be >= 1");
+    MHX_REQUIRE(n_docs >= 0, "n_docs must be >= 0");
+    return MHX_OK;
+}
+
+int mhx_shingle_window_offsets(const int64_t *doc_offsets, int64_t n_docs, int64_t width, int64_t *set_offsets) {
+    MHX_TRY(check_windows(n_docs, width));
+    MHX_REQUIRE(doc_offsets && set_offsets, "doc_offsets/set_offsets is NULL");
+    set_offsets[0] = 0;
+    for (int64_t d = 0; d < n_docs; ++d) {
+        const int64_t items = doc_offsets[d + 1] - doc_offsets[d];
+        MHX_REQUIRE(items >= 0, "doc_offsets must be non-decreasing (document %lld)", (long long)d);
+        set_offsets[d + 1] = set_offsets[d] + (items == 0 ? 0 : items < width ? 1 : items - width + 1);
+    }
+    return MHX_OK;
+}
+
+int mhx_sha1_windows_dev(mhx_ctx *ctx, const uint8_t *d_bytes, const int64_t *d_item_offsets, const int64_t *d_doc_offsets,
+                         const int64_t *d_set_offsets, int64_t n_docs, int64_t n_windows, int64_t width, int out_dtype, void *d_out) {
+    MHX_ENTER(ctx, ctx);
+    MHX_TRY(check_windows(n_docs, width));
+    MHX_REQUIRE(n_windows >= 0, "n_windows must be >= 0");
+    MHX_CHECK_DTYPE(out_dtype);
+    if (n_docs == 0 || n_windows == 0) return MHX_OK;
+    MHX_REQUIRE_POINTERS(d_doc_offsets && d_set_offsets && d_out, kDevice);
+    MHX_TRY(ctx->activate());
+    return mhx::launch_sha1_windows(ctx, d_bytes, d_item_offsets, d_doc_offsets, d_set_offsets, n_docs, n_windows, width, out_dtype, d_out);
+}
+
+extern "C++" {
+namespace {
+
+// a host corpus of the host forms, checked (plan) and then staged (upload): bytes -> In; item offsets | document offsets |
+// set offsets -> Offsets.  Aux and Out are the caller's.
+struct Windows {
+    std::vector<int64_t> set_offsets;
+    int64_t n_windows = 0, n_bytes = 0;
+    uint8_t *d_bytes = nullptr;
+    int64_t *d_items = nullptr, *d_docs = nullptr, *d_sets = nullptr;
+
+    int plan(const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items, const int64_t *doc_offsets, int64_t n_docs, int64_t width) {
+        MHX_REQUIRE(n_items >= 0, "n_items must be >= 0");
+        MHX_REQUIRE(doc_offsets, "doc_offsets is NULL");
+        MHX_REQUIRE(doc_offsets[0] == 0 && doc_offsets[n_docs] == n_items, "doc_offsets must run from 0 to n_items");
+        if (item_offsets) {
+            MHX_REQUIRE(item_offsets[0] == 0, "item_offsets[0] must be 0");
+            for (int64_t i = 0; i < n_items; ++i)
+                MHX_REQUIRE(item_offsets[i + 1] >= item_offsets[i], "item_offsets must be non-decreasing (item %lld)", (long long)i);
+        }
+        n_bytes = item_offsets ? item_offsets[n_items] : n_items;
+        MHX_REQUIRE(bytes || n_bytes == 0, "bytes is NULL");
+        set_offsets.resize((size_t)n_docs + 1);
+        MHX_TRY(mhx_shingle_window_offsets(doc_offsets, n_docs, width, set_offsets.data()));
+        n_windows = set_offsets[(size_t)n_docs];
+        return MHX_OK;
+    }
+
+    int upload(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items, const int64_t *doc_offsets, int64_t n_docs) {
+        Stage s(ctx);
+        const auto p_bytes = s.piece(Stage::In, (size_t)n_bytes);
+        if (n_bytes == 0) s.ask(Stage::In, 8);
+        Stage::Piece p_items{Stage::Offsets, 0, 0};
+        if (item_offsets) p_items = s.piece(Stage::Offsets, sizeof(int64_t) * (size_t)(n_items + 1));
+        const auto p_docs = s.piece(Stage::Offsets, sizeof(int64_t) * (size_t)(n_docs + 1)), p_sets = s.piece(Stage::Offsets, p_docs.bytes);
+        MHX_TRY(s.commit());
+        d_bytes = s.at<uint8_t>(p_bytes);
+        d_items = item_offsets ? s.at<int64_t>(p_items) : nullptr;
+        d_docs = s.at<int64_t>(p_docs);
+        d_sets = s.at<int64_t>(p_sets);
+        MHX_TRY(s.upload(p_bytes, bytes));
+        MHX_TRY(s.upload(p_items, item_offsets));
+        MHX_TRY(s.upload(p_docs, doc_offsets));
+        return s.upload(p_sets, set_offsets.data());
+    }
+};
+
+}  // namespace
+}  // extern "C++"
+
+int mhx_sha1_windows(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items, const int64_t *doc_offsets,
+                     int64_t n_docs, int64_t width, int out_dtype, void *out) {
+    MHX_ENTER(ctx, ctx);
+    MHX_TRY(check_windows(n_docs, width));
+    MHX_CHECK_DTYPE(out_dtype);
+    if (n_docs == 0) return MHX_OK;
+    Windows w;
+    MHX_TRY(w.plan(bytes, item_offsets, n_items, doc_offsets, n_docs, width));
+    if (w.n_windows == 0) return MHX_OK;
+    MHX_REQUIRE(out, "out is NULL");
+    MHX_TRY(ctx->activate());
+    MHX_TRY(w.upload(ctx, bytes, item_offsets, n_items, doc_offsets, n_docs));
+    Stage s(ctx);
+    const auto p_out = s.piece(Stage::Out, (size_t)w.n_windows * (out_dtype == MHX_U32 ? 4 : 8));
+    MHX_TRY(s.commit());
+    MHX_TRY(mhx::launch_sha1_windows(ctx, w.d_bytes, w.d_items, w.d_docs, w.d_sets, n_docs, w.n_windows, width, out_dtype, s.at<void>(p_out)));
+    return s.fetch(out, p_out);
+}
+
+int mhx_minhash_bulk_windows_typed(mhx_perm *perm, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items,
+                                   const int64_t *doc_offsets, int64_t n_docs, int64_t width, int hash_dtype, const uint64_t *init,
+                                   int64_t init_stride, void *out, int out_dtype) {
+    MHX_ENTER(perm, perm->ctx);
+    MHX_TRY(check_windows(n_docs, width));
+    MHX_REQUIRE(hash_dtype == MHX_U32 || hash_dtype == MHX_U64, "hash_dtype must be MHX_U32 (sha1_hash32) or MHX_U64 (sha1_hash64)");
+    MHX_CHECK_DTYPE(out_dtype);
+    MHX_REQUIRE(init_stride == 0 || init_stride >= perm->num_perm, "init_stride must be 0 or >= num_perm");
+    if (n_docs == 0) return MHX_OK;
+    MHX_REQUIRE(out, "out is NULL");
+    Windows w;
+    MHX_TRY(w.plan(bytes, item_offsets, n_items, doc_offsets, n_docs, width));
+    mhx_ctx *ctx = perm->ctx;
+    MHX_TRY(ctx->activate());
+    MHX_TRY(w.upload(ctx, bytes, item_offsets, n_items, doc_offsets, n_docs));
+    const int64_t k = perm->num_perm;
+    // Aux: init | window hashes (uint32 or uint64);  Out: signatures
+    Stage s(ctx);
+    const auto p_init = s.piece(Stage::Aux, init ? sizeof(uint64_t) * (size_t)(init_stride ? n_docs * init_stride : k) : 0);
+    const auto p_hv = s.piece(Stage::Aux, (hash_dtype == MHX_U32 ? 4 : 8) * (size_t)w.n_windows);
+    const auto p_out = s.piece(Stage::Out, (out_dtype == MHX_U32 ? 4 : 8) * (size_t)(n_docs * k));
+    MHX_TRY(s.commit());
+    MHX_TRY(s.upload(p_init, init));
+    MHX_TRY(mhx::launch_sha1_windows(ctx, w.d_bytes, w.d_items, w.d_docs, w.d_sets, n_docs, w.n_windows, width, hash_dtype, s.at<void>(p_hv)));
+    MHX_TRY(mhx::launch_minhash_bulk(perm, s.at<void>(p_hv), hash_dtype, w.d_sets, 0, n_docs, w.n_windows, init ? s.at<uint64_t>(p_init) : nullptr,
+                                     init_stride, s.at<void>(p_out), out_dtype));
+    return s.fetch(out, p_out);
+}
+
+int mhx_hll_bulk_windows(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items, const int64_t *doc_offsets,
+                         int64_t n_docs, int64_t width, int32_t hash_bits, int32_t p, const uint8_t *init, int64_t init_stride, uint8_t *out) {
+    MHX_ENTER(ctx, ctx);
+    MHX_TRY(check_windows(n_docs, width));
+    MHX_TRY(check_hll(p, hash_bits));
+    const int64_t m = (int64_t)1 << p;
+    MHX_REQUIRE(init_stride == 0 || init_stride == m, "init_stride must be 0 (one shared row) or m = %lld", (long long)m);
+    if (n_docs == 0) return MHX_OK;
+    MHX_REQUIRE(out, "out is NULL");
+    Windows w;
+    MHX_TRY(w.plan(bytes, item_offsets, n_items, doc_offsets, n_docs, width));
+    MHX_TRY(ctx->activate());
+    MHX_TRY(w.upload(ctx, bytes, item_offsets, n_items, doc_offsets, n_docs));
+    const int hash_dtype = hash_bits == 32 ? MHX_U32 : MHX_U64;  // sha1_hash32 / sha1_hash64: the hashes fit hash_bits by construction
+    // Aux: init | window hashes;  Out: registers
+    Stage s(ctx);
+    Stage::Piece p_init{Stage::Aux, 0, 0};
+    if (init) p_init = s.piece(Stage::Aux, (size_t)(init_stride ? n_docs * m : m));
+    const auto p_hv = s.piece(Stage::Aux, (hash_bits == 32 ? 4 : 8) * (size_t)w.n_windows);
+    const auto p_out = s.piece(Stage::Out, (size_t)(n_docs * m));
+    MHX_TRY(s.commit());
+    MHX_TRY(s.upload(p_init, init));
+    MHX_TRY(mhx::launch_sha1_windows(ctx, w.d_bytes, w.d_items, w.d_docs, w.d_sets, n_docs, w.n_windows, width, hash_dtype, s.at<void>(p_hv)));
+    MHX_TRY(mhx::launch_hll_bulk(ctx, s.at<void>(p_hv), hash_dtype, w.d_sets, 0, n_docs, w.n_windows, p, hash_bits,
+                                 init ? s.at<uint8_t>(p_init) : nullptr, init_stride, s.at<uint8_t>(p_out), nullptr));
+    return s.fetch(out, p_out);
+}
+
 // ---- MinHashLSHBloom: per-band Bloom filters (ref: datasketch/lsh_bloom.py) ----------------------------------------------
 static int check_bloom(int32_t bands, int64_t n_blocks) {
     MHX_REQUIRE(bands > 0 && bands <= (1 << 24), "bands must be in [1, 2^24]");

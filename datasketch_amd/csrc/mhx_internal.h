@@ -172,6 +172,9 @@ int launch_minhash_bulk(mhx_perm *perm, const void *d_hv, int hv_dtype, const in
                         int64_t first_token = 0);
 int launch_sha1_tokens(mhx_ctx *ctx, const uint8_t *d_bytes, const int64_t *d_offsets, int64_t n_tokens,
                        int out_dtype, void *d_out);
+// shingles hashed in place: d_item_offsets == nullptr = windows of bytes; d_set_offsets = the first window of every document
+int launch_sha1_windows(mhx_ctx *ctx, const uint8_t *d_bytes, const int64_t *d_item_offsets, const int64_t *d_doc_offsets,
+                        const int64_t *d_set_offsets, int64_t n_docs, int64_t n_windows, int64_t width, int out_dtype, void *d_out);
 int launch_minhash_merge(mhx_ctx *ctx, const uint64_t *d_x, const uint64_t *d_y, int64_t count,
                          uint64_t *d_out);
 int launch_weighted(mhx_wgen *gen, const int64_t *d_indptr, const int32_t *d_indices,

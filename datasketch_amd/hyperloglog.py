@@ -26,6 +26,7 @@ from typing import Callable, Iterable, List, Optional
 import numpy as np
 
 from datasketch_amd import _native
+from datasketch_amd import shingle as _shingle
 from datasketch_amd.hashfunc import prehashed, sha1_hash32, sha1_hash64
 from datasketch_amd.minhash import _no_device_error
 
@@ -400,7 +401,7 @@ class HyperLogLog:
 
     @staticmethod
     def bulk_registers(b=None, packed=None, p: int = 8, hashfunc: Callable = sha1_hash32, hash_bits: int = 32,
-                       gpu_mode: str = "detect") -> np.ndarray:
+                       gpu_mode: str = "detect", documents=None, shingle=None) -> np.ndarray:
         """The int8 ``[N, 2**p]`` register matrix of a corpus of N sets, without creating N objects.
 
         ``b``: any iterable of token iterables; with ``hashfunc=prehashed`` also a 2-D integer array (fixed-length sets; uint32
@@ -409,14 +410,23 @@ class HyperLogLog:
         the device when ``hashfunc is sha1_hash32`` with ``hash_bits=32``, or ``sha1_hash64`` with ``hash_bits=64``; any other
         callable is applied per token on the host and the integers go to the device.  ``hash_bits=64`` gives the registers of
         the reference's ``HyperLogLogPlusPlus``.  A hash that does not fit ``hash_bits`` raises ``ValueError``, as the
-        reference's ``update`` does."""
+        reference's ``update`` does.
+
+        Text: ``documents=`` with ``shingle=k`` (a ``(buf, doc_offsets)`` pair or a list of ``bytes`` / ``str``; a ``str`` is shingled
+        over its UTF-8 bytes) counts the distinct ``k``-byte shingles of every document, ``packed=`` with ``shingle=w`` its distinct
+        shingles of ``w`` consecutive tokens -- the rules of ``MinHash.bulk_signatures`` and :mod:`datasketch_amd.shingle`.  On the
+        device the windows are hashed where they lie; ``hyperloglog.count_many`` turns the registers into counts."""
         _check_p(p)
         if hash_bits not in (32, 64):
             raise ValueError("hash_bits must be 32 or 64")
         if not callable(hashfunc):
             raise ValueError("The hashfunc must be a callable.")
-        if (b is None) == (packed is None):
-            raise ValueError("give the corpus either as b or as packed=(buf, byte_offsets, set_offsets)")
+        if (b is not None) + (packed is not None) + (documents is not None) != 1:
+            raise ValueError("give the corpus as exactly one of b, packed=(buf, byte_offsets, set_offsets) and documents=")
+        if shingle is not None and b is not None:
+            raise ValueError("shingle= goes with documents= (bytes) or packed= (tokens), not with b")
+        if documents is not None and shingle is None:
+            raise ValueError("documents= needs shingle=k, the number of bytes per shingle")
         device = _use_gpu(gpu_mode)
         sha1_bits = 32 if hashfunc is sha1_hash32 else 64 if hashfunc is sha1_hash64 else 0
         device_sha1 = device and sha1_bits == hash_bits
@@ -443,7 +453,25 @@ class HyperLogLog:
                 s = e
 
         blocks = []
-        if packed is not None:
+        if shingle is not None:
+            if documents is not None:
+                buf, doc_offsets = _shingle.join_documents(documents)
+                item_offsets = None
+            else:
+                if not (isinstance(packed, tuple) and len(packed) == 3):
+                    raise ValueError("packed is a (buf, byte_offsets, set_offsets) triple")
+                buf, item_offsets, doc_offsets = packed
+            buf, item_offsets, doc_offsets, width = _shingle.check_corpus(buf, item_offsets, doc_offsets, shingle)
+            for s, e in _shingle.window_chunks(_shingle.window_offsets(doc_offsets, width), max_sets, _BULK_CHUNK_TOKENS):
+                piece, local_items, local_docs = _shingle.corpus_piece(buf, item_offsets, doc_offsets, s, e)
+                if device_sha1:
+                    blocks.append(_native.context().hll_bulk_windows(piece, local_docs, width, p, local_items, hash_bits))
+                    continue
+                sets = _shingle.host_shingles(piece, local_items, local_docs, width)
+                offsets = np.zeros(len(sets) + 1, dtype=np.int64)
+                np.cumsum(np.fromiter(map(len, sets), dtype=np.int64, count=len(sets)), out=offsets[1:])
+                blocks.append(from_hashes(_as_hashes([hashfunc(t) for d in sets for t in d], hash_bits, p), offsets, 0, e - s))
+        elif packed is not None:
             if not (isinstance(packed, tuple) and len(packed) == 3):
                 raise ValueError("packed is a (buf, byte_offsets, set_offsets) triple")
             buf = np.frombuffer(memoryview(packed[0]), dtype=np.uint8) if not isinstance(packed[0], np.ndarray) else np.ascontiguousarray(packed[0]).view(np.uint8).reshape(-1)

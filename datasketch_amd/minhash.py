@@ -24,7 +24,7 @@ from typing import Callable, Generator, Iterable, List, Optional, Tuple
 
 import numpy as np
 
-from datasketch_amd import _native
+from datasketch_amd import _native, shingle
 from datasketch_amd.hashfunc import prehashed, sha1_hash32, sha1_hash64
 
 # The size of a hash value in number of bytes (reference: datasketch/minhash.py:27)
@@ -366,7 +366,7 @@ class MinHash:
                 yield m._spawn(row.copy())
 
     @classmethod
-    def bulk_signatures(cls, b=None, out_dtype=np.uint64, packed=None, **minhash_kwargs) -> np.ndarray:
+    def bulk_signatures(cls, b=None, out_dtype=np.uint64, packed=None, documents=None, shingle=None, **minhash_kwargs) -> np.ndarray:
         """Not in the reference: the ``[N, K]`` signature matrix of a corpus, without creating N
         Python objects.  ``b`` is any iterable of token iterables, or -- with ``hashfunc=prehashed``
         -- a 2-D integer array (fixed-length sets; a uint32 array is uploaded as it is) or a
@@ -378,15 +378,31 @@ class MinHash:
         set_offsets[j+1]`` (what a tokenizer writing into one buffer produces; the layout of
         ``mhx_minhash_bulk_bytes``).  No per-object packing on the host at all: with the default ``hashfunc``
         (``sha1_hash32``, or ``sha1_hash64``) SHA-1 and MinHash both run on the device; any other ``hashfunc``, or
-        ``gpu_mode='disable'``, is applied per token on the host (ref: minhash.py:262-263)."""
+        ``gpu_mode='disable'``, is applied per token on the host (ref: minhash.py:262-263).
+
+        Text: ``documents=`` with ``shingle=k`` takes the sets to be the ``k``-byte shingles of the documents
+        (:func:`datasketch_amd.shingle.byte_shingles`: every window of ``k`` consecutive bytes, the whole document where it is
+        shorter).  ``documents`` is a ``(buf, doc_offsets)`` pair -- document ``d`` is ``buf[doc_offsets[d]:doc_offsets[d+1]]`` -- or
+        a list of ``bytes`` / ``str``, joined on the host; a ``str`` is shingled over its UTF-8 bytes, not its characters.
+        ``packed=`` with ``shingle=w`` takes the sets to be the shingles of ``w`` consecutive tokens
+        (:func:`datasketch_amd.shingle.token_shingles`).  With ``sha1_hash32`` / ``sha1_hash64`` on the device the windows are hashed
+        where they lie -- nothing is materialised; any other ``hashfunc``, or ``gpu_mode='disable'``, is applied to the shingles of
+        :mod:`datasketch_amd.shingle` on the host."""
         if np.dtype(out_dtype) not in (np.dtype(np.uint64), np.dtype(np.uint32)):
             raise ValueError("out_dtype must be uint64 or uint32")
-        if (b is None) == (packed is None):
-            raise ValueError("give the corpus either as b or as packed=(buf, byte_offsets, set_offsets)")
+        if (b is not None) + (packed is not None) + (documents is not None) != 1:
+            raise ValueError("give the corpus as exactly one of b, packed=(buf, byte_offsets, set_offsets) and documents=")
+        if shingle is not None and b is not None:
+            raise ValueError("shingle= goes with documents= (bytes) or packed= (tokens), not with b")
+        if documents is not None and shingle is None:
+            raise ValueError("documents= needs shingle=k, the number of bytes per shingle")
         m = cls(**minhash_kwargs)
         if np.dtype(out_dtype) == np.uint32 and not m.is_empty() and int(m.hashvalues.max()) > 0xFFFFFFFF:
             raise ValueError("initial hashvalues >= 2**32 do not fit uint32 signatures")
-        blocks = list(m._packed_chunks(packed, np.dtype(out_dtype)) if packed is not None else m._bulk_chunks(b, np.dtype(out_dtype)))
+        if shingle is not None:
+            blocks = list(m._window_chunks(documents, packed, shingle, np.dtype(out_dtype)))
+        else:
+            blocks = list(m._packed_chunks(packed, np.dtype(out_dtype)) if packed is not None else m._bulk_chunks(b, np.dtype(out_dtype)))
         if not blocks:
             return np.empty((0, len(m)), dtype=out_dtype)
         return blocks[0] if len(blocks) == 1 else np.concatenate(blocks, axis=0)
@@ -429,6 +445,32 @@ class MinHash:
                 blk = self._signatures_csr(hv, local_sets, 0, e - s, init)
             yield blk.astype(out_dtype, copy=False)
             s = e
+
+    def _window_chunks(self, documents, packed, width, out_dtype=np.uint64) -> Generator[np.ndarray, None, None]:
+        """Signature blocks of a corpus whose sets are shingles -- windows of ``width`` bytes of ``documents`` or of ``width`` tokens
+        of ``packed`` -- in chunks of whole documents, a window counting as a token (see :meth:`bulk_signatures`)."""
+        if documents is not None:
+            buf, doc_offsets = shingle.join_documents(documents)
+            item_offsets = None
+        else:
+            if not (isinstance(packed, tuple) and len(packed) == 3):
+                raise ValueError("packed is a (buf, byte_offsets, set_offsets) triple")
+            buf, item_offsets, doc_offsets = packed
+        buf, item_offsets, doc_offsets, width = shingle.check_corpus(buf, item_offsets, doc_offsets, width)
+        init = None if self.is_empty() else self.hashvalues
+        bits = 32 if self.hashfunc is sha1_hash32 else 64 if self.hashfunc is sha1_hash64 else 0
+        on_device = bits and self._use_gpu()
+        for s, e in shingle.window_chunks(shingle.window_offsets(doc_offsets, width), _BULK_CHUNK_SETS, _BULK_CHUNK_TOKENS):
+            piece, local_items, local_docs = shingle.corpus_piece(buf, item_offsets, doc_offsets, s, e)
+            if on_device:
+                yield _native.context().minhash_bulk_windows(self.permutations, piece, local_docs, width, local_items, init, bits, out_dtype)
+                continue
+            f = self.hashfunc
+            sets = shingle.host_shingles(piece, local_items, local_docs, width)
+            offsets = np.zeros(len(sets) + 1, dtype=np.int64)
+            np.cumsum(np.fromiter(map(len, sets), dtype=np.int64, count=len(sets)), out=offsets[1:])
+            hv = _as_hash_array([f(t) for d in sets for t in d]).reshape(-1) if offsets[-1] else np.empty(0, dtype=np.uint64)
+            yield self._signatures_csr(hv, offsets, 0, e - s, init).astype(out_dtype, copy=False)
 
     # ------------------------------------------------------------------ pickling
     # State is plain numpy + the gpu_mode string: device handles live in the process-wide

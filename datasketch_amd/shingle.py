@@ -1,0 +1,154 @@
+"""Shingles: the sliding windows that turn a document into the set MinHash and HyperLogLog summarise.
+
+Not in the reference, which leaves the step to its caller (``for i in range(len(d) - k + 1): m.update(d[i:i+k])``).  The three
+functions :func:`byte_shingles`, :func:`token_shingles` and :func:`window_offsets` ARE the definition; the device kernel
+(``sha1_windows_kernel``, csrc/sha1_kernels.hip), the ``gpu_mode='disable'`` paths and the tests are all written against them.
+
+A corpus is one byte buffer plus ``doc_offsets`` (int64, documents + 1 entries).  A window is ``width`` consecutive *items* of one
+document and never crosses into the next document:
+
+* byte mode: an item is a byte; document ``d`` owns bytes ``doc_offsets[d] .. doc_offsets[d+1]``;
+* token mode: item ``i`` is ``buf[item_offsets[i]:item_offsets[i+1]]`` and document ``d`` owns items ``doc_offsets[d] ..
+  doc_offsets[d+1]`` -- the ``packed=(buf, byte_offsets, set_offsets)`` layout.  A window of ``w`` tokens is the contiguous byte range
+  from the start of its first token to the end of its last, so a tokenizer that keeps each word's trailing separator gets the
+  natural w-word shingle.
+
+A document of ``m`` items has ``m - width + 1`` windows, exactly one (the whole document) if ``0 < m < width`` and none if it is empty.
+Repeated windows stay in (min and max are idempotent); tokens may be empty, and a window of no bytes hashes as ``sha1(b"")``.
+"""
+from __future__ import annotations
+
+from typing import Iterator, List, Optional, Sequence, Tuple
+
+import numpy as np
+
+from datasketch_amd import _native
+from datasketch_amd.hashfunc import sha1_hash32, sha1_hash64
+
+
+def _check_width(width) -> int:
+    if isinstance(width, bool) or not isinstance(width, (int, np.integer)) or width < 1:
+        raise ValueError("the shingle width must be an integer >= 1")
+    return int(width)
+
+
+def byte_shingles(doc: bytes, k: int) -> List[bytes]:
+    """The ``k``-byte windows of ``doc``, in order; the whole document if it is shorter than ``k``; nothing if it is empty."""
+    k = _check_width(k)
+    doc = bytes(doc)
+    if len(doc) <= k:
+        return [doc] if doc else []
+    return [doc[i: i + k] for i in range(len(doc) - k + 1)]
+
+
+def token_shingles(tokens: Sequence[bytes], w: int) -> List[bytes]:
+    """The windows of ``w`` consecutive tokens of a document, each as the bytes of its tokens joined; all tokens joined if there are
+    fewer than ``w``; nothing if there is no token."""
+    w = _check_width(w)
+    tokens = [bytes(t) for t in tokens]
+    if len(tokens) <= w:
+        return [b"".join(tokens)] if tokens else []
+    return [b"".join(tokens[i: i + w]) for i in range(len(tokens) - w + 1)]
+
+
+def window_offsets(doc_offsets, width: int) -> np.ndarray:
+    """int64 [documents + 1]: the prefix sums of the per-document window counts -- the CSR offsets of the windows."""
+    width = _check_width(width)
+    doc_offsets = np.asarray(doc_offsets, dtype=np.int64).reshape(-1)
+    if doc_offsets.size < 1:
+        raise ValueError("doc_offsets has documents + 1 entries")
+    items = np.diff(doc_offsets)
+    if np.any(items < 0):
+        raise ValueError("doc_offsets must never decrease")
+    out = np.zeros(doc_offsets.size, dtype=np.int64)
+    np.cumsum(np.where(items == 0, 0, np.where(items < width, 1, items - width + 1)), out=out[1:])
+    return out
+
+
+# ---- what MinHash.bulk_signatures, HyperLogLog.bulk_registers and sha1_windows share ---------------------------------------
+def _as_bytes_array(buf) -> np.ndarray:
+    if isinstance(buf, np.ndarray):
+        return np.ascontiguousarray(buf).view(np.uint8).reshape(-1)
+    return np.frombuffer(memoryview(buf), dtype=np.uint8)
+
+
+def join_documents(documents) -> Tuple[np.ndarray, np.ndarray]:
+    """``documents=`` of the bulk calls as (uint8 buffer, int64 doc_offsets): a ``(buf, doc_offsets)`` pair as it is, or an iterable
+    of ``bytes`` / ``str`` joined here (``str`` as its UTF-8 bytes)."""
+    if isinstance(documents, tuple) and len(documents) == 2 and not isinstance(documents[1], (bytes, bytearray, str)):
+        return _as_bytes_array(documents[0]), np.ascontiguousarray(documents[1], dtype=np.int64).reshape(-1)
+    if isinstance(documents, (bytes, bytearray, str)):
+        raise ValueError("documents is a (buf, doc_offsets) pair or a list of bytes / str, not one document")
+    docs = [d.encode("utf-8") if isinstance(d, str) else bytes(d) for d in documents]
+    doc_offsets = np.zeros(len(docs) + 1, dtype=np.int64)
+    np.cumsum(np.fromiter(map(len, docs), dtype=np.int64, count=len(docs)), out=doc_offsets[1:])
+    return np.frombuffer(b"".join(docs), dtype=np.uint8), doc_offsets
+
+
+def check_corpus(buf, item_offsets, doc_offsets, width) -> Tuple[np.ndarray, Optional[np.ndarray], np.ndarray, int]:
+    """The arrays of a corpus in their canonical types, checked; ``ValueError`` names what is wrong."""
+    width = _check_width(width)
+    buf = _as_bytes_array(buf)
+    doc_offsets = np.ascontiguousarray(doc_offsets, dtype=np.int64).reshape(-1)
+    n_items = buf.size
+    if item_offsets is not None:
+        item_offsets = np.ascontiguousarray(item_offsets, dtype=np.int64).reshape(-1)
+        if item_offsets.size < 1 or item_offsets[0] != 0 or item_offsets[-1] > buf.size or np.any(np.diff(item_offsets) < 0):
+            raise ValueError("byte_offsets must start at 0, never decrease and end inside buf")
+        n_items = item_offsets.size - 1
+    if doc_offsets.size < 1 or doc_offsets[0] != 0 or doc_offsets[-1] != n_items or np.any(np.diff(doc_offsets) < 0):
+        raise ValueError("the document offsets must start at 0, never decrease and end at the number of %s"
+                         % ("bytes of buf" if item_offsets is None else "tokens"))
+    return buf, item_offsets, doc_offsets, width
+
+
+def window_chunks(set_offsets: np.ndarray, max_docs: int, max_windows: int) -> Iterator[Tuple[int, int]]:
+    """(s, e) ranges of whole documents: at most ``max_docs`` of them and about ``max_windows`` windows (one document may exceed
+    that alone)."""
+    n, s = set_offsets.size - 1, 0
+    while s < n:
+        e = min(n, s + max_docs)
+        t0 = int(set_offsets[s])
+        if int(set_offsets[e]) - t0 > max_windows:
+            e = min(e, max(s + 1, int(np.searchsorted(set_offsets, t0 + max_windows, side="right")) - 1))
+        yield s, e
+        s = e
+
+
+def corpus_piece(buf, item_offsets, doc_offsets, s: int, e: int):
+    """Documents ``s .. e`` as a corpus of their own: (bytes, item offsets or None, doc offsets), offsets starting at 0."""
+    i0, i1 = int(doc_offsets[s]), int(doc_offsets[e])
+    local_docs = doc_offsets[s: e + 1] - i0
+    if item_offsets is None:
+        return buf[i0: i1], None, local_docs
+    b0 = int(item_offsets[i0])
+    return buf[b0: int(item_offsets[i1])], item_offsets[i0: i1 + 1] - b0, local_docs
+
+
+def host_shingles(buf, item_offsets, doc_offsets, width: int) -> List[List[bytes]]:
+    """The shingles of every document of a (checked) corpus, by :func:`byte_shingles` / :func:`token_shingles`."""
+    raw = buf.tobytes()
+    out = []
+    for d in range(doc_offsets.size - 1):
+        i0, i1 = int(doc_offsets[d]), int(doc_offsets[d + 1])
+        if item_offsets is None:
+            out.append(byte_shingles(raw[i0: i1], width))
+        else:
+            out.append(token_shingles([raw[int(item_offsets[i]): int(item_offsets[i + 1])] for i in range(i0, i1)], width))
+    return out
+
+
+def sha1_windows(buf, doc_offsets, width: int, item_offsets=None, bits: int = 32, gpu_mode: str = "detect") -> Tuple[np.ndarray, np.ndarray]:
+    """``(hashes, set_offsets)``: ``sha1_hash32`` (``bits=32``, uint32) or ``sha1_hash64`` (``bits=64``, uint64) of every shingle of
+    the corpus, document by document, and the CSR offsets of the documents into them (:func:`window_offsets`).  One kernel on the
+    device, one thread per window, nothing materialised; ``gpu_mode='disable'`` hashes the shingles of this module with hashlib."""
+    from datasketch_amd.hyperloglog import _use_gpu
+
+    if bits not in (32, 64):
+        raise ValueError("bits must be 32 or 64")
+    buf, item_offsets, doc_offsets, width = check_corpus(buf, item_offsets, doc_offsets, width)
+    if _use_gpu(gpu_mode):
+        return _native.context().sha1_windows(buf, doc_offsets, width, item_offsets, bits)
+    f = sha1_hash32 if bits == 32 else sha1_hash64
+    flat = [f(s) for doc in host_shingles(buf, item_offsets, doc_offsets, width) for s in doc]
+    return np.array(flat, dtype=np.uint32 if bits == 32 else np.uint64), window_offsets(doc_offsets, width)

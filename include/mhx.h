@@ -736,6 +736,48 @@ MHX_API_CC int mhx_cc_finish_dev(mhx_ctx *ctx, uint32_t *d_labels, int64_t n);
 MHX_API_CC int mhx_cc_pairs(mhx_ctx *ctx, const int64_t *pairs, int64_t n_pairs, const int32_t *counts, int32_t min_count, int64_t n,
                             uint32_t *labels, int64_t *invalid);
 
+/* ---- Shingles: the windows of a document hashed in place ------------------------------------------------------------------
+ * Not in the reference, which leaves shingling to the caller (`for i in range(len(d) - k + 1): m.update(d[i:i+k])`);
+ * datasketch_amd/shingle.py is the definition.  A corpus is one byte buffer and doc_offsets int64[n_docs + 1]; a window is `width`
+ * consecutive ITEMS of one document and never crosses into the next one.
+ *   byte mode  (item_offsets == NULL): an item is a byte; document d owns bytes doc_offsets[d] .. doc_offsets[d + 1]
+ *   token mode: item i is bytes[item_offsets[i] .. item_offsets[i + 1]) (int64[n_items + 1], the byte_offsets of
+ *              mhx_sha1_tokens); document d owns items doc_offsets[d] .. doc_offsets[d + 1]; a window is the contiguous byte range
+ *              from the start of its first token to the end of its last
+ * A document of m items has m - width + 1 windows, exactly one (the whole document) if 0 < m < width, none if m == 0.  Windows are
+ * numbered document by document: set_offsets int64[n_docs + 1], the prefix sums of those counts, are the CSR offsets that
+ * mhx_minhash_bulk_dev / mhx_hll_bulk_dev take with the window hashes as hv.  Nothing is materialised: the kernel reads the
+ * corpus where it lies, one SHA-1 per window, and touches no byte outside bytes[0 .. end of the last item) rounded out to aligned
+ * dwords that hold at least one such byte.
+ *
+ * Exported through MHX_API_SHINGLE (the same visibility as MHX_API), bound from _native._PROTOTYPES_SHINGLE; declared = bound =
+ * exported is checked in tests/test_shingle_host.py, the argument checks in tests/test_gpu_shingles.py. */
+#define MHX_API_SHINGLE __attribute__((visibility("default")))
+/* set_offsets of a corpus: pure host logic, no device.  width >= 1; doc_offsets non-decreasing. */
+MHX_API_SHINGLE int mhx_shingle_window_offsets(const int64_t *doc_offsets, int64_t n_docs, int64_t width, int64_t *set_offsets);
+/* d_out[t] = sha1_hash32 (MHX_U32) or sha1_hash64 (MHX_U64) of window t, n_windows = set_offsets[n_docs] of them.  The device
+ * arrays are TRUSTED: d_set_offsets must be what mhx_shingle_window_offsets gives for d_doc_offsets and width, and the item
+ * offsets must be non-decreasing -- nothing on the device checks them.  d_bytes may be NULL when every window is empty. */
+MHX_API_SHINGLE int mhx_sha1_windows_dev(mhx_ctx *ctx, const uint8_t *d_bytes, const int64_t *d_item_offsets,
+                                         const int64_t *d_doc_offsets, const int64_t *d_set_offsets, int64_t n_docs,
+                                         int64_t n_windows, int64_t width, int out_dtype, void *d_out);
+/* The host forms (blocking) check their input -- width >= 1; doc_offsets runs from 0 to n_items (the number of bytes in byte mode)
+ * and never decreases; item_offsets starts at 0 and never decreases, bytes holds item_offsets[n_items] bytes -- and compute the
+ * set offsets themselves.  n_docs == 0 is a no-op.  out: one hash per window, sized by the caller from
+ * mhx_shingle_window_offsets. */
+MHX_API_SHINGLE int mhx_sha1_windows(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items,
+                                     const int64_t *doc_offsets, int64_t n_docs, int64_t width, int out_dtype, void *out);
+/* Text in, signatures out: the twin of mhx_minhash_bulk_bytes_typed over windows -- the corpus goes up, the windows kernel and the
+ * MinHash kernel run, out [n_docs, K] of out_dtype comes back (MHX_U32 as in mhx_minhash_bulk_typed).  init as in
+ * mhx_minhash_bulk; a document without a window keeps its init row. */
+MHX_API_SHINGLE int mhx_minhash_bulk_windows_typed(mhx_perm *perm, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items,
+                                                   const int64_t *doc_offsets, int64_t n_docs, int64_t width, int hash_dtype,
+                                                   const uint64_t *init, int64_t init_stride, void *out, int out_dtype);
+/* The twin of mhx_hll_bulk_bytes over windows: uint8 registers [n_docs, 2^p]; p, hash_bits, init and init_stride as there. */
+MHX_API_SHINGLE int mhx_hll_bulk_windows(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items,
+                                         const int64_t *doc_offsets, int64_t n_docs, int64_t width, int32_t hash_bits, int32_t p,
+                                         const uint8_t *init, int64_t init_stride, uint8_t *out);
+
 /* ---- Multi-GPU: assemble the signature matrix (RCCL over xGMI) ----------------------------- */
 /* 128-byte RCCL unique id, created on rank 0 and distributed by the caller (env, file, socket). */
 #define MHX_COMM_ID_BYTES 128
