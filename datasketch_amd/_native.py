@@ -10,14 +10,14 @@ import ctypes
 import weakref
 import os
 import threading
-from typing import Optional
+from typing import Optional, Tuple
 
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("MHX_LIBRARY") or os.path.join(_HERE, "libmhx.so")  # MHX_LIBRARY: A/B builds (tools/)
 
-MHX_OK, MHX_ERR_NO_DEVICE, MHX_ERR_INVALID, MHX_ERR_HIP, MHX_ERR_OOM, MHX_ERR_UNSUPPORTED, MHX_ERR_COMM = range(7)
+MHX_OK, MHX_ERR_NO_DEVICE, MHX_ERR_INVALID, MHX_ERR_HIP, MHX_ERR_OOM, MHX_ERR_UNSUPPORTED, MHX_ERR_COMM, MHX_ERR_CAPACITY = range(8)
 MHX_U64, MHX_U32 = 0, 1
 MHX_TOPK_MAX = 64  # include/mhx.h: the longest list of the top-k Jaccard entries
 COMM_ID_BYTES = 128
@@ -187,6 +187,14 @@ _PROTOTYPES_SHINGLE = {
     "mhx_minhash_bulk_windows_typed": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _vp, _i64, _vp, _int],
     "mhx_hll_bulk_windows": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _i64, _vp],
 }
+# Entry points declared MHX_API_WORDS (text tokenised and normalised on the device): a seventh list for the same reason; declared =
+# bound = exported is checked in tests/test_words_host.py, the argument checks in tests/test_gpu_words.py.
+_PROTOTYPES_WORDS = {
+    "mhx_words_normalize_dev": [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
+    "mhx_words_normalize": [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)],
+    "mhx_minhash_bulk_words_typed": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _int, _vp, _i64, _vp, _int],
+    "mhx_hll_bulk_words": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp],
+}
 _RESTYPE = {"mhx_last_error": ctypes.c_char_p, "mhx_version": ctypes.c_char_p}
 
 EXPORTED_SYMBOLS = sorted(list(_PROTOTYPES) + list(_RESTYPE))
@@ -195,6 +203,7 @@ EXPORTED_SYMBOLS_BLOOM = sorted(_PROTOTYPES_BLOOM)
 EXPORTED_SYMBOLS_TOPK = sorted(_PROTOTYPES_TOPK)
 EXPORTED_SYMBOLS_CC = sorted(_PROTOTYPES_CC)
 EXPORTED_SYMBOLS_SHINGLE = sorted(_PROTOTYPES_SHINGLE)
+EXPORTED_SYMBOLS_WORDS = sorted(_PROTOTYPES_WORDS)
 
 
 try:  # CPython helper (csrc/pack_module.c): ~10 ns per token instead of ~180 in the interpreter
@@ -234,7 +243,8 @@ def load():
             )
             raise MhxError(_lib_error) from e
         for name, argtypes in (list(_PROTOTYPES.items()) + list(_PROTOTYPES_EXT.items()) + list(_PROTOTYPES_BLOOM.items())
-                               + list(_PROTOTYPES_TOPK.items()) + list(_PROTOTYPES_CC.items()) + list(_PROTOTYPES_SHINGLE.items())):
+                               + list(_PROTOTYPES_TOPK.items()) + list(_PROTOTYPES_CC.items()) + list(_PROTOTYPES_SHINGLE.items())
+                               + list(_PROTOTYPES_WORDS.items())):
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = _int
@@ -737,6 +747,80 @@ class Context:
         out = np.empty((n_docs, 1 << int(p)), dtype=np.uint8)
         check(self.lib.mhx_hll_bulk_windows(self.handle, _ptr(buf), _ptr(item_offsets), n_items, _ptr(doc_offsets), n_docs, int(width),
                                             int(hash_bits), int(p), _ptr(init), stride, _ptr(out)))
+        return out
+
+    @staticmethod
+    def _words_corpus(buf, doc_offsets, table):
+        """The arrays of a byte-mode corpus and its translate table as the C ABI takes them, and (n_bytes, n_docs)."""
+        buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
+        doc_offsets = np.ascontiguousarray(doc_offsets, dtype=np.int64).reshape(-1)
+        if doc_offsets.size < 1:
+            raise ValueError("doc_offsets has documents + 1 entries")
+        table = np.ascontiguousarray(table, dtype=np.uint8).reshape(-1)
+        if table.size != 256:
+            raise ValueError("the word table has 256 entries")
+        return buf, doc_offsets, table, buf.size, doc_offsets.size - 1
+
+    def words_normalize(self, buf, doc_offsets, table):
+        """(out_buf, item_offsets, word_doc_offsets): the normal form of a byte-mode corpus -- every word translated by ``table`` and
+        followed by one space -- as a ``packed=`` triple (mhx_words_normalize, host in, host out: a sizing call, then the call)."""
+        buf, doc_offsets, table, n_bytes, n_docs = self._words_corpus(buf, doc_offsets, table)
+        n_words, n_out = _i64(0), _i64(0)
+        check(self.lib.mhx_words_normalize(self.handle, _ptr(buf), n_bytes, _ptr(doc_offsets), n_docs, _ptr(table), None, 0, None, 0, None,
+                                           ctypes.byref(n_words), ctypes.byref(n_out)))
+        out = np.empty(n_out.value, dtype=np.uint8)
+        items = np.zeros(n_words.value + 1, dtype=np.int64)
+        word_docs = np.zeros(n_docs + 1, dtype=np.int64)
+        check(self.lib.mhx_words_normalize(self.handle, _ptr(buf), n_bytes, _ptr(doc_offsets), n_docs, _ptr(table), _ptr(out), out.size,
+                                           _ptr(items), items.size - 1, _ptr(word_docs), ctypes.byref(n_words), ctypes.byref(n_out)))
+        return out, items, word_docs
+
+    def words_normalize_dev(self, d_bytes: Optional[int], n_bytes: int, d_doc_offsets: Optional[int], n_docs: int, table,
+                            d_out_bytes: Optional[int] = None, cap_bytes: int = 0, d_item_offsets: Optional[int] = None, cap_words: int = 0,
+                            d_word_doc_offsets: Optional[int] = None) -> Tuple[int, int, int]:
+        """mhx_words_normalize_dev on device arrays (trusted): ``(status, n_words, n_out_bytes)``.  All three outputs ``None`` is the
+        sizing call; ``status`` is ``MHX_ERR_CAPACITY`` when a total exceeds its capacity (nothing was written) and ``MHX_OK``
+        otherwise; every other failure raises.  Blocks for the totals; the emit is enqueued."""
+        table = np.ascontiguousarray(table, dtype=np.uint8).reshape(-1)
+        if table.size != 256:
+            raise ValueError("the word table has 256 entries")
+        n_words, n_out = _i64(0), _i64(0)
+        rc = self.lib.mhx_words_normalize_dev(self.handle, _vp(d_bytes), int(n_bytes), _vp(d_doc_offsets), int(n_docs), _ptr(table),
+                                              _vp(d_out_bytes), int(cap_bytes), _vp(d_item_offsets), int(cap_words), _vp(d_word_doc_offsets),
+                                              ctypes.byref(n_words), ctypes.byref(n_out))
+        if rc != MHX_ERR_CAPACITY:
+            check(rc)
+        return rc, n_words.value, n_out.value
+
+    def minhash_bulk_words(self, permutations, buf, doc_offsets, width: int, table, init: Optional[np.ndarray] = None, bits: int = 32,
+                           out_dtype=np.uint64) -> np.ndarray:
+        """Raw text -> words -> w-word shingles -> sha1_hash32 / sha1_hash64 -> [n_docs, K] signatures, all on the device
+        (mhx_minhash_bulk_words_typed)."""
+        if bits not in (32, 64):
+            raise ValueError("bits must be 32 or 64")
+        perm = self.perm_handle(permutations)
+        k = len(permutations[0])
+        buf, doc_offsets, table, n_bytes, n_docs = self._words_corpus(buf, doc_offsets, table)
+        stride = 0
+        if init is not None:
+            init = np.ascontiguousarray(init, dtype=np.uint64)
+            if init.shape == (n_docs, k):
+                stride = k
+            elif init.shape != (k,):
+                raise ValueError("init must have shape (K,) or (n_docs, K)")
+        out = np.empty((n_docs, k), dtype=out_dtype)
+        check(self.lib.mhx_minhash_bulk_words_typed(perm, _ptr(buf), n_bytes, _ptr(doc_offsets), n_docs, _ptr(table), int(width),
+                                                    MHX_U32 if bits == 32 else MHX_U64, _ptr(init), stride, _ptr(out),
+                                                    MHX_U32 if np.dtype(out_dtype) == np.uint32 else MHX_U64))
+        return out
+
+    def hll_bulk_words(self, buf, doc_offsets, width: int, p: int, table, hash_bits: int = 32, init: Optional[np.ndarray] = None) -> np.ndarray:
+        """Raw text -> words -> w-word shingles -> sha1_hash32 / sha1_hash64 (``hash_bits``) -> uint8 [n_docs, 2**p] registers."""
+        buf, doc_offsets, table, n_bytes, n_docs = self._words_corpus(buf, doc_offsets, table)
+        init, stride = self._hll_init(init, n_docs, 1 << int(p))
+        out = np.empty((n_docs, 1 << int(p)), dtype=np.uint8)
+        check(self.lib.mhx_hll_bulk_words(self.handle, _ptr(buf), n_bytes, _ptr(doc_offsets), n_docs, _ptr(table), int(width), int(hash_bits),
+                                          int(p), _ptr(init), stride, _ptr(out)))
         return out
 
     def minhash_update_batch(self, permutations, hv: np.ndarray, hashvalues: np.ndarray) -> np.ndarray:

@@ -2424,6 +2424,200 @@ int mhx_hll_bulk_windows(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *item
     return s.fetch(out, p_out);
 }
 
+// ---- word shingles: text tokenised and normalised on the device (datasketch_amd/shingle.py is the definition) ---------------
+static int check_words(int64_t n_bytes, int64_t n_docs, const uint8_t *table) {
+    MHX_REQUIRE(n_bytes >= 0, "n_bytes must be >= 0");
+    MHX_REQUIRE(n_docs >= 0, "n_docs must be >= 0");
+    MHX_REQUIRE(table, "table is NULL");
+    MHX_REQUIRE(table[0] == 0, "table[0] must be 0: byte 0 is always a separator");
+    return MHX_OK;
+}
+
+// the host corpus of the host forms
+static int check_words_corpus(const uint8_t *bytes, int64_t n_bytes, const int64_t *doc_offsets, int64_t n_docs) {
+    MHX_REQUIRE(doc_offsets, "doc_offsets is NULL");
+    MHX_REQUIRE(bytes || n_bytes == 0, "bytes is NULL");
+    MHX_REQUIRE(doc_offsets[0] == 0 && doc_offsets[n_docs] == n_bytes, "doc_offsets must run from 0 to n_bytes");
+    for (int64_t d = 0; d < n_docs; ++d)
+        MHX_REQUIRE(doc_offsets[d + 1] >= doc_offsets[d], "doc_offsets must be non-decreasing (document %lld)", (long long)d);
+    return MHX_OK;
+}
+
+// what follows the count, for device and host forms alike: the sizing call, the capacities, the outputs
+static int check_words_outputs(const void *out_bytes, int64_t cap_bytes, const void *item_offsets, int64_t cap_words,
+                               const void *word_doc_offsets, int64_t n_words, int64_t n_out_bytes, Where where, bool *emit) {
+    *emit = false;
+    if (!out_bytes && !item_offsets && !word_doc_offsets) return MHX_OK;  // a sizing call
+    if (n_words > cap_words || n_out_bytes > cap_bytes)
+        return fail(MHX_ERR_CAPACITY, "the normal form has %lld words and %lld bytes; the outputs hold %lld and %lld", (long long)n_words,
+                    (long long)n_out_bytes, (long long)cap_words, (long long)cap_bytes);
+    MHX_REQUIRE_POINTERS(item_offsets && word_doc_offsets && (out_bytes || n_out_bytes == 0), where);
+    *emit = true;
+    return MHX_OK;
+}
+
+int mhx_words_normalize_dev(mhx_ctx *ctx, const uint8_t *d_bytes, int64_t n_bytes, const int64_t *d_doc_offsets, int64_t n_docs,
+                            const uint8_t *table, uint8_t *d_out_bytes, int64_t cap_bytes, int64_t *d_item_offsets, int64_t cap_words,
+                            int64_t *d_word_doc_offsets, int64_t *n_words, int64_t *n_out_bytes) {
+    MHX_ENTER(ctx, ctx);
+    MHX_REQUIRE(n_words && n_out_bytes, "n_words/n_out_bytes is NULL");
+    *n_words = *n_out_bytes = 0;
+    MHX_TRY(check_words(n_bytes, n_docs, table));
+    MHX_REQUIRE(cap_bytes >= 0 && cap_words >= 0, "cap_bytes and cap_words must be >= 0");
+    if (n_docs == 0) return MHX_OK;
+    MHX_REQUIRE_POINTERS(d_doc_offsets && (d_bytes || n_bytes == 0), kDevice);
+    MHX_TRY(ctx->activate());
+    MHX_TRY(mhx::launch_words_count(ctx, d_bytes, n_bytes, d_doc_offsets, n_docs, table, n_words, n_out_bytes));
+    bool emit = false;
+    MHX_TRY(check_words_outputs(d_out_bytes, cap_bytes, d_item_offsets, cap_words, d_word_doc_offsets, *n_words, *n_out_bytes, kDevice, &emit));
+    if (!emit) return MHX_OK;
+    return mhx::launch_words_emit(ctx, d_bytes, n_bytes, d_doc_offsets, n_docs, table, d_out_bytes, d_item_offsets, d_word_doc_offsets);
+}
+
+extern "C++" {
+namespace {
+
+// A host corpus staged and counted: bytes -> In; document offsets | word offsets of the documents | set offsets -> Offsets.
+// The caller then names where the text and its item offsets go (they are sized by the count) and calls emit().
+struct Words {
+    int64_t n_words = 0, n_out_bytes = 0, n_windows = 0;
+    uint8_t *d_bytes = nullptr;
+    int64_t *d_docs = nullptr, *d_wdocs = nullptr, *d_sets = nullptr;
+    std::vector<int64_t> wdocs, sets;  // (alive until the call has synchronised: they are uploaded from)
+
+    int count(mhx_ctx *ctx, const uint8_t *bytes, int64_t n_bytes, const int64_t *doc_offsets, int64_t n_docs, const uint8_t *table) {
+        Stage s(ctx);
+        const auto p_bytes = s.piece(Stage::In, (size_t)n_bytes);
+        if (n_bytes == 0) s.ask(Stage::In, 8);
+        const auto p_docs = s.piece(Stage::Offsets, sizeof(int64_t) * (size_t)(n_docs + 1)), p_wdocs = s.piece(Stage::Offsets, p_docs.bytes),
+                   p_sets = s.piece(Stage::Offsets, p_docs.bytes);
+        MHX_TRY(s.commit());
+        d_bytes = s.at<uint8_t>(p_bytes);
+        d_docs = s.at<int64_t>(p_docs);
+        d_wdocs = s.at<int64_t>(p_wdocs);
+        d_sets = s.at<int64_t>(p_sets);
+        MHX_TRY(s.upload(p_bytes, bytes));
+        MHX_TRY(s.upload(p_docs, doc_offsets));
+        return mhx::launch_words_count(ctx, d_bytes, n_bytes, d_docs, n_docs, table, &n_words, &n_out_bytes);
+    }
+
+    int emit(mhx_ctx *ctx, int64_t n_bytes, int64_t n_docs, const uint8_t *table, uint8_t *d_text, int64_t *d_items) {
+        return mhx::launch_words_emit(ctx, d_bytes, n_bytes, d_docs, n_docs, table, d_text, d_items, d_wdocs);
+    }
+
+    // the set offsets of the windows of `width` words: 8 bytes per document down, mhx_shingle_window_offsets, 8 bytes up.  Blocks.
+    int window_offsets(mhx_ctx *ctx, int64_t n_docs, int64_t width) {
+        wdocs.resize((size_t)n_docs + 1);
+        sets.resize((size_t)n_docs + 1);
+        const size_t bytes = sizeof(int64_t) * (size_t)(n_docs + 1);
+        MHX_HIP_CHECK(hipMemcpyAsync(wdocs.data(), d_wdocs, bytes, hipMemcpyDeviceToHost, ctx->stream));
+        MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
+        MHX_TRY(mhx_shingle_window_offsets(wdocs.data(), n_docs, width, sets.data()));
+        n_windows = sets[(size_t)n_docs];
+        MHX_HIP_CHECK(hipMemcpyAsync(d_sets, sets.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
+        return MHX_OK;
+    }
+};
+
+}  // namespace
+}  // extern "C++"
+
+int mhx_words_normalize(mhx_ctx *ctx, const uint8_t *bytes, int64_t n_bytes, const int64_t *doc_offsets, int64_t n_docs,
+                        const uint8_t *table, uint8_t *out_bytes, int64_t cap_bytes, int64_t *item_offsets, int64_t cap_words,
+                        int64_t *word_doc_offsets, int64_t *n_words, int64_t *n_out_bytes) {
+    MHX_ENTER(ctx, ctx);
+    MHX_REQUIRE(n_words && n_out_bytes, "n_words/n_out_bytes is NULL");
+    *n_words = *n_out_bytes = 0;
+    MHX_TRY(check_words(n_bytes, n_docs, table));
+    MHX_REQUIRE(cap_bytes >= 0 && cap_words >= 0, "cap_bytes and cap_words must be >= 0");
+    if (n_docs == 0) return MHX_OK;
+    MHX_TRY(check_words_corpus(bytes, n_bytes, doc_offsets, n_docs));
+    MHX_TRY(ctx->activate());
+    Words w;
+    MHX_TRY(w.count(ctx, bytes, n_bytes, doc_offsets, n_docs, table));
+    *n_words = w.n_words;
+    *n_out_bytes = w.n_out_bytes;
+    bool emit = false;
+    MHX_TRY(check_words_outputs(out_bytes, cap_bytes, item_offsets, cap_words, word_doc_offsets, w.n_words, w.n_out_bytes, kHost, &emit));
+    if (!emit) return MHX_OK;
+    Stage s(ctx);
+    const auto p_text = s.piece(Stage::Out, (size_t)w.n_out_bytes), p_items = s.piece(Stage::Out, sizeof(int64_t) * (size_t)(w.n_words + 1));
+    MHX_TRY(s.commit());
+    MHX_TRY(w.emit(ctx, n_bytes, n_docs, table, s.at<uint8_t>(p_text), s.at<int64_t>(p_items)));
+    if (w.n_out_bytes) MHX_TRY(s.download(out_bytes, p_text));
+    MHX_TRY(s.download(item_offsets, p_items));
+    MHX_HIP_CHECK(hipMemcpyAsync(word_doc_offsets, w.d_wdocs, sizeof(int64_t) * (size_t)(n_docs + 1), hipMemcpyDeviceToHost, ctx->stream));
+    return s.synchronize();
+}
+
+int mhx_minhash_bulk_words_typed(mhx_perm *perm, const uint8_t *bytes, int64_t n_bytes, const int64_t *doc_offsets, int64_t n_docs,
+                                 const uint8_t *table, int64_t width, int hash_dtype, const uint64_t *init, int64_t init_stride, void *out,
+                                 int out_dtype) {
+    MHX_ENTER(perm, perm->ctx);
+    MHX_TRY(check_windows(n_docs, width));
+    MHX_TRY(check_words(n_bytes, n_docs, table));
+    MHX_REQUIRE(hash_dtype == MHX_U32 || hash_dtype == MHX_U64, "hash_dtype must be MHX_U32 (sha1_hash32) or MHX_U64 (sha1_hash64)");
+    MHX_CHECK_DTYPE(out_dtype);
+    MHX_REQUIRE(init_stride == 0 || init_stride >= perm->num_perm, "init_stride must be 0 or >= num_perm");
+    if (n_docs == 0) return MHX_OK;
+    MHX_REQUIRE(out, "out is NULL");
+    MHX_TRY(check_words_corpus(bytes, n_bytes, doc_offsets, n_docs));
+    mhx_ctx *ctx = perm->ctx;
+    MHX_TRY(ctx->activate());
+    Words w;
+    MHX_TRY(w.count(ctx, bytes, n_bytes, doc_offsets, n_docs, table));
+    const int64_t k = perm->num_perm;
+    // Aux: init | window hashes (a document has no more windows than words) | the normalised text | its item offsets;  Out: signatures
+    Stage s(ctx);
+    const auto p_init = s.piece(Stage::Aux, init ? sizeof(uint64_t) * (size_t)(init_stride ? n_docs * init_stride : k) : 0);
+    const auto p_hv = s.piece(Stage::Aux, (hash_dtype == MHX_U32 ? 4 : 8) * (size_t)w.n_words);
+    const auto p_text = s.piece(Stage::Aux, (size_t)w.n_out_bytes), p_items = s.piece(Stage::Aux, sizeof(int64_t) * (size_t)(w.n_words + 1));
+    const auto p_out = s.piece(Stage::Out, (out_dtype == MHX_U32 ? 4 : 8) * (size_t)(n_docs * k));
+    MHX_TRY(s.commit());
+    MHX_TRY(s.upload(p_init, init));
+    MHX_TRY(w.emit(ctx, n_bytes, n_docs, table, s.at<uint8_t>(p_text), s.at<int64_t>(p_items)));
+    MHX_TRY(w.window_offsets(ctx, n_docs, width));
+    MHX_TRY(mhx::launch_sha1_windows(ctx, s.at<uint8_t>(p_text), s.at<int64_t>(p_items), w.d_wdocs, w.d_sets, n_docs, w.n_windows, width,
+                                     hash_dtype, s.at<void>(p_hv)));
+    MHX_TRY(mhx::launch_minhash_bulk(perm, s.at<void>(p_hv), hash_dtype, w.d_sets, 0, n_docs, w.n_windows, init ? s.at<uint64_t>(p_init) : nullptr,
+                                     init_stride, s.at<void>(p_out), out_dtype));
+    return s.fetch(out, p_out);
+}
+
+int mhx_hll_bulk_words(mhx_ctx *ctx, const uint8_t *bytes, int64_t n_bytes, const int64_t *doc_offsets, int64_t n_docs,
+                       const uint8_t *table, int64_t width, int32_t hash_bits, int32_t p, const uint8_t *init, int64_t init_stride,
+                       uint8_t *out) {
+    MHX_ENTER(ctx, ctx);
+    MHX_TRY(check_windows(n_docs, width));
+    MHX_TRY(check_words(n_bytes, n_docs, table));
+    MHX_TRY(check_hll(p, hash_bits));
+    const int64_t m = (int64_t)1 << p;
+    MHX_REQUIRE(init_stride == 0 || init_stride == m, "init_stride must be 0 (one shared row) or m = %lld", (long long)m);
+    if (n_docs == 0) return MHX_OK;
+    MHX_REQUIRE(out, "out is NULL");
+    MHX_TRY(check_words_corpus(bytes, n_bytes, doc_offsets, n_docs));
+    MHX_TRY(ctx->activate());
+    Words w;
+    MHX_TRY(w.count(ctx, bytes, n_bytes, doc_offsets, n_docs, table));
+    const int hash_dtype = hash_bits == 32 ? MHX_U32 : MHX_U64;
+    // Aux: init | window hashes | the normalised text | its item offsets;  Out: registers
+    Stage s(ctx);
+    Stage::Piece p_init{Stage::Aux, 0, 0};
+    if (init) p_init = s.piece(Stage::Aux, (size_t)(init_stride ? n_docs * m : m));
+    const auto p_hv = s.piece(Stage::Aux, (hash_bits == 32 ? 4 : 8) * (size_t)w.n_words);
+    const auto p_text = s.piece(Stage::Aux, (size_t)w.n_out_bytes), p_items = s.piece(Stage::Aux, sizeof(int64_t) * (size_t)(w.n_words + 1));
+    const auto p_out = s.piece(Stage::Out, (size_t)(n_docs * m));
+    MHX_TRY(s.commit());
+    MHX_TRY(s.upload(p_init, init));
+    MHX_TRY(w.emit(ctx, n_bytes, n_docs, table, s.at<uint8_t>(p_text), s.at<int64_t>(p_items)));
+    MHX_TRY(w.window_offsets(ctx, n_docs, width));
+    MHX_TRY(mhx::launch_sha1_windows(ctx, s.at<uint8_t>(p_text), s.at<int64_t>(p_items), w.d_wdocs, w.d_sets, n_docs, w.n_windows, width,
+                                     hash_dtype, s.at<void>(p_hv)));
+    MHX_TRY(mhx::launch_hll_bulk(ctx, s.at<void>(p_hv), hash_dtype, w.d_sets, 0, n_docs, w.n_windows, p, hash_bits,
+                                 init ? s.at<uint8_t>(p_init) : nullptr, init_stride, s.at<uint8_t>(p_out), nullptr));
+    return s.fetch(out, p_out);
+}
+
 // ---- MinHashLSHBloom: per-band Bloom filters (ref: datasketch/lsh_bloom.py) ----------------------------------------------
 static int check_bloom(int32_t bands, int64_t n_blocks) {
     MHX_REQUIRE(bands > 0 && bands <= (1 << 24), "bands must be in [1, 2^24]");

@@ -175,6 +175,12 @@ int launch_sha1_tokens(mhx_ctx *ctx, const uint8_t *d_bytes, const int64_t *d_of
 // shingles hashed in place: d_item_offsets == nullptr = windows of bytes; d_set_offsets = the first window of every document
 int launch_sha1_windows(mhx_ctx *ctx, const uint8_t *d_bytes, const int64_t *d_item_offsets, const int64_t *d_doc_offsets,
                         const int64_t *d_set_offsets, int64_t n_docs, int64_t n_windows, int64_t width, int out_dtype, void *d_out);
+// words_kernels.hip: a byte-mode corpus to its normal form (every word translated and followed by one space).  Count blocks (it
+// reads the two totals back); emit enqueues, for the corpus and table just counted, scratch[4] untouched in between.
+int launch_words_count(mhx_ctx *ctx, const uint8_t *d_bytes, int64_t n_bytes, const int64_t *d_doc_offsets, int64_t n_docs,
+                       const uint8_t *table, int64_t *n_words, int64_t *n_out_bytes);
+int launch_words_emit(mhx_ctx *ctx, const uint8_t *d_bytes, int64_t n_bytes, const int64_t *d_doc_offsets, int64_t n_docs,
+                      const uint8_t *table, uint8_t *d_out, int64_t *d_item_offsets, int64_t *d_word_doc_offsets);
 int launch_minhash_merge(mhx_ctx *ctx, const uint64_t *d_x, const uint64_t *d_y, int64_t count,
                          uint64_t *d_out);
 int launch_weighted(mhx_wgen *gen, const int64_t *d_indptr, const int32_t *d_indices,

@@ -401,7 +401,7 @@ class HyperLogLog:
 
     @staticmethod
     def bulk_registers(b=None, packed=None, p: int = 8, hashfunc: Callable = sha1_hash32, hash_bits: int = 32,
-                       gpu_mode: str = "detect", documents=None, shingle=None) -> np.ndarray:
+                       gpu_mode: str = "detect", documents=None, shingle=None, words=None) -> np.ndarray:
         """The int8 ``[N, 2**p]`` register matrix of a corpus of N sets, without creating N objects.
 
         ``b``: any iterable of token iterables; with ``hashfunc=prehashed`` also a 2-D integer array (fixed-length sets; uint32
@@ -415,7 +415,11 @@ class HyperLogLog:
         Text: ``documents=`` with ``shingle=k`` (a ``(buf, doc_offsets)`` pair or a list of ``bytes`` / ``str``; a ``str`` is shingled
         over its UTF-8 bytes) counts the distinct ``k``-byte shingles of every document, ``packed=`` with ``shingle=w`` its distinct
         shingles of ``w`` consecutive tokens -- the rules of ``MinHash.bulk_signatures`` and :mod:`datasketch_amd.shingle`.  On the
-        device the windows are hashed where they lie; ``hyperloglog.count_many`` turns the registers into counts."""
+        device the windows are hashed where they lie; ``hyperloglog.count_many`` turns the registers into counts.
+
+        Words: ``documents=`` with ``shingle=w`` and ``words=True`` (or a uint8[256] translate table) counts the distinct shingles of
+        ``w`` consecutive words of the normalised text (:func:`datasketch_amd.shingle.word_shingles`); on the device the raw text is
+        tokenised, normalised, windowed and hashed in one call."""
         _check_p(p)
         if hash_bits not in (32, 64):
             raise ValueError("hash_bits must be 32 or 64")
@@ -427,6 +431,9 @@ class HyperLogLog:
             raise ValueError("shingle= goes with documents= (bytes) or packed= (tokens), not with b")
         if documents is not None and shingle is None:
             raise ValueError("documents= needs shingle=k, the number of bytes per shingle")
+        table = _shingle.words_argument(words)
+        if table is not None and documents is None:
+            raise ValueError("words= goes with documents= and shingle=w, the number of words per shingle")
         device = _use_gpu(gpu_mode)
         sha1_bits = 32 if hashfunc is sha1_hash32 else 64 if hashfunc is sha1_hash64 else 0
         device_sha1 = device and sha1_bits == hash_bits
@@ -453,7 +460,20 @@ class HyperLogLog:
                 s = e
 
         blocks = []
-        if shingle is not None:
+        if table is not None:
+            # chunks by bytes: a document has no more windows than words and no more words than bytes
+            buf, doc_offsets = _shingle.join_documents(documents)
+            buf, _, doc_offsets, width = _shingle.check_corpus(buf, None, doc_offsets, shingle)
+            for s, e in _shingle.window_chunks(doc_offsets, max_sets, _BULK_CHUNK_TOKENS):
+                piece, _, local_docs = _shingle.corpus_piece(buf, None, doc_offsets, s, e)
+                if device_sha1:
+                    blocks.append(_native.context().hll_bulk_words(piece, local_docs, width, p, table, hash_bits))
+                    continue
+                sets = _shingle.host_word_shingles(piece, local_docs, width, table)
+                offsets = np.zeros(len(sets) + 1, dtype=np.int64)
+                np.cumsum(np.fromiter(map(len, sets), dtype=np.int64, count=len(sets)), out=offsets[1:])
+                blocks.append(from_hashes(_as_hashes([hashfunc(t) for d in sets for t in d], hash_bits, p), offsets, 0, e - s))
+        elif shingle is not None:
             if documents is not None:
                 buf, doc_offsets = _shingle.join_documents(documents)
                 item_offsets = None

@@ -25,6 +25,7 @@ from typing import Callable, Generator, Iterable, List, Optional, Tuple
 import numpy as np
 
 from datasketch_amd import _native, shingle
+from datasketch_amd.shingle import words_argument as _shingle_words_argument  # (bulk_signatures has a parameter called shingle)
 from datasketch_amd.hashfunc import prehashed, sha1_hash32, sha1_hash64
 
 # The size of a hash value in number of bytes (reference: datasketch/minhash.py:27)
@@ -366,7 +367,7 @@ class MinHash:
                 yield m._spawn(row.copy())
 
     @classmethod
-    def bulk_signatures(cls, b=None, out_dtype=np.uint64, packed=None, documents=None, shingle=None, **minhash_kwargs) -> np.ndarray:
+    def bulk_signatures(cls, b=None, out_dtype=np.uint64, packed=None, documents=None, shingle=None, words=None, **minhash_kwargs) -> np.ndarray:
         """Not in the reference: the ``[N, K]`` signature matrix of a corpus, without creating N
         Python objects.  ``b`` is any iterable of token iterables, or -- with ``hashfunc=prehashed``
         -- a 2-D integer array (fixed-length sets; a uint32 array is uploaded as it is) or a
@@ -387,7 +388,13 @@ class MinHash:
         ``packed=`` with ``shingle=w`` takes the sets to be the shingles of ``w`` consecutive tokens
         (:func:`datasketch_amd.shingle.token_shingles`).  With ``sha1_hash32`` / ``sha1_hash64`` on the device the windows are hashed
         where they lie -- nothing is materialised; any other ``hashfunc``, or ``gpu_mode='disable'``, is applied to the shingles of
-        :mod:`datasketch_amd.shingle` on the host."""
+        :mod:`datasketch_amd.shingle` on the host.
+
+        Words: ``documents=`` with ``shingle=w`` and ``words=True`` (or ``words=table``, a uint8[256] translate table, see
+        :func:`datasketch_amd.shingle.word_table`) takes the sets to be the shingles of ``w`` consecutive words of the normalised
+        text (:func:`datasketch_amd.shingle.word_shingles`: case folded, separators ignored, every word followed by one space).
+        On the device the raw text is tokenised, normalised, windowed and hashed in one call; the normal form never visits the
+        host."""
         if np.dtype(out_dtype) not in (np.dtype(np.uint64), np.dtype(np.uint32)):
             raise ValueError("out_dtype must be uint64 or uint32")
         if (b is not None) + (packed is not None) + (documents is not None) != 1:
@@ -396,10 +403,15 @@ class MinHash:
             raise ValueError("shingle= goes with documents= (bytes) or packed= (tokens), not with b")
         if documents is not None and shingle is None:
             raise ValueError("documents= needs shingle=k, the number of bytes per shingle")
+        table = _shingle_words_argument(words)
+        if table is not None and documents is None:
+            raise ValueError("words= goes with documents= and shingle=w, the number of words per shingle")
         m = cls(**minhash_kwargs)
         if np.dtype(out_dtype) == np.uint32 and not m.is_empty() and int(m.hashvalues.max()) > 0xFFFFFFFF:
             raise ValueError("initial hashvalues >= 2**32 do not fit uint32 signatures")
-        if shingle is not None:
+        if table is not None:
+            blocks = list(m._word_chunks(documents, shingle, table, np.dtype(out_dtype)))
+        elif shingle is not None:
             blocks = list(m._window_chunks(documents, packed, shingle, np.dtype(out_dtype)))
         else:
             blocks = list(m._packed_chunks(packed, np.dtype(out_dtype)) if packed is not None else m._bulk_chunks(b, np.dtype(out_dtype)))
@@ -467,6 +479,27 @@ class MinHash:
                 continue
             f = self.hashfunc
             sets = shingle.host_shingles(piece, local_items, local_docs, width)
+            offsets = np.zeros(len(sets) + 1, dtype=np.int64)
+            np.cumsum(np.fromiter(map(len, sets), dtype=np.int64, count=len(sets)), out=offsets[1:])
+            hv = _as_hash_array([f(t) for d in sets for t in d]).reshape(-1) if offsets[-1] else np.empty(0, dtype=np.uint64)
+            yield self._signatures_csr(hv, offsets, 0, e - s, init).astype(out_dtype, copy=False)
+
+    def _word_chunks(self, documents, width, table, out_dtype=np.uint64) -> Generator[np.ndarray, None, None]:
+        """Signature blocks of a corpus whose sets are the shingles of ``width`` words of ``documents``, in chunks of whole
+        documents.  Chunking is by bytes: a document has no more windows than words and no more words than bytes, so the bounds of
+        :meth:`_window_chunks` hold without knowing the word counts in advance."""
+        buf, doc_offsets = shingle.join_documents(documents)
+        buf, _, doc_offsets, width = shingle.check_corpus(buf, None, doc_offsets, width)
+        init = None if self.is_empty() else self.hashvalues
+        bits = 32 if self.hashfunc is sha1_hash32 else 64 if self.hashfunc is sha1_hash64 else 0
+        on_device = bits and self._use_gpu()
+        for s, e in shingle.window_chunks(doc_offsets, _BULK_CHUNK_SETS, _BULK_CHUNK_TOKENS):
+            piece, _, local_docs = shingle.corpus_piece(buf, None, doc_offsets, s, e)
+            if on_device:
+                yield _native.context().minhash_bulk_words(self.permutations, piece, local_docs, width, table, init, bits, out_dtype)
+                continue
+            f = self.hashfunc
+            sets = shingle.host_word_shingles(piece, local_docs, width, table)
             offsets = np.zeros(len(sets) + 1, dtype=np.int64)
             np.cumsum(np.fromiter(map(len, sets), dtype=np.int64, count=len(sets)), out=offsets[1:])
             hv = _as_hash_array([f(t) for d in sets for t in d]).reshape(-1) if offsets[-1] else np.empty(0, dtype=np.uint64)

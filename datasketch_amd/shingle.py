@@ -15,6 +15,12 @@ document and never crosses into the next document:
 
 A document of ``m`` items has ``m - width + 1`` windows, exactly one (the whole document) if ``0 < m < width`` and none if it is empty.
 Repeated windows stay in (min and max are idempotent); tokens may be empty, and a window of no bytes hashes as ``sha1(b"")``.
+
+Words: :func:`word_table`, :func:`words`, :func:`word_shingles` and :func:`normalize_words` define the w-word shingles of
+normalised text -- a 256-byte translate table says which bytes separate and what the others become, a word is a maximal run of
+non-separator bytes of one document, and the normal form of a byte-mode corpus is every word followed by exactly one space, as a
+token-mode corpus.  ``"the  cat"``, ``"The cat"`` and ``"the cat,"`` then give the same shingle.  The device kernels
+(csrc/words_kernels.hip) and ``words=`` of the bulk calls are written against these four.
 """
 from __future__ import annotations
 
@@ -63,6 +69,83 @@ def window_offsets(doc_offsets, width: int) -> np.ndarray:
     out = np.zeros(doc_offsets.size, dtype=np.int64)
     np.cumsum(np.where(items == 0, 0, np.where(items < width, 1, items - width + 1)), out=out[1:])
     return out
+
+
+# ---- words: the normal form of text, and its w-word shingles ------------------------------------------------------------------
+# These four ARE the definition too: words_kernels.hip, the gpu_mode='disable' paths of ``words=`` and the tests are written
+# against them.
+def word_table(lowercase: bool = True, extra: bytes = b"") -> np.ndarray:
+    """The default translate table, uint8[256]: ``table[c] == 0`` makes byte ``c`` a separator, any other value is the byte emitted
+    for ``c``.  Word bytes are ``0-9 A-Z a-z _``, every byte ``>= 0x80`` (UTF-8 letters stay inside words) and the bytes of
+    ``extra``; with ``lowercase``, ``A-Z`` map to ``a-z`` and every other word byte to itself.  Byte 0 is always a separator."""
+    extra = bytes(extra)
+    if 0 in extra:
+        raise ValueError("byte 0 is always a separator: it cannot be in extra")
+    table = np.zeros(256, dtype=np.uint8)
+    for c in list(b"0123456789ABCDEFGHIJKLMNOPQRSTUVWXYZabcdefghijklmnopqrstuvwxyz_") + list(range(0x80, 0x100)) + list(extra):
+        table[c] = c
+    if lowercase:
+        table[ord("A"): ord("Z") + 1] = np.arange(ord("a"), ord("z") + 1, dtype=np.uint8)
+    return table
+
+
+def check_table(table) -> np.ndarray:
+    """``table`` (None: the default) as a checked uint8[256]; ``ValueError`` unless it is one with ``table[0] == 0``."""
+    if table is None:
+        return word_table()
+    t = np.asarray(table)
+    if t.dtype != np.uint8 or t.shape != (256,):
+        raise ValueError("a word table is a uint8 array of 256 entries")
+    if t[0] != 0:
+        raise ValueError("table[0] must be 0: byte 0 is always a separator")
+    return np.ascontiguousarray(t)
+
+
+def words(doc, table=None) -> List[bytes]:
+    """The words of ``doc``: its maximal runs of non-separator bytes, translated."""
+    table = check_table(table)
+    return [w for w in bytes(doc).translate(table.tobytes()).split(b"\0") if w]
+
+
+def word_shingles(doc, w: int, table=None) -> List[bytes]:
+    """The shingles of ``w`` consecutive words of ``doc``, every word followed by exactly one space -- the last one included -- so
+    that a shingle depends on its words alone, never on the separators that stood between them."""
+    return token_shingles([x + b" " for x in words(doc, table)], w)
+
+
+def normalize_words(buf, doc_offsets, table=None, gpu_mode: str = "detect") -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """``(out_buf, item_offsets, word_doc_offsets)``: the normal form of a byte-mode corpus as a ``packed=`` triple.  ``out_buf`` is
+    every word followed by one space; item ``i`` (``item_offsets``, int64[words + 1]) is word ``i`` with its space;
+    ``word_doc_offsets`` (int64[documents + 1]) counts in words.  A word never crosses a document boundary.  Fed to ``packed=,
+    shingle=w`` it gives :func:`word_shingles`.  One scan-and-compact pass on the device; ``gpu_mode='disable'`` builds it from
+    :func:`words`."""
+    from datasketch_amd.hyperloglog import _use_gpu
+
+    table = check_table(table)
+    buf, _, doc_offsets, _ = check_corpus(buf, None, doc_offsets, 1)
+    if _use_gpu(gpu_mode):
+        return _native.context().words_normalize(buf, doc_offsets, table)
+    raw = buf.tobytes()
+    per_doc = [words(raw[int(doc_offsets[d]): int(doc_offsets[d + 1])], table) for d in range(doc_offsets.size - 1)]
+    flat = [x + b" " for doc in per_doc for x in doc]
+    item_offsets = np.zeros(len(flat) + 1, dtype=np.int64)
+    np.cumsum(np.fromiter(map(len, flat), dtype=np.int64, count=len(flat)), out=item_offsets[1:])
+    word_doc_offsets = np.zeros(len(per_doc) + 1, dtype=np.int64)
+    np.cumsum(np.fromiter(map(len, per_doc), dtype=np.int64, count=len(per_doc)), out=word_doc_offsets[1:])
+    return np.frombuffer(b"".join(flat), dtype=np.uint8), item_offsets, word_doc_offsets
+
+
+def words_argument(words_arg) -> Optional[np.ndarray]:
+    """``words=`` of the bulk calls: None / False = no word shingles, True = the default table, anything else = a user table."""
+    if words_arg is None or words_arg is False:
+        return None
+    return check_table(None if words_arg is True else words_arg)
+
+
+def host_word_shingles(buf, doc_offsets, width: int, table) -> List[List[bytes]]:
+    """The word shingles of every document of a (checked) byte-mode corpus, by :func:`word_shingles`."""
+    raw = buf.tobytes()
+    return [word_shingles(raw[int(doc_offsets[d]): int(doc_offsets[d + 1])], width, table) for d in range(doc_offsets.size - 1)]
 
 
 # ---- what MinHash.bulk_signatures, HyperLogLog.bulk_registers and sha1_windows share ---------------------------------------

@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
 """Near-duplicate detection from raw text: documents in, clusters out, no tokens built on the host.
 
-    python examples/near_duplicate_text.py [--docs 20000] [--shingle 9] [--gpu-mode detect]
+    python examples/near_duplicate_text.py [--docs 20000] [--shingle 9] [--words 0] [--gpu-mode detect]
 
 1. ``MinHash.bulk_signatures(documents=..., shingle=k)`` -- one signature row per document over its k-byte shingles.  On the
    device every window is hashed where it lies in the text (``sha1_windows_kernel``): nothing like
    ``for i in range(len(d) - k + 1): m.update(d[i:i+k])`` runs, and no copy of the corpus per shingle byte is made;
 2. ``HyperLogLog.bulk_registers(documents=..., shingle=k)`` + ``count_many`` -- the number of distinct shingles per document;
 3. ``lsh_bulk.candidate_pairs`` / ``jaccard_pairs`` / ``duplicate_clusters`` -- the chain of examples/near_duplicates.py.
+
+``--words w`` shingles over ``w`` consecutive *words* of the normalised text instead (``words=True``: case folded, punctuation and runs
+of white space ignored); the raw text is tokenised and normalised on the device too (``words_kernels.hip``).
 
 With ``--gpu-mode disable`` everything runs on the host paths and gives the same answer.
 """
@@ -51,6 +54,7 @@ def main(argv=None) -> dict:
     ap = argparse.ArgumentParser()
     ap.add_argument("--docs", type=int, default=20_000)
     ap.add_argument("--shingle", type=int, default=9)
+    ap.add_argument("--words", type=int, default=0, help="shingle over this many words of the normalised text, not over bytes")
     ap.add_argument("--num-perm", type=int, default=128)
     ap.add_argument("--bands", type=int, default=32)
     ap.add_argument("--rows", type=int, default=4)
@@ -60,13 +64,14 @@ def main(argv=None) -> dict:
 
     docs, truth = synthetic_text(args.docs)
     t0 = time.perf_counter()
-    sig = MinHash.bulk_signatures(documents=docs, shingle=args.shingle, num_perm=args.num_perm, seed=1, gpu_mode=args.gpu_mode)
+    width, how = (args.words, {"words": True}) if args.words else (args.shingle, {})
+    sig = MinHash.bulk_signatures(documents=docs, shingle=width, num_perm=args.num_perm, seed=1, gpu_mode=args.gpu_mode, **how)
     t1 = time.perf_counter()
-    reg = HyperLogLog.bulk_registers(documents=docs, shingle=args.shingle, p=8, gpu_mode=args.gpu_mode)
+    reg = HyperLogLog.bulk_registers(documents=docs, shingle=width, p=8, gpu_mode=args.gpu_mode, **how)
     distinct = hyperloglog.count_many(reg, gpu_mode=args.gpu_mode)
     t2 = time.perf_counter()
     n_bytes = sum(map(len, docs))
-    print(f"{len(docs)} documents, {n_bytes / 1e6:.1f} MB of text, {args.shingle}-byte shingles -> signatures {t1 - t0:.3f} s; "
+    print(f"{len(docs)} documents, {n_bytes / 1e6:.1f} MB of text, {width}-{'word' if args.words else 'byte'} shingles -> signatures {t1 - t0:.3f} s; "
           f"distinct shingles per document {t2 - t1:.3f} s (median {np.median(distinct):.0f})")
     pairs = lsh_bulk.candidate_pairs(sig, args.bands, args.rows, gpu_mode=args.gpu_mode)
     est = lsh_bulk.jaccard_pairs(sig, pairs, gpu_mode=args.gpu_mode)

@@ -45,7 +45,9 @@ enum {
     MHX_ERR_HIP = 3,         /* a HIP runtime call failed                                         */
     MHX_ERR_OOM = 4,         /* device allocation failed                                          */
     MHX_ERR_UNSUPPORTED = 5, /* valid request outside what this build implements                  */
-    MHX_ERR_COMM = 6         /* RCCL failure                                                      */
+    MHX_ERR_COMM = 6,        /* RCCL failure                                                      */
+    MHX_ERR_CAPACITY = 7     /* the caller's output arrays are too small; the sizes needed were
+                                stored and nothing was written (mhx_words_normalize*)             */
 };
 
 /* element types of token / signature buffers */
@@ -777,6 +779,49 @@ MHX_API_SHINGLE int mhx_minhash_bulk_windows_typed(mhx_perm *perm, const uint8_t
 MHX_API_SHINGLE int mhx_hll_bulk_windows(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items,
                                          const int64_t *doc_offsets, int64_t n_docs, int64_t width, int32_t hash_bits, int32_t p,
                                          const uint8_t *init, int64_t init_stride, uint8_t *out);
+
+/* ---- Word shingles: text tokenised and normalised on the device -----------------------------------------------------------
+ * datasketch_amd/shingle.py (word_table, words, word_shingles, normalize_words) is the definition.  table is a 256-byte translate
+ * table on the HOST: table[c] == 0 makes byte c a separator, any other value is the byte emitted for c; table[0] must be 0.  A
+ * word is a maximal run of non-separator bytes inside one document of a byte-mode corpus (bytes, doc_offsets int64[n_docs + 1]).
+ * The normal form of the corpus is a token-mode corpus, the `packed=` triple of the shingle entry points:
+ *   out_bytes         every word, translated, followed by one 0x20 -- the last word of a document included
+ *   item_offsets      int64[n_words + 1]: item i is word i with its space
+ *   word_doc_offsets  int64[n_docs + 1], in words: document d owns words word_doc_offsets[d] .. word_doc_offsets[d + 1]
+ * so windows of w items of it are the w-word shingles, whatever separators stood between the words.
+ *
+ * The capacity protocol of the two normalize entries: the call counts first and ALWAYS stores *n_words and *n_out_bytes (blocking:
+ * the totals are read back).  cap_bytes is the number of bytes out_bytes holds, cap_words the number of WORDS item_offsets holds
+ * (it has cap_words + 1 entries); word_doc_offsets always has n_docs + 1.  With all three outputs NULL the call is a sizing call
+ * and returns MHX_OK.  Otherwise, when n_words > cap_words or n_out_bytes > cap_bytes, nothing is written to any output and the
+ * call returns MHX_ERR_CAPACITY (no older code means "your arrays are too small": MHX_ERR_OOM is about device allocations and
+ * maps to MemoryError).  Otherwise it emits: exactly n_out_bytes bytes, n_words + 1 and n_docs + 1 entries.  n_docs == 0 is a no-op
+ * (the totals are 0).  The kernels touch no input byte outside bytes[0 .. n_bytes) rounded out to aligned dwords that hold at
+ * least one such byte.
+ *
+ * Exported through MHX_API_WORDS (the same visibility as MHX_API), bound from _native._PROTOTYPES_WORDS; declared = bound =
+ * exported is checked in tests/test_words_host.py, the argument checks in tests/test_gpu_words.py. */
+#define MHX_API_WORDS __attribute__((visibility("default")))
+/* Device arrays in and out; they are TRUSTED (d_doc_offsets must run from 0 to n_bytes and never decrease). */
+MHX_API_WORDS int mhx_words_normalize_dev(mhx_ctx *ctx, const uint8_t *d_bytes, int64_t n_bytes, const int64_t *d_doc_offsets,
+                                          int64_t n_docs, const uint8_t *table, uint8_t *d_out_bytes, int64_t cap_bytes,
+                                          int64_t *d_item_offsets, int64_t cap_words, int64_t *d_word_doc_offsets, int64_t *n_words,
+                                          int64_t *n_out_bytes);
+/* Host arrays in and out, checked: doc_offsets runs from 0 to n_bytes and never decreases, table is non-NULL with table[0] == 0;
+ * MHX_ERR_INVALID otherwise. */
+MHX_API_WORDS int mhx_words_normalize(mhx_ctx *ctx, const uint8_t *bytes, int64_t n_bytes, const int64_t *doc_offsets, int64_t n_docs,
+                                      const uint8_t *table, uint8_t *out_bytes, int64_t cap_bytes, int64_t *item_offsets,
+                                      int64_t cap_words, int64_t *word_doc_offsets, int64_t *n_words, int64_t *n_out_bytes);
+/* Raw text in, word-shingle signatures out: the twins of mhx_minhash_bulk_windows_typed and mhx_hll_bulk_windows.  The corpus goes
+ * up once, is normalised on the device, and the normal form goes straight into the windows kernel in token mode (width words per
+ * window) and the MinHash / HyperLogLog kernels; the normalised text and its item offsets never visit the host.  The other
+ * arguments as in the twins; checked like mhx_words_normalize. */
+MHX_API_WORDS int mhx_minhash_bulk_words_typed(mhx_perm *perm, const uint8_t *bytes, int64_t n_bytes, const int64_t *doc_offsets,
+                                               int64_t n_docs, const uint8_t *table, int64_t width, int hash_dtype,
+                                               const uint64_t *init, int64_t init_stride, void *out, int out_dtype);
+MHX_API_WORDS int mhx_hll_bulk_words(mhx_ctx *ctx, const uint8_t *bytes, int64_t n_bytes, const int64_t *doc_offsets, int64_t n_docs,
+                                     const uint8_t *table, int64_t width, int32_t hash_bits, int32_t p, const uint8_t *init,
+                                     int64_t init_stride, uint8_t *out);
 
 /* ---- Multi-GPU: assemble the signature matrix (RCCL over xGMI) ----------------------------- */
 /* 128-byte RCCL unique id, created on rank 0 and distributed by the caller (env, file, socket). */
