@@ -598,15 +598,7 @@ class Context:
                 raise ValueError("offsets run past the token array")
         elif fixed_len * n_sets > hv.size:
             raise ValueError("token array shorter than n_sets*fixed_len")
-        stride = 0
-        if init is not None:
-            init = np.ascontiguousarray(init, dtype=np.uint64)
-            if init.shape == (k,):
-                stride = 0
-            elif init.shape == (n_sets, k):
-                stride = k
-            else:
-                raise ValueError("init must have shape (K,) or (n_sets, K)")
+        init, stride = self._minhash_init(init, n_sets, k)
         if out is None:
             out = np.empty((n_sets, k), dtype=out_dtype)
         elif out.shape != (n_sets, k) or not out.flags.c_contiguous:
@@ -654,46 +646,71 @@ class Context:
             return None
         return np.frombuffer(packed[0], dtype=np.uint64), np.frombuffer(packed[1], dtype=np.int64)
 
+    # -- text to sketches: three sources (packed byte tokens, windows over bytes or tokens, words of raw text) into MinHash
+    # signatures or HyperLogLog registers.  Each method marshals its source's arrays and its sink's init and out; the C side
+    # (mhx_api.hip, "text to sketches") stages the source and hands its hashes to the sink.
+    @staticmethod
+    def _hash_code(bits: int) -> int:
+        """MHX_U32 (sha1_hash32) or MHX_U64 (sha1_hash64)."""
+        if bits not in (32, 64):
+            raise ValueError("bits must be 32 or 64")
+        return MHX_U32 if bits == 32 else MHX_U64
+
+    @staticmethod
+    def _minhash_init(init, n_sets: int, k: int):
+        """(init as the C ABI takes it, init_stride): one row for all sets or a row per set."""
+        if init is None:
+            return None, 0
+        init = np.ascontiguousarray(init, dtype=np.uint64)
+        if init.shape == (k,):
+            return init, 0
+        if init.shape == (n_sets, k):
+            return init, k
+        raise ValueError("init must have shape (K,) or (n_sets, K)")
+
+    @staticmethod
+    def _bytes_and_offsets(buf, *offsets):
+        """A byte buffer and its offset arrays as the C ABI takes them: flat, contiguous, uint8 and int64."""
+        out = [np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)]
+        for o in offsets:
+            out.append(np.ascontiguousarray(o, dtype=np.int64).reshape(-1))
+        return out
+
     def sha1_tokens(self, buf: np.ndarray, byte_offsets: np.ndarray, bits: int = 32) -> np.ndarray:
         """sha1_hash32 / sha1_hash64 of every token of a packed byte corpus (host in, host out)."""
         n = byte_offsets.size - 1
         out = np.empty(n, dtype=np.uint32 if bits == 32 else np.uint64)
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        byte_offsets = np.ascontiguousarray(byte_offsets, dtype=np.int64)
+        buf, byte_offsets = self._bytes_and_offsets(buf, byte_offsets)
         check(self.lib.mhx_sha1_tokens(self.handle, _ptr(buf), _ptr(byte_offsets), n, MHX_U32 if bits == 32 else MHX_U64, _ptr(out)))
         return out
 
     def minhash_bulk_bytes(self, permutations, buf: np.ndarray, byte_offsets: np.ndarray, set_offsets: np.ndarray,
-                           init: Optional[np.ndarray] = None, bits: int = 32) -> np.ndarray:
-        """Raw byte tokens -> sha1_hash32 (``bits=32``) or sha1_hash64 (``bits=64``) -> [n_sets, K] uint64
-        signatures, all on the device."""
-        if bits not in (32, 64):
-            raise ValueError("bits must be 32 or 64")
+                           init: Optional[np.ndarray] = None, bits: int = 32, out_dtype=np.uint64) -> np.ndarray:
+        """Raw byte tokens -> sha1_hash32 (``bits=32``) or sha1_hash64 (``bits=64``) -> [n_sets, K] signatures, all on the
+        device.  (This entry writes uint64; any other ``out_dtype`` is a conversion here.)"""
+        code = self._hash_code(bits)
         perm = self.perm_handle(permutations)
         k = len(permutations[0])
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        byte_offsets = np.ascontiguousarray(byte_offsets, dtype=np.int64)
-        set_offsets = np.ascontiguousarray(set_offsets, dtype=np.int64)
+        buf, byte_offsets, set_offsets = self._bytes_and_offsets(buf, byte_offsets, set_offsets)
         n_sets, n_tokens = set_offsets.size - 1, byte_offsets.size - 1
-        stride = 0
-        if init is not None:
-            init = np.ascontiguousarray(init, dtype=np.uint64)
-            if init.shape == (n_sets, k):
-                stride = k
-            elif init.shape != (k,):
-                raise ValueError("init must have shape (K,) or (n_sets, K)")
+        init, stride = self._minhash_init(init, n_sets, k)
         out = np.empty((n_sets, k), dtype=np.uint64)
-        check(self.lib.mhx_minhash_bulk_bytes_typed(perm, _ptr(buf), _ptr(byte_offsets), n_tokens, MHX_U32 if bits == 32 else MHX_U64,
-                                                    _ptr(set_offsets), n_sets, _ptr(init), stride, _ptr(out)))
-        return out
+        check(self.lib.mhx_minhash_bulk_bytes_typed(perm, _ptr(buf), _ptr(byte_offsets), n_tokens, code, _ptr(set_offsets), n_sets, _ptr(init),
+                                                    stride, _ptr(out)))
+        return out.astype(out_dtype, copy=False)
+
+    @staticmethod
+    def _documents(buf, doc_offsets):
+        """What the windows and the words corpus share: the bytes and the document offsets, which hold at least the leading 0."""
+        buf, doc_offsets = Context._bytes_and_offsets(buf, doc_offsets)
+        if doc_offsets.size < 1:
+            raise ValueError("doc_offsets has documents + 1 entries")
+        return buf, doc_offsets
 
     @staticmethod
     def _windows_corpus(buf, item_offsets, doc_offsets):
         """The three arrays of a shingle corpus as the C ABI takes them, and (n_items, n_docs)."""
-        buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
-        doc_offsets = np.ascontiguousarray(doc_offsets, dtype=np.int64).reshape(-1)
-        if doc_offsets.size < 1:
-            raise ValueError("doc_offsets has documents + 1 entries")
+        buf, doc_offsets = Context._documents(buf, doc_offsets)
         if item_offsets is None:
             return buf, None, doc_offsets, buf.size, doc_offsets.size - 1
         item_offsets = np.ascontiguousarray(item_offsets, dtype=np.int64).reshape(-1)
@@ -703,13 +720,11 @@ class Context:
 
     def sha1_windows(self, buf, doc_offsets, width: int, item_offsets=None, bits: int = 32):
         """(sha1_hash32 / sha1_hash64 of every shingle of a corpus, set_offsets): mhx_sha1_windows (host in, host out)."""
-        if bits not in (32, 64):
-            raise ValueError("bits must be 32 or 64")
+        code = self._hash_code(bits)
         buf, item_offsets, doc_offsets, n_items, n_docs = self._windows_corpus(buf, item_offsets, doc_offsets)
         set_offsets = window_offsets(doc_offsets, width)
         out = np.empty(int(set_offsets[-1]), dtype=np.uint32 if bits == 32 else np.uint64)
-        check(self.lib.mhx_sha1_windows(self.handle, _ptr(buf), _ptr(item_offsets), n_items, _ptr(doc_offsets), n_docs, int(width),
-                                        MHX_U32 if bits == 32 else MHX_U64, _ptr(out)))
+        check(self.lib.mhx_sha1_windows(self.handle, _ptr(buf), _ptr(item_offsets), n_items, _ptr(doc_offsets), n_docs, int(width), code, _ptr(out)))
         return out, set_offsets
 
     def sha1_windows_dev(self, d_bytes: Optional[int], d_item_offsets: Optional[int], d_doc_offsets: Optional[int], d_set_offsets: Optional[int],
@@ -721,22 +736,14 @@ class Context:
     def minhash_bulk_windows(self, permutations, buf, doc_offsets, width: int, item_offsets=None, init: Optional[np.ndarray] = None,
                              bits: int = 32, out_dtype=np.uint64) -> np.ndarray:
         """Text -> shingles -> sha1_hash32 / sha1_hash64 -> [n_docs, K] signatures, all on the device (mhx_minhash_bulk_windows_typed)."""
-        if bits not in (32, 64):
-            raise ValueError("bits must be 32 or 64")
+        code = self._hash_code(bits)
         perm = self.perm_handle(permutations)
         k = len(permutations[0])
         buf, item_offsets, doc_offsets, n_items, n_docs = self._windows_corpus(buf, item_offsets, doc_offsets)
-        stride = 0
-        if init is not None:
-            init = np.ascontiguousarray(init, dtype=np.uint64)
-            if init.shape == (n_docs, k):
-                stride = k
-            elif init.shape != (k,):
-                raise ValueError("init must have shape (K,) or (n_docs, K)")
+        init, stride = self._minhash_init(init, n_docs, k)
         out = np.empty((n_docs, k), dtype=out_dtype)
-        check(self.lib.mhx_minhash_bulk_windows_typed(perm, _ptr(buf), _ptr(item_offsets), n_items, _ptr(doc_offsets), n_docs, int(width),
-                                                      MHX_U32 if bits == 32 else MHX_U64, _ptr(init), stride, _ptr(out),
-                                                      MHX_U32 if np.dtype(out_dtype) == np.uint32 else MHX_U64))
+        check(self.lib.mhx_minhash_bulk_windows_typed(perm, _ptr(buf), _ptr(item_offsets), n_items, _ptr(doc_offsets), n_docs, int(width), code,
+                                                      _ptr(init), stride, _ptr(out), MHX_U32 if np.dtype(out_dtype) == np.uint32 else MHX_U64))
         return out
 
     def hll_bulk_windows(self, buf, doc_offsets, width: int, p: int, item_offsets=None, hash_bits: int = 32,
@@ -752,10 +759,7 @@ class Context:
     @staticmethod
     def _words_corpus(buf, doc_offsets, table):
         """The arrays of a byte-mode corpus and its translate table as the C ABI takes them, and (n_bytes, n_docs)."""
-        buf = np.ascontiguousarray(buf, dtype=np.uint8).reshape(-1)
-        doc_offsets = np.ascontiguousarray(doc_offsets, dtype=np.int64).reshape(-1)
-        if doc_offsets.size < 1:
-            raise ValueError("doc_offsets has documents + 1 entries")
+        buf, doc_offsets = Context._documents(buf, doc_offsets)
         table = np.ascontiguousarray(table, dtype=np.uint8).reshape(-1)
         if table.size != 256:
             raise ValueError("the word table has 256 entries")
@@ -796,22 +800,14 @@ class Context:
                            out_dtype=np.uint64) -> np.ndarray:
         """Raw text -> words -> w-word shingles -> sha1_hash32 / sha1_hash64 -> [n_docs, K] signatures, all on the device
         (mhx_minhash_bulk_words_typed)."""
-        if bits not in (32, 64):
-            raise ValueError("bits must be 32 or 64")
+        code = self._hash_code(bits)
         perm = self.perm_handle(permutations)
         k = len(permutations[0])
         buf, doc_offsets, table, n_bytes, n_docs = self._words_corpus(buf, doc_offsets, table)
-        stride = 0
-        if init is not None:
-            init = np.ascontiguousarray(init, dtype=np.uint64)
-            if init.shape == (n_docs, k):
-                stride = k
-            elif init.shape != (k,):
-                raise ValueError("init must have shape (K,) or (n_docs, K)")
+        init, stride = self._minhash_init(init, n_docs, k)
         out = np.empty((n_docs, k), dtype=out_dtype)
-        check(self.lib.mhx_minhash_bulk_words_typed(perm, _ptr(buf), n_bytes, _ptr(doc_offsets), n_docs, _ptr(table), int(width),
-                                                    MHX_U32 if bits == 32 else MHX_U64, _ptr(init), stride, _ptr(out),
-                                                    MHX_U32 if np.dtype(out_dtype) == np.uint32 else MHX_U64))
+        check(self.lib.mhx_minhash_bulk_words_typed(perm, _ptr(buf), n_bytes, _ptr(doc_offsets), n_docs, _ptr(table), int(width), code,
+                                                    _ptr(init), stride, _ptr(out), MHX_U32 if np.dtype(out_dtype) == np.uint32 else MHX_U64))
         return out
 
     def hll_bulk_words(self, buf, doc_offsets, width: int, p: int, table, hash_bits: int = 32, init: Optional[np.ndarray] = None) -> np.ndarray:
@@ -1324,9 +1320,7 @@ class Context:
     def hll_bulk_bytes(self, buf: np.ndarray, byte_offsets: np.ndarray, set_offsets: np.ndarray, p: int, hash_bits: int = 32,
                        init: Optional[np.ndarray] = None) -> np.ndarray:
         """Packed byte tokens -> sha1_hash32 / sha1_hash64 (``hash_bits``) -> uint8 [n_sets, 2**p] registers, all on the device."""
-        buf = np.ascontiguousarray(buf, dtype=np.uint8)
-        byte_offsets = np.ascontiguousarray(byte_offsets, dtype=np.int64)
-        set_offsets = np.ascontiguousarray(set_offsets, dtype=np.int64)
+        buf, byte_offsets, set_offsets = self._bytes_and_offsets(buf, byte_offsets, set_offsets)
         n_sets, n_tokens = set_offsets.size - 1, byte_offsets.size - 1
         init, stride = self._hll_init(init, n_sets, 1 << int(p))
         out = np.empty((n_sets, 1 << int(p)), dtype=np.uint8)

@@ -1000,24 +1000,88 @@ int mhx_sha1_tokens_dev(mhx_ctx *ctx, const uint8_t *d_bytes, const int64_t *d_b
     return mhx::launch_sha1_tokens(ctx, d_bytes, d_byte_offsets, n_tokens, out_dtype, d_out);
 }
 
-// validate + upload a packed byte corpus: bytes -> In, byte offsets -> Offsets
-static int upload_tokens(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens, uint8_t **d_bytes, int64_t **d_offs) {
-    MHX_REQUIRE(byte_offsets, "byte_offsets is NULL");
-    MHX_REQUIRE(byte_offsets[0] == 0, "byte_offsets[0] must be 0");
-    for (int64_t i = 0; i < n_tokens; ++i)
-        MHX_REQUIRE(byte_offsets[i + 1] >= byte_offsets[i], "byte_offsets must be non-decreasing (token %lld)", (long long)i);
-    const int64_t total = byte_offsets[n_tokens];
-    MHX_REQUIRE(bytes || total == 0, "bytes is NULL");
-    Stage s(ctx);
-    const auto p_bytes = s.piece(Stage::In, (size_t)total);
-    const auto p_offs = s.piece(Stage::Offsets, sizeof(int64_t) * (size_t)(n_tokens + 1));
-    s.ask(Stage::In, (size_t)total + 256);
-    MHX_TRY(s.commit());
-    *d_bytes = s.at<uint8_t>(p_bytes);
-    *d_offs = s.at<int64_t>(p_offs);
-    MHX_TRY(s.upload(p_bytes, bytes));
-    return s.upload(p_offs, byte_offsets);
-}
+extern "C++" {
+namespace {
+
+// ---- text to sketches: a corpus becomes sets of hashes (a source), the hashes become a sketch (a sink) ------------------------
+// The three sources -- Tokens here, Windows and Words further down -- have the same members, so that a sink is a function
+// template over its source and neither knows the other:
+//   kNoOut                   what a NULL `out` answers
+//   check_sizes(), n_sets()  the scalar arguments; a corpus of no sets is done before any array is looked at
+//   check_arrays()           the host arrays, checked
+//   stage(ctx)               the corpus into scratch, a Stage of the source's own: bytes -> In (alone), every offset array -> Offsets
+//   max_hashes()             a bound on the number of hashes, known once staged: what the sink sizes its hash piece by
+//   reserve(s)               Aux pieces of the source's own in the SINK's Stage, behind init | hashes (one Stage per slot and
+//                            call: a slot that grows is reallocated)
+//   hash(s, dtype, d_hv)     the launches that fill d_hv; d_sets and n_hashes hold from then on
+
+// packed byte tokens: token i is bytes[byte_offsets[i] .. byte_offsets[i+1]], set j owns tokens set_offsets[j] .. set_offsets[j+1]
+// (set_offsets NULL: the tokens alone, for mhx_sha1_tokens).  Offsets: byte offsets | set offsets.
+struct Tokens {
+    static constexpr const char *kNoOut = "out/set_offsets is NULL";
+    const uint8_t *bytes;
+    const int64_t *byte_offsets;
+    int64_t n_tokens;
+    const int64_t *set_offsets;
+    int64_t n;
+    size_t aux_slack;  // the slack reserve() leaves behind the hashes (see Stage::ask): its entry says how much it has always carried
+    uint8_t *d_bytes = nullptr;
+    int64_t *d_boffs = nullptr, *d_sets = nullptr;
+    int64_t n_hashes = 0;
+
+    int check_sizes() const {
+        MHX_REQUIRE(n >= 0 && n_tokens >= 0, "n_sets and n_tokens must be >= 0");
+        return MHX_OK;
+    }
+    int64_t n_sets() const { return n; }
+    int64_t max_hashes() const { return n_tokens; }
+
+    int check_tokens() const {
+        MHX_REQUIRE(byte_offsets, "byte_offsets is NULL");
+        MHX_REQUIRE(byte_offsets[0] == 0, "byte_offsets[0] must be 0");
+        for (int64_t i = 0; i < n_tokens; ++i)
+            MHX_REQUIRE(byte_offsets[i + 1] >= byte_offsets[i], "byte_offsets must be non-decreasing (token %lld)", (long long)i);
+        MHX_REQUIRE(bytes || byte_offsets[n_tokens] == 0, "bytes is NULL");
+        return MHX_OK;
+    }
+    int check_arrays() const {
+        MHX_REQUIRE(set_offsets, "%s", kNoOut);
+        MHX_REQUIRE(set_offsets[0] == 0 && set_offsets[n] == n_tokens, "set_offsets must run from 0 to n_tokens");
+        for (int64_t i = 0; i < n; ++i)
+            MHX_REQUIRE(set_offsets[i + 1] >= set_offsets[i], "set_offsets must be non-decreasing (set %lld)", (long long)i);
+        return n_tokens > 0 ? check_tokens() : MHX_OK;  // (no token: bytes and byte_offsets are not looked at)
+    }
+
+    int stage(mhx_ctx *ctx) {
+        Stage s(ctx);
+        Stage::Piece p_bytes{Stage::In, 0, 0}, p_boffs{Stage::Offsets, 0, 0}, p_sets{Stage::Offsets, 0, 0};
+        if (n_tokens > 0) {
+            p_bytes = s.piece(Stage::In, (size_t)byte_offsets[n_tokens]);
+            s.ask(Stage::In, p_bytes.bytes + 256);
+            p_boffs = s.piece(Stage::Offsets, sizeof(int64_t) * (size_t)(n_tokens + 1));
+        }
+        if (set_offsets) p_sets = s.piece(Stage::Offsets, sizeof(int64_t) * (size_t)(n + 1));
+        MHX_TRY(s.commit());
+        if (n_tokens > 0) {
+            d_bytes = s.at<uint8_t>(p_bytes);
+            d_boffs = s.at<int64_t>(p_boffs);
+        }
+        if (set_offsets) d_sets = s.at<int64_t>(p_sets);
+        MHX_TRY(s.upload(p_bytes, bytes));
+        MHX_TRY(s.upload(p_boffs, byte_offsets));
+        return s.upload(p_sets, set_offsets);
+    }
+    void reserve(Stage &s) const {
+        if (aux_slack) s.ask(Stage::Aux, s.size[Stage::Aux] + aux_slack);
+    }
+    int hash(const Stage &s, int dtype, void *d_hv) {
+        n_hashes = n_tokens;
+        return mhx::launch_sha1_tokens(s.ctx, d_bytes, d_boffs, n_tokens, dtype, d_hv);
+    }
+};
+
+}  // namespace
+}  // extern "C++"
 
 int mhx_sha1_tokens(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens, int out_dtype, void *out) {
     MHX_ENTER(ctx, ctx);
@@ -1025,51 +1089,13 @@ int mhx_sha1_tokens(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *byte_offs
     if (n_tokens == 0) return MHX_OK;
     MHX_REQUIRE(out, "out is NULL");
     MHX_TRY(ctx->activate());
-    uint8_t *d_bytes = nullptr;
-    int64_t *d_offs = nullptr;
-    MHX_TRY(upload_tokens(ctx, bytes, byte_offsets, n_tokens, &d_bytes, &d_offs));
+    Tokens src{bytes, byte_offsets, n_tokens, nullptr, 0, 0};
+    MHX_TRY(src.check_tokens());
+    MHX_TRY(src.stage(ctx));
     Stage s(ctx);
     const auto p_out = s.piece(Stage::Out, (size_t)n_tokens * (out_dtype == MHX_U32 ? 4 : 8));
     MHX_TRY(s.commit());
-    MHX_TRY(mhx::launch_sha1_tokens(ctx, d_bytes, d_offs, n_tokens, out_dtype, s.at<void>(p_out)));
-    return s.fetch(out, p_out);
-}
-
-int mhx_minhash_bulk_bytes(mhx_perm *perm, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens, const int64_t *set_offsets,
-                           int64_t n_sets, const uint64_t *init, int64_t init_stride, uint64_t *out) {
-    return mhx_minhash_bulk_bytes_typed(perm, bytes, byte_offsets, n_tokens, MHX_U32, set_offsets, n_sets, init, init_stride, out);
-}
-
-int mhx_minhash_bulk_bytes_typed(mhx_perm *perm, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens, int hash_dtype,
-                                 const int64_t *set_offsets, int64_t n_sets, const uint64_t *init, int64_t init_stride, uint64_t *out) {
-    MHX_ENTER(perm, perm->ctx);
-    MHX_REQUIRE(hash_dtype == MHX_U32 || hash_dtype == MHX_U64, "hash_dtype must be MHX_U32 (sha1_hash32) or MHX_U64 (sha1_hash64)");
-    MHX_REQUIRE(n_sets >= 0 && n_tokens >= 0, "n_sets and n_tokens must be >= 0");
-    if (n_sets == 0) return MHX_OK;
-    MHX_REQUIRE(out && set_offsets, "out/set_offsets is NULL");
-    MHX_REQUIRE(set_offsets[0] == 0 && set_offsets[n_sets] == n_tokens, "set_offsets must run from 0 to n_tokens");
-    for (int64_t i = 0; i < n_sets; ++i)
-        MHX_REQUIRE(set_offsets[i + 1] >= set_offsets[i], "set_offsets must be non-decreasing (set %lld)", (long long)i);
-    mhx_ctx *ctx = perm->ctx;
-    MHX_TRY(ctx->activate());
-    const int64_t k = perm->num_perm;
-    uint8_t *d_bytes = nullptr;
-    int64_t *d_boffs = nullptr;
-    if (n_tokens > 0) MHX_TRY(upload_tokens(ctx, bytes, byte_offsets, n_tokens, &d_bytes, &d_boffs));
-    // Aux: set offsets | init | token hashes (uint32 or uint64);  Out: signatures
-    Stage s(ctx);
-    const auto p_soffs = s.piece(Stage::Aux, sizeof(int64_t) * (size_t)(n_sets + 1));
-    const auto p_init = s.piece(Stage::Aux, init ? sizeof(uint64_t) * (size_t)(init_stride ? n_sets * init_stride : k) : 0);
-    const auto p_hv = s.piece(Stage::Aux, (hash_dtype == MHX_U32 ? 4 : 8) * (size_t)n_tokens);
-    const auto p_out = s.piece(Stage::Out, sizeof(uint64_t) * (size_t)(n_sets * k));
-    s.ask(Stage::Aux, p_hv.at + p_hv.bytes + 256);
-    MHX_TRY(s.commit());
-    uint64_t *d_init = init ? s.at<uint64_t>(p_init) : nullptr;
-    MHX_TRY(s.upload(p_soffs, set_offsets));
-    MHX_TRY(s.upload(p_init, init));
-    MHX_TRY(mhx::launch_sha1_tokens(ctx, d_bytes, d_boffs, n_tokens, hash_dtype, s.at<void>(p_hv)));
-    MHX_TRY(mhx::launch_minhash_bulk(perm, s.at<void>(p_hv), hash_dtype, s.at<int64_t>(p_soffs), 0, n_sets, n_tokens, d_init, init_stride,
-                                     s.at<uint64_t>(p_out), MHX_U64));
+    MHX_TRY(src.hash(s, out_dtype, s.at<void>(p_out)));
     return s.fetch(out, p_out);
 }
 
@@ -2154,39 +2180,6 @@ int mhx_hll_bulk_typed(mhx_ctx *ctx, const void *hv, int hv_dtype, const int64_t
     return hll_bulk(ctx, hv, hv_dtype, offsets, fixed_len, n_sets, 0, p, hash_bits, init, init_stride, out, overflow, kHost);
 }
 
-int mhx_hll_bulk_bytes(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens, int32_t hash_bits,
-                       const int64_t *set_offsets, int64_t n_sets, int32_t p, const uint8_t *init, int64_t init_stride, uint8_t *out) {
-    MHX_ENTER(ctx, ctx);
-    MHX_TRY(check_hll(p, hash_bits));
-    const int64_t m = (int64_t)1 << p;
-    MHX_REQUIRE(n_sets >= 0 && n_tokens >= 0, "n_sets and n_tokens must be >= 0");
-    MHX_REQUIRE(init_stride == 0 || init_stride == m, "init_stride must be 0 (one shared row) or m = %lld", (long long)m);
-    if (n_sets == 0) return MHX_OK;
-    MHX_REQUIRE(out && set_offsets, "out/set_offsets is NULL");
-    MHX_REQUIRE(set_offsets[0] == 0 && set_offsets[n_sets] == n_tokens, "set_offsets must run from 0 to n_tokens");
-    for (int64_t i = 0; i < n_sets; ++i)
-        MHX_REQUIRE(set_offsets[i + 1] >= set_offsets[i], "set_offsets must be non-decreasing (set %lld)", (long long)i);
-    MHX_TRY(ctx->activate());
-    const int hash_dtype = hash_bits == 32 ? MHX_U32 : MHX_U64;  // sha1_hash32 / sha1_hash64: the hashes fit hash_bits by construction
-    uint8_t *d_bytes = nullptr;
-    int64_t *d_boffs = nullptr;
-    if (n_tokens > 0) MHX_TRY(upload_tokens(ctx, bytes, byte_offsets, n_tokens, &d_bytes, &d_boffs));
-    // Aux: set offsets | init | token hashes;  Out: registers
-    Stage s(ctx);
-    const auto p_soffs = s.piece(Stage::Aux, sizeof(int64_t) * (size_t)(n_sets + 1));
-    Stage::Piece p_init{Stage::Aux, 0, 0};
-    if (init) p_init = s.piece(Stage::Aux, (size_t)(init_stride ? n_sets * m : m));
-    const auto p_hv = s.piece(Stage::Aux, (hash_bits == 32 ? 4 : 8) * (size_t)n_tokens);
-    const auto p_out = s.piece(Stage::Out, (size_t)(n_sets * m));
-    MHX_TRY(s.commit());
-    MHX_TRY(s.upload(p_soffs, set_offsets));
-    MHX_TRY(s.upload(p_init, init));
-    MHX_TRY(mhx::launch_sha1_tokens(ctx, d_bytes, d_boffs, n_tokens, hash_dtype, s.at<void>(p_hv)));
-    MHX_TRY(mhx::launch_hll_bulk(ctx, s.at<void>(p_hv), hash_dtype, s.at<int64_t>(p_soffs), 0, n_sets, n_tokens, p, hash_bits,
-                                 init ? s.at<uint8_t>(p_init) : nullptr, init_stride, s.at<uint8_t>(p_out), nullptr));
-    return s.fetch(out, p_out);
-}
-
 static int hll_histogram(mhx_ctx *ctx, const uint8_t *reg, int64_t n, int p, uint32_t *hist, int64_t *invalid, Where where) {
     MHX_ENTER(ctx, ctx);
     MHX_TRY(check_hll(p, 32));
@@ -2301,15 +2294,25 @@ int mhx_sha1_windows_dev(mhx_ctx *ctx, const uint8_t *d_bytes, const int64_t *d_
 extern "C++" {
 namespace {
 
-// a host corpus of the host forms, checked (plan) and then staged (upload): bytes -> In; item offsets | document offsets |
-// set offsets -> Offsets.  Aux and Out are the caller's.
+// windows over the bytes (item_offsets NULL) or the tokens of documents: a source (see Tokens).  Offsets: item offsets | document
+// offsets | set offsets.
 struct Windows {
-    std::vector<int64_t> set_offsets;
-    int64_t n_windows = 0, n_bytes = 0;
+    static constexpr const char *kNoOut = "out is NULL";
+    const uint8_t *bytes;
+    const int64_t *item_offsets;
+    int64_t n_items;
+    const int64_t *doc_offsets;
+    int64_t n_docs, width;
+    std::vector<int64_t> set_offsets;  // (alive until the call has synchronised: it is uploaded from)
+    int64_t n_bytes = 0, n_hashes = 0;  // n_hashes: the number of windows, known from check_arrays() on
     uint8_t *d_bytes = nullptr;
     int64_t *d_items = nullptr, *d_docs = nullptr, *d_sets = nullptr;
 
-    int plan(const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items, const int64_t *doc_offsets, int64_t n_docs, int64_t width) {
+    int check_sizes() const { return check_windows(n_docs, width); }
+    int64_t n_sets() const { return n_docs; }
+    int64_t max_hashes() const { return n_hashes; }
+
+    int check_arrays() {
         MHX_REQUIRE(n_items >= 0, "n_items must be >= 0");
         MHX_REQUIRE(doc_offsets, "doc_offsets is NULL");
         MHX_REQUIRE(doc_offsets[0] == 0 && doc_offsets[n_docs] == n_items, "doc_offsets must run from 0 to n_items");
@@ -2322,11 +2325,11 @@ struct Windows {
         MHX_REQUIRE(bytes || n_bytes == 0, "bytes is NULL");
         set_offsets.resize((size_t)n_docs + 1);
         MHX_TRY(mhx_shingle_window_offsets(doc_offsets, n_docs, width, set_offsets.data()));
-        n_windows = set_offsets[(size_t)n_docs];
+        n_hashes = set_offsets[(size_t)n_docs];
         return MHX_OK;
     }
 
-    int upload(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items, const int64_t *doc_offsets, int64_t n_docs) {
+    int stage(mhx_ctx *ctx) {
         Stage s(ctx);
         const auto p_bytes = s.piece(Stage::In, (size_t)n_bytes);
         if (n_bytes == 0) s.ask(Stage::In, 8);
@@ -2343,6 +2346,10 @@ struct Windows {
         MHX_TRY(s.upload(p_docs, doc_offsets));
         return s.upload(p_sets, set_offsets.data());
     }
+    void reserve(Stage &) const {}
+    int hash(const Stage &s, int dtype, void *d_hv) const {
+        return mhx::launch_sha1_windows(s.ctx, d_bytes, d_items, d_docs, d_sets, n_docs, n_hashes, width, dtype, d_hv);
+    }
 };
 
 }  // namespace
@@ -2351,76 +2358,19 @@ struct Windows {
 int mhx_sha1_windows(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items, const int64_t *doc_offsets,
                      int64_t n_docs, int64_t width, int out_dtype, void *out) {
     MHX_ENTER(ctx, ctx);
-    MHX_TRY(check_windows(n_docs, width));
+    Windows src{bytes, item_offsets, n_items, doc_offsets, n_docs, width};
+    MHX_TRY(src.check_sizes());
     MHX_CHECK_DTYPE(out_dtype);
     if (n_docs == 0) return MHX_OK;
-    Windows w;
-    MHX_TRY(w.plan(bytes, item_offsets, n_items, doc_offsets, n_docs, width));
-    if (w.n_windows == 0) return MHX_OK;
+    MHX_TRY(src.check_arrays());
+    if (src.n_hashes == 0) return MHX_OK;
     MHX_REQUIRE(out, "out is NULL");
     MHX_TRY(ctx->activate());
-    MHX_TRY(w.upload(ctx, bytes, item_offsets, n_items, doc_offsets, n_docs));
+    MHX_TRY(src.stage(ctx));
     Stage s(ctx);
-    const auto p_out = s.piece(Stage::Out, (size_t)w.n_windows * (out_dtype == MHX_U32 ? 4 : 8));
+    const auto p_out = s.piece(Stage::Out, (size_t)src.n_hashes * (out_dtype == MHX_U32 ? 4 : 8));
     MHX_TRY(s.commit());
-    MHX_TRY(mhx::launch_sha1_windows(ctx, w.d_bytes, w.d_items, w.d_docs, w.d_sets, n_docs, w.n_windows, width, out_dtype, s.at<void>(p_out)));
-    return s.fetch(out, p_out);
-}
-
-int mhx_minhash_bulk_windows_typed(mhx_perm *perm, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items,
-                                   const int64_t *doc_offsets, int64_t n_docs, int64_t width, int hash_dtype, const uint64_t *init,
-                                   int64_t init_stride, void *out, int out_dtype) {
-    MHX_ENTER(perm, perm->ctx);
-    MHX_TRY(check_windows(n_docs, width));
-    MHX_REQUIRE(hash_dtype == MHX_U32 || hash_dtype == MHX_U64, "hash_dtype must be MHX_U32 (sha1_hash32) or MHX_U64 (sha1_hash64)");
-    MHX_CHECK_DTYPE(out_dtype);
-    MHX_REQUIRE(init_stride == 0 || init_stride >= perm->num_perm, "init_stride must be 0 or >= num_perm");
-    if (n_docs == 0) return MHX_OK;
-    MHX_REQUIRE(out, "out is NULL");
-    Windows w;
-    MHX_TRY(w.plan(bytes, item_offsets, n_items, doc_offsets, n_docs, width));
-    mhx_ctx *ctx = perm->ctx;
-    MHX_TRY(ctx->activate());
-    MHX_TRY(w.upload(ctx, bytes, item_offsets, n_items, doc_offsets, n_docs));
-    const int64_t k = perm->num_perm;
-    // Aux: init | window hashes (uint32 or uint64);  Out: signatures
-    Stage s(ctx);
-    const auto p_init = s.piece(Stage::Aux, init ? sizeof(uint64_t) * (size_t)(init_stride ? n_docs * init_stride : k) : 0);
-    const auto p_hv = s.piece(Stage::Aux, (hash_dtype == MHX_U32 ? 4 : 8) * (size_t)w.n_windows);
-    const auto p_out = s.piece(Stage::Out, (out_dtype == MHX_U32 ? 4 : 8) * (size_t)(n_docs * k));
-    MHX_TRY(s.commit());
-    MHX_TRY(s.upload(p_init, init));
-    MHX_TRY(mhx::launch_sha1_windows(ctx, w.d_bytes, w.d_items, w.d_docs, w.d_sets, n_docs, w.n_windows, width, hash_dtype, s.at<void>(p_hv)));
-    MHX_TRY(mhx::launch_minhash_bulk(perm, s.at<void>(p_hv), hash_dtype, w.d_sets, 0, n_docs, w.n_windows, init ? s.at<uint64_t>(p_init) : nullptr,
-                                     init_stride, s.at<void>(p_out), out_dtype));
-    return s.fetch(out, p_out);
-}
-
-int mhx_hll_bulk_windows(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items, const int64_t *doc_offsets,
-                         int64_t n_docs, int64_t width, int32_t hash_bits, int32_t p, const uint8_t *init, int64_t init_stride, uint8_t *out) {
-    MHX_ENTER(ctx, ctx);
-    MHX_TRY(check_windows(n_docs, width));
-    MHX_TRY(check_hll(p, hash_bits));
-    const int64_t m = (int64_t)1 << p;
-    MHX_REQUIRE(init_stride == 0 || init_stride == m, "init_stride must be 0 (one shared row) or m = %lld", (long long)m);
-    if (n_docs == 0) return MHX_OK;
-    MHX_REQUIRE(out, "out is NULL");
-    Windows w;
-    MHX_TRY(w.plan(bytes, item_offsets, n_items, doc_offsets, n_docs, width));
-    MHX_TRY(ctx->activate());
-    MHX_TRY(w.upload(ctx, bytes, item_offsets, n_items, doc_offsets, n_docs));
-    const int hash_dtype = hash_bits == 32 ? MHX_U32 : MHX_U64;  // sha1_hash32 / sha1_hash64: the hashes fit hash_bits by construction
-    // Aux: init | window hashes;  Out: registers
-    Stage s(ctx);
-    Stage::Piece p_init{Stage::Aux, 0, 0};
-    if (init) p_init = s.piece(Stage::Aux, (size_t)(init_stride ? n_docs * m : m));
-    const auto p_hv = s.piece(Stage::Aux, (hash_bits == 32 ? 4 : 8) * (size_t)w.n_windows);
-    const auto p_out = s.piece(Stage::Out, (size_t)(n_docs * m));
-    MHX_TRY(s.commit());
-    MHX_TRY(s.upload(p_init, init));
-    MHX_TRY(mhx::launch_sha1_windows(ctx, w.d_bytes, w.d_items, w.d_docs, w.d_sets, n_docs, w.n_windows, width, hash_dtype, s.at<void>(p_hv)));
-    MHX_TRY(mhx::launch_hll_bulk(ctx, s.at<void>(p_hv), hash_dtype, w.d_sets, 0, n_docs, w.n_windows, p, hash_bits,
-                                 init ? s.at<uint8_t>(p_init) : nullptr, init_stride, s.at<uint8_t>(p_out), nullptr));
+    MHX_TRY(src.hash(s, out_dtype, s.at<void>(p_out)));
     return s.fetch(out, p_out);
 }
 
@@ -2430,16 +2380,6 @@ static int check_words(int64_t n_bytes, int64_t n_docs, const uint8_t *table) {
     MHX_REQUIRE(n_docs >= 0, "n_docs must be >= 0");
     MHX_REQUIRE(table, "table is NULL");
     MHX_REQUIRE(table[0] == 0, "table[0] must be 0: byte 0 is always a separator");
-    return MHX_OK;
-}
-
-// the host corpus of the host forms
-static int check_words_corpus(const uint8_t *bytes, int64_t n_bytes, const int64_t *doc_offsets, int64_t n_docs) {
-    MHX_REQUIRE(doc_offsets, "doc_offsets is NULL");
-    MHX_REQUIRE(bytes || n_bytes == 0, "bytes is NULL");
-    MHX_REQUIRE(doc_offsets[0] == 0 && doc_offsets[n_docs] == n_bytes, "doc_offsets must run from 0 to n_bytes");
-    for (int64_t d = 0; d < n_docs; ++d)
-        MHX_REQUIRE(doc_offsets[d + 1] >= doc_offsets[d], "doc_offsets must be non-decreasing (document %lld)", (long long)d);
     return MHX_OK;
 }
 
@@ -2477,15 +2417,40 @@ int mhx_words_normalize_dev(mhx_ctx *ctx, const uint8_t *d_bytes, int64_t n_byte
 extern "C++" {
 namespace {
 
-// A host corpus staged and counted: bytes -> In; document offsets | word offsets of the documents | set offsets -> Offsets.
-// The caller then names where the text and its item offsets go (they are sized by the count) and calls emit().
+// the words of raw text in windows of `width`: a source (see Tokens).  Offsets: document offsets | word offsets of the documents |
+// set offsets.  stage() also counts -- it blocks -- since everything after it is sized by the count; reserve() names where the
+// normalised text and its item offsets go.
 struct Words {
-    int64_t n_words = 0, n_out_bytes = 0, n_windows = 0;
+    static constexpr const char *kNoOut = "out is NULL";
+    const uint8_t *bytes;
+    int64_t n_bytes;
+    const int64_t *doc_offsets;
+    int64_t n_docs;
+    const uint8_t *table;
+    int64_t width;
+    int64_t n_words = 0, n_out_bytes = 0, n_hashes = 0;
     uint8_t *d_bytes = nullptr;
     int64_t *d_docs = nullptr, *d_wdocs = nullptr, *d_sets = nullptr;
+    Stage::Piece p_text{Stage::Aux, 0, 0}, p_items{Stage::Aux, 0, 0};
     std::vector<int64_t> wdocs, sets;  // (alive until the call has synchronised: they are uploaded from)
 
-    int count(mhx_ctx *ctx, const uint8_t *bytes, int64_t n_bytes, const int64_t *doc_offsets, int64_t n_docs, const uint8_t *table) {
+    int check_sizes() const {
+        MHX_TRY(check_windows(n_docs, width));
+        return check_words(n_bytes, n_docs, table);
+    }
+    int64_t n_sets() const { return n_docs; }
+    int64_t max_hashes() const { return n_words; }  // (a document has no more windows than words)
+
+    int check_arrays() const {
+        MHX_REQUIRE(doc_offsets, "doc_offsets is NULL");
+        MHX_REQUIRE(bytes || n_bytes == 0, "bytes is NULL");
+        MHX_REQUIRE(doc_offsets[0] == 0 && doc_offsets[n_docs] == n_bytes, "doc_offsets must run from 0 to n_bytes");
+        for (int64_t d = 0; d < n_docs; ++d)
+            MHX_REQUIRE(doc_offsets[d + 1] >= doc_offsets[d], "doc_offsets must be non-decreasing (document %lld)", (long long)d);
+        return MHX_OK;
+    }
+
+    int stage(mhx_ctx *ctx) {
         Stage s(ctx);
         const auto p_bytes = s.piece(Stage::In, (size_t)n_bytes);
         if (n_bytes == 0) s.ask(Stage::In, 8);
@@ -2500,22 +2465,30 @@ struct Words {
         MHX_TRY(s.upload(p_docs, doc_offsets));
         return mhx::launch_words_count(ctx, d_bytes, n_bytes, d_docs, n_docs, table, &n_words, &n_out_bytes);
     }
-
-    int emit(mhx_ctx *ctx, int64_t n_bytes, int64_t n_docs, const uint8_t *table, uint8_t *d_text, int64_t *d_items) {
-        return mhx::launch_words_emit(ctx, d_bytes, n_bytes, d_docs, n_docs, table, d_text, d_items, d_wdocs);
+    void reserve(Stage &s) {
+        p_text = s.piece(Stage::Aux, (size_t)n_out_bytes);
+        p_items = s.piece(Stage::Aux, sizeof(int64_t) * (size_t)(n_words + 1));
     }
 
+    int emit(mhx_ctx *ctx, uint8_t *d_text, int64_t *d_items) const {
+        return mhx::launch_words_emit(ctx, d_bytes, n_bytes, d_docs, n_docs, table, d_text, d_items, d_wdocs);
+    }
     // the set offsets of the windows of `width` words: 8 bytes per document down, mhx_shingle_window_offsets, 8 bytes up.  Blocks.
-    int window_offsets(mhx_ctx *ctx, int64_t n_docs, int64_t width) {
+    int window_offsets(mhx_ctx *ctx) {
         wdocs.resize((size_t)n_docs + 1);
         sets.resize((size_t)n_docs + 1);
         const size_t bytes = sizeof(int64_t) * (size_t)(n_docs + 1);
         MHX_HIP_CHECK(hipMemcpyAsync(wdocs.data(), d_wdocs, bytes, hipMemcpyDeviceToHost, ctx->stream));
         MHX_HIP_CHECK(hipStreamSynchronize(ctx->stream));
         MHX_TRY(mhx_shingle_window_offsets(wdocs.data(), n_docs, width, sets.data()));
-        n_windows = sets[(size_t)n_docs];
+        n_hashes = sets[(size_t)n_docs];
         MHX_HIP_CHECK(hipMemcpyAsync(d_sets, sets.data(), bytes, hipMemcpyHostToDevice, ctx->stream));
         return MHX_OK;
+    }
+    int hash(const Stage &s, int dtype, void *d_hv) {
+        MHX_TRY(emit(s.ctx, s.at<uint8_t>(p_text), s.at<int64_t>(p_items)));
+        MHX_TRY(window_offsets(s.ctx));
+        return mhx::launch_sha1_windows(s.ctx, s.at<uint8_t>(p_text), s.at<int64_t>(p_items), d_wdocs, d_sets, n_docs, n_hashes, width, dtype, d_hv);
     }
 };
 
@@ -2531,10 +2504,10 @@ int mhx_words_normalize(mhx_ctx *ctx, const uint8_t *bytes, int64_t n_bytes, con
     MHX_TRY(check_words(n_bytes, n_docs, table));
     MHX_REQUIRE(cap_bytes >= 0 && cap_words >= 0, "cap_bytes and cap_words must be >= 0");
     if (n_docs == 0) return MHX_OK;
-    MHX_TRY(check_words_corpus(bytes, n_bytes, doc_offsets, n_docs));
+    Words w{bytes, n_bytes, doc_offsets, n_docs, table, /*width: no windows here*/ 0};
+    MHX_TRY(w.check_arrays());
     MHX_TRY(ctx->activate());
-    Words w;
-    MHX_TRY(w.count(ctx, bytes, n_bytes, doc_offsets, n_docs, table));
+    MHX_TRY(w.stage(ctx));
     *n_words = w.n_words;
     *n_out_bytes = w.n_out_bytes;
     bool emit = false;
@@ -2543,79 +2516,116 @@ int mhx_words_normalize(mhx_ctx *ctx, const uint8_t *bytes, int64_t n_bytes, con
     Stage s(ctx);
     const auto p_text = s.piece(Stage::Out, (size_t)w.n_out_bytes), p_items = s.piece(Stage::Out, sizeof(int64_t) * (size_t)(w.n_words + 1));
     MHX_TRY(s.commit());
-    MHX_TRY(w.emit(ctx, n_bytes, n_docs, table, s.at<uint8_t>(p_text), s.at<int64_t>(p_items)));
+    MHX_TRY(w.emit(ctx, s.at<uint8_t>(p_text), s.at<int64_t>(p_items)));
     if (w.n_out_bytes) MHX_TRY(s.download(out_bytes, p_text));
     MHX_TRY(s.download(item_offsets, p_items));
     MHX_HIP_CHECK(hipMemcpyAsync(word_doc_offsets, w.d_wdocs, sizeof(int64_t) * (size_t)(n_docs + 1), hipMemcpyDeviceToHost, ctx->stream));
     return s.synchronize();
 }
 
+// ---- the two sinks, and the six entries: a source constructed, a sink called ------------------------------------------------------
+extern "C++" {
+namespace {
+
+// Aux: init | hashes (uint32 or uint64) | whatever the source reserves;  Out: signatures
+template <class Source>
+int minhash_of(mhx_perm *perm, Source &&src, int hash_dtype, const uint64_t *init, int64_t init_stride, void *out, int out_dtype) {
+    MHX_REQUIRE(hash_dtype == MHX_U32 || hash_dtype == MHX_U64, "hash_dtype must be MHX_U32 (sha1_hash32) or MHX_U64 (sha1_hash64)");
+    MHX_CHECK_DTYPE(out_dtype);
+    MHX_REQUIRE(init_stride == 0 || init_stride >= perm->num_perm, "init_stride must be 0 or >= num_perm");
+    MHX_TRY(src.check_sizes());
+    const int64_t n = src.n_sets(), k = perm->num_perm;
+    if (n == 0) return MHX_OK;
+    MHX_REQUIRE(out, "%s", src.kNoOut);
+    MHX_TRY(src.check_arrays());
+    mhx_ctx *ctx = perm->ctx;
+    MHX_TRY(ctx->activate());
+    MHX_TRY(src.stage(ctx));
+    Stage s(ctx);
+    const auto p_init = s.piece(Stage::Aux, init ? sizeof(uint64_t) * (size_t)(init_stride ? n * init_stride : k) : 0);
+    const auto p_hv = s.piece(Stage::Aux, (hash_dtype == MHX_U32 ? 4 : 8) * (size_t)src.max_hashes());
+    src.reserve(s);
+    const auto p_out = s.piece(Stage::Out, (out_dtype == MHX_U32 ? 4 : 8) * (size_t)(n * k));
+    MHX_TRY(s.commit());
+    MHX_TRY(s.upload(p_init, init));
+    MHX_TRY(src.hash(s, hash_dtype, s.at<void>(p_hv)));
+    MHX_TRY(mhx::launch_minhash_bulk(perm, s.at<void>(p_hv), hash_dtype, src.d_sets, 0, n, src.n_hashes, init ? s.at<uint64_t>(p_init) : nullptr,
+                                     init_stride, s.at<void>(p_out), out_dtype));
+    return s.fetch(out, p_out);
+}
+
+// Aux: init | hashes (sha1_hash32 / sha1_hash64: they fit hash_bits by construction) | whatever the source reserves;  Out: registers
+template <class Source>
+int hll_of(mhx_ctx *ctx, Source &&src, int32_t hash_bits, int32_t p, const uint8_t *init, int64_t init_stride, uint8_t *out) {
+    MHX_TRY(check_hll(p, hash_bits));
+    const int64_t m = (int64_t)1 << p;
+    MHX_REQUIRE(init_stride == 0 || init_stride == m, "init_stride must be 0 (one shared row) or m = %lld", (long long)m);
+    MHX_TRY(src.check_sizes());
+    const int64_t n = src.n_sets();
+    if (n == 0) return MHX_OK;
+    MHX_REQUIRE(out, "%s", src.kNoOut);
+    MHX_TRY(src.check_arrays());
+    MHX_TRY(ctx->activate());
+    MHX_TRY(src.stage(ctx));
+    const int hash_dtype = hash_bits == 32 ? MHX_U32 : MHX_U64;
+    Stage s(ctx);
+    const auto p_init = s.piece(Stage::Aux, init ? (size_t)(init_stride ? n * m : m) : 0);
+    const auto p_hv = s.piece(Stage::Aux, (hash_bits == 32 ? 4 : 8) * (size_t)src.max_hashes());
+    src.reserve(s);
+    const auto p_out = s.piece(Stage::Out, (size_t)(n * m));
+    MHX_TRY(s.commit());
+    MHX_TRY(s.upload(p_init, init));
+    MHX_TRY(src.hash(s, hash_dtype, s.at<void>(p_hv)));
+    MHX_TRY(mhx::launch_hll_bulk(ctx, s.at<void>(p_hv), hash_dtype, src.d_sets, 0, n, src.n_hashes, p, hash_bits,
+                                 init ? s.at<uint8_t>(p_init) : nullptr, init_stride, s.at<uint8_t>(p_out), nullptr));
+    return s.fetch(out, p_out);
+}
+
+}  // namespace
+}  // extern "C++"
+
+int mhx_minhash_bulk_bytes(mhx_perm *perm, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens, const int64_t *set_offsets,
+                           int64_t n_sets, const uint64_t *init, int64_t init_stride, uint64_t *out) {
+    return mhx_minhash_bulk_bytes_typed(perm, bytes, byte_offsets, n_tokens, MHX_U32, set_offsets, n_sets, init, init_stride, out);
+}
+
+int mhx_minhash_bulk_bytes_typed(mhx_perm *perm, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens, int hash_dtype,
+                                 const int64_t *set_offsets, int64_t n_sets, const uint64_t *init, int64_t init_stride, uint64_t *out) {
+    MHX_ENTER(perm, perm->ctx);
+    return minhash_of(perm, Tokens{bytes, byte_offsets, n_tokens, set_offsets, n_sets, /*aux_slack*/ 256}, hash_dtype, init, init_stride, out, MHX_U64);
+}
+
+int mhx_hll_bulk_bytes(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens, int32_t hash_bits,
+                       const int64_t *set_offsets, int64_t n_sets, int32_t p, const uint8_t *init, int64_t init_stride, uint8_t *out) {
+    MHX_ENTER(ctx, ctx);
+    return hll_of(ctx, Tokens{bytes, byte_offsets, n_tokens, set_offsets, n_sets, /*aux_slack*/ 0}, hash_bits, p, init, init_stride, out);
+}
+
+int mhx_minhash_bulk_windows_typed(mhx_perm *perm, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items,
+                                   const int64_t *doc_offsets, int64_t n_docs, int64_t width, int hash_dtype, const uint64_t *init,
+                                   int64_t init_stride, void *out, int out_dtype) {
+    MHX_ENTER(perm, perm->ctx);
+    return minhash_of(perm, Windows{bytes, item_offsets, n_items, doc_offsets, n_docs, width}, hash_dtype, init, init_stride, out, out_dtype);
+}
+
+int mhx_hll_bulk_windows(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items, const int64_t *doc_offsets,
+                         int64_t n_docs, int64_t width, int32_t hash_bits, int32_t p, const uint8_t *init, int64_t init_stride, uint8_t *out) {
+    MHX_ENTER(ctx, ctx);
+    return hll_of(ctx, Windows{bytes, item_offsets, n_items, doc_offsets, n_docs, width}, hash_bits, p, init, init_stride, out);
+}
+
 int mhx_minhash_bulk_words_typed(mhx_perm *perm, const uint8_t *bytes, int64_t n_bytes, const int64_t *doc_offsets, int64_t n_docs,
                                  const uint8_t *table, int64_t width, int hash_dtype, const uint64_t *init, int64_t init_stride, void *out,
                                  int out_dtype) {
     MHX_ENTER(perm, perm->ctx);
-    MHX_TRY(check_windows(n_docs, width));
-    MHX_TRY(check_words(n_bytes, n_docs, table));
-    MHX_REQUIRE(hash_dtype == MHX_U32 || hash_dtype == MHX_U64, "hash_dtype must be MHX_U32 (sha1_hash32) or MHX_U64 (sha1_hash64)");
-    MHX_CHECK_DTYPE(out_dtype);
-    MHX_REQUIRE(init_stride == 0 || init_stride >= perm->num_perm, "init_stride must be 0 or >= num_perm");
-    if (n_docs == 0) return MHX_OK;
-    MHX_REQUIRE(out, "out is NULL");
-    MHX_TRY(check_words_corpus(bytes, n_bytes, doc_offsets, n_docs));
-    mhx_ctx *ctx = perm->ctx;
-    MHX_TRY(ctx->activate());
-    Words w;
-    MHX_TRY(w.count(ctx, bytes, n_bytes, doc_offsets, n_docs, table));
-    const int64_t k = perm->num_perm;
-    // Aux: init | window hashes (a document has no more windows than words) | the normalised text | its item offsets;  Out: signatures
-    Stage s(ctx);
-    const auto p_init = s.piece(Stage::Aux, init ? sizeof(uint64_t) * (size_t)(init_stride ? n_docs * init_stride : k) : 0);
-    const auto p_hv = s.piece(Stage::Aux, (hash_dtype == MHX_U32 ? 4 : 8) * (size_t)w.n_words);
-    const auto p_text = s.piece(Stage::Aux, (size_t)w.n_out_bytes), p_items = s.piece(Stage::Aux, sizeof(int64_t) * (size_t)(w.n_words + 1));
-    const auto p_out = s.piece(Stage::Out, (out_dtype == MHX_U32 ? 4 : 8) * (size_t)(n_docs * k));
-    MHX_TRY(s.commit());
-    MHX_TRY(s.upload(p_init, init));
-    MHX_TRY(w.emit(ctx, n_bytes, n_docs, table, s.at<uint8_t>(p_text), s.at<int64_t>(p_items)));
-    MHX_TRY(w.window_offsets(ctx, n_docs, width));
-    MHX_TRY(mhx::launch_sha1_windows(ctx, s.at<uint8_t>(p_text), s.at<int64_t>(p_items), w.d_wdocs, w.d_sets, n_docs, w.n_windows, width,
-                                     hash_dtype, s.at<void>(p_hv)));
-    MHX_TRY(mhx::launch_minhash_bulk(perm, s.at<void>(p_hv), hash_dtype, w.d_sets, 0, n_docs, w.n_windows, init ? s.at<uint64_t>(p_init) : nullptr,
-                                     init_stride, s.at<void>(p_out), out_dtype));
-    return s.fetch(out, p_out);
+    return minhash_of(perm, Words{bytes, n_bytes, doc_offsets, n_docs, table, width}, hash_dtype, init, init_stride, out, out_dtype);
 }
 
 int mhx_hll_bulk_words(mhx_ctx *ctx, const uint8_t *bytes, int64_t n_bytes, const int64_t *doc_offsets, int64_t n_docs,
                        const uint8_t *table, int64_t width, int32_t hash_bits, int32_t p, const uint8_t *init, int64_t init_stride,
                        uint8_t *out) {
     MHX_ENTER(ctx, ctx);
-    MHX_TRY(check_windows(n_docs, width));
-    MHX_TRY(check_words(n_bytes, n_docs, table));
-    MHX_TRY(check_hll(p, hash_bits));
-    const int64_t m = (int64_t)1 << p;
-    MHX_REQUIRE(init_stride == 0 || init_stride == m, "init_stride must be 0 (one shared row) or m = %lld", (long long)m);
-    if (n_docs == 0) return MHX_OK;
-    MHX_REQUIRE(out, "out is NULL");
-    MHX_TRY(check_words_corpus(bytes, n_bytes, doc_offsets, n_docs));
-    MHX_TRY(ctx->activate());
-    Words w;
-    MHX_TRY(w.count(ctx, bytes, n_bytes, doc_offsets, n_docs, table));
-    const int hash_dtype = hash_bits == 32 ? MHX_U32 : MHX_U64;
-    // Aux: init | window hashes | the normalised text | its item offsets;  Out: registers
-    Stage s(ctx);
-    Stage::Piece p_init{Stage::Aux, 0, 0};
-    if (init) p_init = s.piece(Stage::Aux, (size_t)(init_stride ? n_docs * m : m));
-    const auto p_hv = s.piece(Stage::Aux, (hash_bits == 32 ? 4 : 8) * (size_t)w.n_words);
-    const auto p_text = s.piece(Stage::Aux, (size_t)w.n_out_bytes), p_items = s.piece(Stage::Aux, sizeof(int64_t) * (size_t)(w.n_words + 1));
-    const auto p_out = s.piece(Stage::Out, (size_t)(n_docs * m));
-    MHX_TRY(s.commit());
-    MHX_TRY(s.upload(p_init, init));
-    MHX_TRY(w.emit(ctx, n_bytes, n_docs, table, s.at<uint8_t>(p_text), s.at<int64_t>(p_items)));
-    MHX_TRY(w.window_offsets(ctx, n_docs, width));
-    MHX_TRY(mhx::launch_sha1_windows(ctx, s.at<uint8_t>(p_text), s.at<int64_t>(p_items), w.d_wdocs, w.d_sets, n_docs, w.n_windows, width,
-                                     hash_dtype, s.at<void>(p_hv)));
-    MHX_TRY(mhx::launch_hll_bulk(ctx, s.at<void>(p_hv), hash_dtype, w.d_sets, 0, n_docs, w.n_windows, p, hash_bits,
-                                 init ? s.at<uint8_t>(p_init) : nullptr, init_stride, s.at<uint8_t>(p_out), nullptr));
-    return s.fetch(out, p_out);
+    return hll_of(ctx, Words{bytes, n_bytes, doc_offsets, n_docs, table, width}, hash_bits, p, init, init_stride, out);
 }
 
 // ---- MinHashLSHBloom: per-band Bloom filters (ref: datasketch/lsh_bloom.py) ----------------------------------------------

@@ -448,70 +448,14 @@ class HyperLogLog:
                 raise _overflow_error(hash_bits, p)
             return reg
 
-        def csr_chunks(set_offsets):
-            """(s, e) ranges of whole sets of about _BULK_CHUNK_TOKENS tokens and at most max_sets sets"""
-            n, s = set_offsets.size - 1, 0
-            while s < n:
-                e = min(n, s + max_sets)
-                t0 = int(set_offsets[s])
-                if int(set_offsets[e]) - t0 > _BULK_CHUNK_TOKENS:
-                    e = min(e, max(s + 1, int(np.searchsorted(set_offsets, t0 + _BULK_CHUNK_TOKENS, side="right")) - 1))
-                yield s, e
-                s = e
-
         blocks = []
-        if table is not None:
-            # chunks by bytes: a document has no more windows than words and no more words than bytes
-            buf, doc_offsets = _shingle.join_documents(documents)
-            buf, _, doc_offsets, width = _shingle.check_corpus(buf, None, doc_offsets, shingle)
-            for s, e in _shingle.window_chunks(doc_offsets, max_sets, _BULK_CHUNK_TOKENS):
-                piece, _, local_docs = _shingle.corpus_piece(buf, None, doc_offsets, s, e)
+        if b is None:
+            for piece in _shingle.text_corpus(packed, documents, shingle, table).chunks(max_sets, _BULK_CHUNK_TOKENS):
                 if device_sha1:
-                    blocks.append(_native.context().hll_bulk_words(piece, local_docs, width, p, table, hash_bits))
+                    blocks.append(getattr(_native.context(), "hll_bulk_" + piece.native)(p=p, hash_bits=hash_bits, **piece.arrays()))
                     continue
-                sets = _shingle.host_word_shingles(piece, local_docs, width, table)
-                offsets = np.zeros(len(sets) + 1, dtype=np.int64)
-                np.cumsum(np.fromiter(map(len, sets), dtype=np.int64, count=len(sets)), out=offsets[1:])
-                blocks.append(from_hashes(_as_hashes([hashfunc(t) for d in sets for t in d], hash_bits, p), offsets, 0, e - s))
-        elif shingle is not None:
-            if documents is not None:
-                buf, doc_offsets = _shingle.join_documents(documents)
-                item_offsets = None
-            else:
-                if not (isinstance(packed, tuple) and len(packed) == 3):
-                    raise ValueError("packed is a (buf, byte_offsets, set_offsets) triple")
-                buf, item_offsets, doc_offsets = packed
-            buf, item_offsets, doc_offsets, width = _shingle.check_corpus(buf, item_offsets, doc_offsets, shingle)
-            for s, e in _shingle.window_chunks(_shingle.window_offsets(doc_offsets, width), max_sets, _BULK_CHUNK_TOKENS):
-                piece, local_items, local_docs = _shingle.corpus_piece(buf, item_offsets, doc_offsets, s, e)
-                if device_sha1:
-                    blocks.append(_native.context().hll_bulk_windows(piece, local_docs, width, p, local_items, hash_bits))
-                    continue
-                sets = _shingle.host_shingles(piece, local_items, local_docs, width)
-                offsets = np.zeros(len(sets) + 1, dtype=np.int64)
-                np.cumsum(np.fromiter(map(len, sets), dtype=np.int64, count=len(sets)), out=offsets[1:])
-                blocks.append(from_hashes(_as_hashes([hashfunc(t) for d in sets for t in d], hash_bits, p), offsets, 0, e - s))
-        elif packed is not None:
-            if not (isinstance(packed, tuple) and len(packed) == 3):
-                raise ValueError("packed is a (buf, byte_offsets, set_offsets) triple")
-            buf = np.frombuffer(memoryview(packed[0]), dtype=np.uint8) if not isinstance(packed[0], np.ndarray) else np.ascontiguousarray(packed[0]).view(np.uint8).reshape(-1)
-            byte_offsets = np.ascontiguousarray(packed[1], dtype=np.int64).reshape(-1)
-            set_offsets = np.ascontiguousarray(packed[2], dtype=np.int64).reshape(-1)
-            if byte_offsets.size < 1 or byte_offsets[0] != 0 or byte_offsets[-1] > buf.size or np.any(np.diff(byte_offsets) < 0):
-                raise ValueError("byte_offsets must start at 0, never decrease and end inside buf")
-            if set_offsets.size < 1 or set_offsets[0] != 0 or set_offsets[-1] != byte_offsets.size - 1 or np.any(np.diff(set_offsets) < 0):
-                raise ValueError("set_offsets must start at 0, never decrease and end at the number of tokens")
-            for s, e in csr_chunks(set_offsets):
-                t0, t1 = int(set_offsets[s]), int(set_offsets[e])
-                b0 = int(byte_offsets[t0])
-                local_bytes, local_sets = byte_offsets[t0: t1 + 1] - b0, set_offsets[s: e + 1] - t0
-                piece = buf[b0: int(byte_offsets[t1])]
-                if device_sha1:
-                    blocks.append(_native.context().hll_bulk_bytes(piece, local_bytes, local_sets, p, hash_bits))
-                else:
-                    raw = piece.tobytes()
-                    hv = _as_hashes([hashfunc(raw[local_bytes[i]: local_bytes[i + 1]]) for i in range(t1 - t0)], hash_bits, p)
-                    blocks.append(from_hashes(hv, local_sets, 0, e - s))
+                flat, offsets = _shingle.flatten(piece.host_sets())
+                blocks.append(from_hashes(_as_hashes([hashfunc(t) for t in flat], hash_bits, p), offsets, 0, offsets.size - 1))
         elif hashfunc is prehashed and isinstance(b, np.ndarray) and b.ndim == 2:
             n, t = b.shape
             step = max(1, min(max_sets, _BULK_CHUNK_TOKENS // max(t, 1)))
@@ -522,7 +466,7 @@ class HyperLogLog:
             values, offsets = _as_hashes(b[0], hash_bits, p), np.ascontiguousarray(b[1], dtype=np.int64).reshape(-1)
             if offsets.size < 1 or offsets[0] < 0 or offsets[-1] > values.size or np.any(np.diff(offsets) < 0):
                 raise ValueError("offsets must never decrease and stay inside values")
-            for s, e in csr_chunks(offsets):
+            for s, e in _shingle.window_chunks(offsets, max_sets, _BULK_CHUNK_TOKENS):
                 blocks.append(from_hashes(values[int(offsets[s]): int(offsets[e])], offsets[s: e + 1] - offsets[s], 0, e - s))
         else:
             chunk, tokens = [], 0

@@ -24,8 +24,8 @@ from typing import Callable, Generator, Iterable, List, Optional, Tuple
 
 import numpy as np
 
-from datasketch_amd import _native, shingle
-from datasketch_amd.shingle import words_argument as _shingle_words_argument  # (bulk_signatures has a parameter called shingle)
+from datasketch_amd import _native
+from datasketch_amd import shingle as _shingle  # (bulk_signatures has a parameter called shingle)
 from datasketch_amd.hashfunc import prehashed, sha1_hash32, sha1_hash64
 
 # The size of a hash value in number of bytes (reference: datasketch/minhash.py:27)
@@ -403,107 +403,35 @@ class MinHash:
             raise ValueError("shingle= goes with documents= (bytes) or packed= (tokens), not with b")
         if documents is not None and shingle is None:
             raise ValueError("documents= needs shingle=k, the number of bytes per shingle")
-        table = _shingle_words_argument(words)
+        table = _shingle.words_argument(words)
         if table is not None and documents is None:
             raise ValueError("words= goes with documents= and shingle=w, the number of words per shingle")
         m = cls(**minhash_kwargs)
         if np.dtype(out_dtype) == np.uint32 and not m.is_empty() and int(m.hashvalues.max()) > 0xFFFFFFFF:
             raise ValueError("initial hashvalues >= 2**32 do not fit uint32 signatures")
-        if table is not None:
-            blocks = list(m._word_chunks(documents, shingle, table, np.dtype(out_dtype)))
-        elif shingle is not None:
-            blocks = list(m._window_chunks(documents, packed, shingle, np.dtype(out_dtype)))
+        if b is None:
+            blocks = list(m._text_chunks(_shingle.text_corpus(packed, documents, shingle, table), np.dtype(out_dtype)))
         else:
-            blocks = list(m._packed_chunks(packed, np.dtype(out_dtype)) if packed is not None else m._bulk_chunks(b, np.dtype(out_dtype)))
+            blocks = list(m._bulk_chunks(b, np.dtype(out_dtype)))
         if not blocks:
             return np.empty((0, len(m)), dtype=out_dtype)
         return blocks[0] if len(blocks) == 1 else np.concatenate(blocks, axis=0)
 
-    def _packed_chunks(self, packed, out_dtype=np.uint64) -> Generator[np.ndarray, None, None]:
-        """Signature blocks of a corpus of packed byte tokens, in chunks of whole sets (see :meth:`bulk_signatures`)."""
-        if not (isinstance(packed, tuple) and len(packed) == 3):
-            raise ValueError("packed is a (buf, byte_offsets, set_offsets) triple")
-        buf = np.frombuffer(memoryview(packed[0]), dtype=np.uint8) if not isinstance(packed[0], np.ndarray) else np.ascontiguousarray(packed[0]).view(np.uint8).reshape(-1)
-        byte_offsets = np.ascontiguousarray(packed[1], dtype=np.int64).reshape(-1)
-        set_offsets = np.ascontiguousarray(packed[2], dtype=np.int64).reshape(-1)
-        if byte_offsets.size < 1 or set_offsets.size < 1:
-            raise ValueError("byte_offsets has tokens + 1 entries and set_offsets sets + 1")
-        n_tokens, n_sets = byte_offsets.size - 1, set_offsets.size - 1
-        if byte_offsets[0] != 0 or byte_offsets[-1] > buf.size or np.any(np.diff(byte_offsets) < 0):
-            raise ValueError("byte_offsets must start at 0, never decrease and end inside buf")
-        if set_offsets[0] != 0 or set_offsets[-1] != n_tokens or np.any(np.diff(set_offsets) < 0):
-            raise ValueError("set_offsets must start at 0, never decrease and end at the number of tokens")
+    def _text_chunks(self, corpus, out_dtype=np.uint64) -> Generator[np.ndarray, None, None]:
+        """Signature blocks of a text corpus (one of the kinds of :mod:`datasketch_amd.shingle`), in chunks of whole sets: SHA-1 and
+        MinHash both on the device, or ``hashfunc`` applied to the sets on the host (see :meth:`bulk_signatures`)."""
         init = None if self.is_empty() else self.hashvalues
         bits = 32 if self.hashfunc is sha1_hash32 else 64 if self.hashfunc is sha1_hash64 else 0
         on_device = bits and self._use_gpu()
-        s = 0
-        while s < n_sets:
-            # whole sets, at most _BULK_CHUNK_SETS of them and about _BULK_CHUNK_TOKENS tokens (one set may exceed that alone)
-            e = min(n_sets, s + _BULK_CHUNK_SETS)
-            t0 = int(set_offsets[s])
-            if int(set_offsets[e]) - t0 > _BULK_CHUNK_TOKENS:
-                e = max(s + 1, int(np.searchsorted(set_offsets, t0 + _BULK_CHUNK_TOKENS, side="right")) - 1)
-            t1 = int(set_offsets[e])
-            b0 = int(byte_offsets[t0])
-            local_bytes = byte_offsets[t0: t1 + 1] - b0
-            local_sets = set_offsets[s: e + 1] - t0
-            piece = buf[b0: int(byte_offsets[t1])]
+        for piece in corpus.chunks(_BULK_CHUNK_SETS, _BULK_CHUNK_TOKENS):
             if on_device:
-                blk = _native.context().minhash_bulk_bytes(self.permutations, piece, local_bytes, local_sets, init, bits=bits)
-            else:
-                f = self.hashfunc
-                raw = piece.tobytes()
-                hv = _as_hash_array([f(raw[local_bytes[i]: local_bytes[i + 1]]) for i in range(t1 - t0)]).reshape(-1) if t1 > t0 else np.empty(0, dtype=np.uint64)
-                blk = self._signatures_csr(hv, local_sets, 0, e - s, init)
-            yield blk.astype(out_dtype, copy=False)
-            s = e
-
-    def _window_chunks(self, documents, packed, width, out_dtype=np.uint64) -> Generator[np.ndarray, None, None]:
-        """Signature blocks of a corpus whose sets are shingles -- windows of ``width`` bytes of ``documents`` or of ``width`` tokens
-        of ``packed`` -- in chunks of whole documents, a window counting as a token (see :meth:`bulk_signatures`)."""
-        if documents is not None:
-            buf, doc_offsets = shingle.join_documents(documents)
-            item_offsets = None
-        else:
-            if not (isinstance(packed, tuple) and len(packed) == 3):
-                raise ValueError("packed is a (buf, byte_offsets, set_offsets) triple")
-            buf, item_offsets, doc_offsets = packed
-        buf, item_offsets, doc_offsets, width = shingle.check_corpus(buf, item_offsets, doc_offsets, width)
-        init = None if self.is_empty() else self.hashvalues
-        bits = 32 if self.hashfunc is sha1_hash32 else 64 if self.hashfunc is sha1_hash64 else 0
-        on_device = bits and self._use_gpu()
-        for s, e in shingle.window_chunks(shingle.window_offsets(doc_offsets, width), _BULK_CHUNK_SETS, _BULK_CHUNK_TOKENS):
-            piece, local_items, local_docs = shingle.corpus_piece(buf, item_offsets, doc_offsets, s, e)
-            if on_device:
-                yield _native.context().minhash_bulk_windows(self.permutations, piece, local_docs, width, local_items, init, bits, out_dtype)
+                call = getattr(_native.context(), "minhash_bulk_" + piece.native)
+                yield call(self.permutations, init=init, bits=bits, out_dtype=out_dtype, **piece.arrays())
                 continue
             f = self.hashfunc
-            sets = shingle.host_shingles(piece, local_items, local_docs, width)
-            offsets = np.zeros(len(sets) + 1, dtype=np.int64)
-            np.cumsum(np.fromiter(map(len, sets), dtype=np.int64, count=len(sets)), out=offsets[1:])
-            hv = _as_hash_array([f(t) for d in sets for t in d]).reshape(-1) if offsets[-1] else np.empty(0, dtype=np.uint64)
-            yield self._signatures_csr(hv, offsets, 0, e - s, init).astype(out_dtype, copy=False)
-
-    def _word_chunks(self, documents, width, table, out_dtype=np.uint64) -> Generator[np.ndarray, None, None]:
-        """Signature blocks of a corpus whose sets are the shingles of ``width`` words of ``documents``, in chunks of whole
-        documents.  Chunking is by bytes: a document has no more windows than words and no more words than bytes, so the bounds of
-        :meth:`_window_chunks` hold without knowing the word counts in advance."""
-        buf, doc_offsets = shingle.join_documents(documents)
-        buf, _, doc_offsets, width = shingle.check_corpus(buf, None, doc_offsets, width)
-        init = None if self.is_empty() else self.hashvalues
-        bits = 32 if self.hashfunc is sha1_hash32 else 64 if self.hashfunc is sha1_hash64 else 0
-        on_device = bits and self._use_gpu()
-        for s, e in shingle.window_chunks(doc_offsets, _BULK_CHUNK_SETS, _BULK_CHUNK_TOKENS):
-            piece, _, local_docs = shingle.corpus_piece(buf, None, doc_offsets, s, e)
-            if on_device:
-                yield _native.context().minhash_bulk_words(self.permutations, piece, local_docs, width, table, init, bits, out_dtype)
-                continue
-            f = self.hashfunc
-            sets = shingle.host_word_shingles(piece, local_docs, width, table)
-            offsets = np.zeros(len(sets) + 1, dtype=np.int64)
-            np.cumsum(np.fromiter(map(len, sets), dtype=np.int64, count=len(sets)), out=offsets[1:])
-            hv = _as_hash_array([f(t) for d in sets for t in d]).reshape(-1) if offsets[-1] else np.empty(0, dtype=np.uint64)
-            yield self._signatures_csr(hv, offsets, 0, e - s, init).astype(out_dtype, copy=False)
+            flat, offsets = _shingle.flatten(piece.host_sets())
+            hv = _as_hash_array([f(t) for t in flat]).reshape(-1) if flat else np.empty(0, dtype=np.uint64)
+            yield self._signatures_csr(hv, offsets, 0, offsets.size - 1, init).astype(out_dtype, copy=False)
 
     # ------------------------------------------------------------------ pickling
     # State is plain numpy + the gpu_mode string: device handles live in the process-wide

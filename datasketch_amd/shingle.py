@@ -24,6 +24,7 @@ token-mode corpus.  ``"the  cat"``, ``"The cat"`` and ``"the cat,"`` then give t
 """
 from __future__ import annotations
 
+import copy
 from typing import Iterator, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -142,12 +143,6 @@ def words_argument(words_arg) -> Optional[np.ndarray]:
     return check_table(None if words_arg is True else words_arg)
 
 
-def host_word_shingles(buf, doc_offsets, width: int, table) -> List[List[bytes]]:
-    """The word shingles of every document of a (checked) byte-mode corpus, by :func:`word_shingles`."""
-    raw = buf.tobytes()
-    return [word_shingles(raw[int(doc_offsets[d]): int(doc_offsets[d + 1])], width, table) for d in range(doc_offsets.size - 1)]
-
-
 # ---- what MinHash.bulk_signatures, HyperLogLog.bulk_registers and sha1_windows share ---------------------------------------
 def _as_bytes_array(buf) -> np.ndarray:
     if isinstance(buf, np.ndarray):
@@ -187,7 +182,7 @@ def check_corpus(buf, item_offsets, doc_offsets, width) -> Tuple[np.ndarray, Opt
 
 def window_chunks(set_offsets: np.ndarray, max_docs: int, max_windows: int) -> Iterator[Tuple[int, int]]:
     """(s, e) ranges of whole documents: at most ``max_docs`` of them and about ``max_windows`` windows (one document may exceed
-    that alone)."""
+    that alone).  The one chunker: every bulk call that cuts a CSR corpus into device calls cuts it here."""
     n, s = set_offsets.size - 1, 0
     while s < n:
         e = min(n, s + max_docs)
@@ -219,6 +214,91 @@ def host_shingles(buf, item_offsets, doc_offsets, width: int) -> List[List[bytes
         else:
             out.append(token_shingles([raw[int(item_offsets[i]): int(item_offsets[i + 1])] for i in range(i0, i1)], width))
     return out
+
+
+# ---- a text corpus: how packed=, documents=, shingle= and words= of the bulk calls become sets -------------------------------
+# Three kinds with the same members, so that MinHash.bulk_signatures and HyperLogLog.bulk_registers each have one loop and neither
+# knows which kind it was handed:
+#   chunks(max_sets, max_tokens)   pieces of whole sets (documents), offsets re-based to 0, cut by window_chunks
+#   host_sets()                    the sets of a piece as lists of bytes: what a host hashfunc is applied to
+#   native, arrays()               the device route of a piece: Context.minhash_bulk_<native> / hll_bulk_<native>(**arrays(), ...)
+# All three are stored alike -- bytes, item offsets (None: an item is a byte), document offsets -- and checked by check_corpus.
+class _Corpus:
+    def __init__(self, buf, item_offsets, doc_offsets, width=1):
+        self.buf, self.item_offsets, self.doc_offsets, self.width = check_corpus(buf, item_offsets, doc_offsets, width)
+
+    def chunks(self, max_sets: int, max_tokens: int) -> Iterator["_Corpus"]:
+        for s, e in window_chunks(self.chunk_offsets(), max_sets, max_tokens):
+            piece = copy.copy(self)
+            piece.buf, piece.item_offsets, piece.doc_offsets = corpus_piece(self.buf, self.item_offsets, self.doc_offsets, s, e)
+            yield piece
+
+
+class PackedSets(_Corpus):
+    """``packed=(buf, byte_offsets, set_offsets)``: a set is its tokens."""
+    native = "bytes"
+
+    def chunk_offsets(self) -> np.ndarray:
+        return self.doc_offsets
+
+    def arrays(self) -> dict:
+        return dict(buf=self.buf, byte_offsets=self.item_offsets, set_offsets=self.doc_offsets)
+
+    def host_sets(self) -> List[List[bytes]]:
+        raw, at, sets = self.buf.tobytes(), self.item_offsets.tolist(), self.doc_offsets.tolist()
+        return [[raw[at[i]: at[i + 1]] for i in range(sets[j], sets[j + 1])] for j in range(len(sets) - 1)]
+
+
+class Windows(_Corpus):
+    """``documents=`` or ``packed=`` with ``shingle=width``: a set is the windows of ``width`` bytes or tokens of a document."""
+    native = "windows"
+
+    def chunk_offsets(self) -> np.ndarray:
+        return window_offsets(self.doc_offsets, self.width)  # (a window counts as a token)
+
+    def arrays(self) -> dict:
+        return dict(buf=self.buf, doc_offsets=self.doc_offsets, width=self.width, item_offsets=self.item_offsets)
+
+    def host_sets(self) -> List[List[bytes]]:
+        return host_shingles(self.buf, self.item_offsets, self.doc_offsets, self.width)
+
+
+class WordWindows(_Corpus):
+    """``documents=`` with ``shingle=width`` and ``words=table``: a set is the windows of ``width`` words of a document."""
+    native = "words"
+
+    def __init__(self, buf, doc_offsets, width, table):
+        super().__init__(buf, None, doc_offsets, width)
+        self.table = table
+
+    def chunk_offsets(self) -> np.ndarray:
+        # by bytes: a document has no more windows than words and no more words than bytes, so the bounds hold without knowing
+        # the word counts in advance
+        return self.doc_offsets
+
+    def arrays(self) -> dict:
+        return dict(buf=self.buf, doc_offsets=self.doc_offsets, width=self.width, table=self.table)
+
+    def host_sets(self) -> List[List[bytes]]:
+        raw, docs = self.buf.tobytes(), self.doc_offsets.tolist()
+        return [word_shingles(raw[docs[d]: docs[d + 1]], self.width, self.table) for d in range(len(docs) - 1)]
+
+
+def text_corpus(packed, documents, width, table) -> _Corpus:
+    """The kind of corpus that ``packed=`` / ``documents=``, ``shingle=width`` and ``words=`` (as its table) name."""
+    if documents is not None:
+        buf, doc_offsets = join_documents(documents)
+        return Windows(buf, None, doc_offsets, width) if table is None else WordWindows(buf, doc_offsets, width, table)
+    if not (isinstance(packed, tuple) and len(packed) == 3):
+        raise ValueError("packed is a (buf, byte_offsets, set_offsets) triple")
+    return PackedSets(*packed) if width is None else Windows(*packed, width)
+
+
+def flatten(sets) -> Tuple[list, np.ndarray]:
+    """(every element of every set, in order; the int64 CSR offsets of the sets into them)."""
+    offsets = np.zeros(len(sets) + 1, dtype=np.int64)
+    np.cumsum(np.fromiter(map(len, sets), dtype=np.int64, count=len(sets)), out=offsets[1:])
+    return [t for s in sets for t in s], offsets
 
 
 def sha1_windows(buf, doc_offsets, width: int, item_offsets=None, bits: int = 32, gpu_mode: str = "detect") -> Tuple[np.ndarray, np.ndarray]:

@@ -140,6 +140,27 @@ def test_chunks_of_whole_documents(monkeypatch):
     assert list(shingle.window_chunks(np.array([0, 5, 5, 105, 106, 107]), 2, 50)) == [(0, 2), (2, 3), (3, 5)]
 
 
+def test_the_one_chunker_on_random_offsets():
+    """What every chunked bulk call relies on: the ranges are contiguous, cover [0, n), hold at most max_sets sets, and at most
+    max_tokens tokens unless a range is one set."""
+    rng = np.random.RandomState(11)
+    cases = [(np.zeros(1, dtype=np.int64), 3, 10), (np.zeros(6, dtype=np.int64), 2, 10)]  # no set; empty sets only
+    for trial in range(60):
+        n, max_sets, max_tokens = int(rng.randint(1, 40)), int(rng.randint(1, 9)), int(rng.randint(1, 30))
+        lengths = rng.randint(0, 12, n) * (rng.random_sample(n) < 0.7)  # ~30 % empty sets
+        lengths[rng.randint(n)] = max_tokens + int(rng.randint(1, 50))  # one set larger than max_tokens
+        offsets = np.concatenate([[0], np.cumsum(lengths)]).astype(np.int64)
+        cases.append((offsets + (trial % 2) * 17, max_sets, max_tokens))  # (a CSR pair of hashes need not start at 0)
+    for offsets, max_sets, max_tokens in cases:
+        n, at = offsets.size - 1, 0
+        for s, e in shingle.window_chunks(offsets, max_sets, max_tokens):
+            assert s == at and s < e <= n
+            assert e - s <= max_sets
+            assert offsets[e] - offsets[s] <= max_tokens or e - s == 1
+            at = e
+        assert at == n
+
+
 def test_str_documents_are_shingled_over_their_utf8_bytes():
     docs = ["naïve café", "", "日本語のテキスト", "plain"]
     as_bytes = [d.encode("utf-8") for d in docs]
