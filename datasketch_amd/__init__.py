@@ -9,6 +9,7 @@ from datasketch_amd.b_bit_minhash import bBitMinHash
 from datasketch_amd import lsh_bulk
 from datasketch_amd import hyperloglog
 from datasketch_amd import shingle
+from datasketch_amd import overlap
 from datasketch_amd.hashfunc import prehashed, sha1_hash32, sha1_hash64, sha1_hash_many
 from datasketch_amd.hyperloglog import HyperLogLog
 from datasketch_amd.lean_minhash import LeanMinHash
@@ -40,4 +41,5 @@ __all__ = [
     "hyperloglog",
     "lsh_bulk",
     "shingle",
+    "overlap",
 ]

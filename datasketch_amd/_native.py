@@ -195,6 +195,16 @@ _PROTOTYPES_WORDS = {
     "mhx_minhash_bulk_words_typed": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _int, _vp, _i64, _vp, _int],
     "mhx_hll_bulk_words": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _i64, _vp],
 }
+# Entry points declared MHX_API_OVERLAP (exact overlap counts of listed pairs): an eighth list for the same reason; declared = bound =
+# exported is checked in tests/test_overlap_host.py, the argument checks in tests/test_gpu_overlap.py.
+_PROTOTYPES_OVERLAP = {
+    "mhx_overlap_limits": [_int, _i64, ctypes.POINTER(_i64)],
+    "mhx_overlap_pairs_dev": [_vp, _vp, _int, _vp, _i64, _i64, _vp, _i64, _vp, _vp],
+    "mhx_overlap_pairs": [_vp, _vp, _int, _vp, _i64, _vp, _i64, _vp],
+    "mhx_overlap_pairs_bytes": [_vp, _vp, _vp, _i64, _int, _vp, _i64, _vp, _i64, _vp],
+    "mhx_overlap_pairs_windows": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _vp, _i64, _vp],
+    "mhx_overlap_pairs_words": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _int, _vp, _i64, _vp],
+}
 _RESTYPE = {"mhx_last_error": ctypes.c_char_p, "mhx_version": ctypes.c_char_p}
 
 EXPORTED_SYMBOLS = sorted(list(_PROTOTYPES) + list(_RESTYPE))
@@ -204,6 +214,7 @@ EXPORTED_SYMBOLS_TOPK = sorted(_PROTOTYPES_TOPK)
 EXPORTED_SYMBOLS_CC = sorted(_PROTOTYPES_CC)
 EXPORTED_SYMBOLS_SHINGLE = sorted(_PROTOTYPES_SHINGLE)
 EXPORTED_SYMBOLS_WORDS = sorted(_PROTOTYPES_WORDS)
+EXPORTED_SYMBOLS_OVERLAP = sorted(_PROTOTYPES_OVERLAP)
 
 
 try:  # CPython helper (csrc/pack_module.c): ~10 ns per token instead of ~180 in the interpreter
@@ -244,7 +255,7 @@ def load():
             raise MhxError(_lib_error) from e
         for name, argtypes in (list(_PROTOTYPES.items()) + list(_PROTOTYPES_EXT.items()) + list(_PROTOTYPES_BLOOM.items())
                                + list(_PROTOTYPES_TOPK.items()) + list(_PROTOTYPES_CC.items()) + list(_PROTOTYPES_SHINGLE.items())
-                               + list(_PROTOTYPES_WORDS.items())):
+                               + list(_PROTOTYPES_WORDS.items()) + list(_PROTOTYPES_OVERLAP.items())):
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = _int
@@ -331,6 +342,14 @@ def window_offsets(doc_offsets, width: int) -> np.ndarray:
     out = np.empty(doc_offsets.size, dtype=np.int64)
     check(load().mhx_shingle_window_offsets(_ptr(doc_offsets), doc_offsets.size - 1, int(width), _ptr(out)))
     return out
+
+
+def overlap_limits(bits: int, lds_per_block: int) -> int:
+    """mhx_overlap_limits: the most items (both sets, repeats counted) of a pair whose hash set fits ``lds_per_block`` bytes of LDS
+    at ``bits``-bit keys (pure host logic: the library, no device)."""
+    out = _i64(0)
+    check(load().mhx_overlap_limits(Context._hash_code(bits), int(lds_per_block), ctypes.byref(out)))
+    return int(out.value)
 
 
 class WeightedFeed:
@@ -817,6 +836,65 @@ class Context:
         out = np.empty((n_docs, 1 << int(p)), dtype=np.uint8)
         check(self.lib.mhx_hll_bulk_words(self.handle, _ptr(buf), n_bytes, _ptr(doc_offsets), n_docs, _ptr(table), int(width), int(hash_bits),
                                           int(p), _ptr(init), stride, _ptr(out)))
+        return out
+
+    # -- exact overlap counts of listed pairs (overlap_kernels.hip; datasketch_amd/overlap.py is the definition)
+    @staticmethod
+    def _pairs(pairs) -> np.ndarray:
+        pairs = np.ascontiguousarray(pairs, dtype=np.int64)
+        if pairs.ndim != 2 or pairs.shape[1] != 2:
+            raise ValueError("pairs is an [P, 2] array of set indices")
+        return pairs
+
+    def overlap_pairs(self, hashes: np.ndarray, set_offsets, pairs) -> np.ndarray:
+        """int32 [P, 3] = (|Si n Sj|, |Si|, |Sj|) over distinct values of uint32 / uint64 hashes in CSR sets: mhx_overlap_pairs
+        (host in, host out)."""
+        hashes = np.ascontiguousarray(hashes).reshape(-1)
+        if hashes.dtype not in (np.dtype(np.uint32), np.dtype(np.uint64)):
+            raise ValueError("hashes must be uint32 or uint64")
+        set_offsets = np.ascontiguousarray(set_offsets, dtype=np.int64).reshape(-1)
+        if set_offsets.size < 1 or int(set_offsets[-1]) > hashes.size:
+            raise ValueError("set_offsets has sets + 1 entries and ends inside hashes")
+        pairs = self._pairs(pairs)
+        out = np.empty((pairs.shape[0], 3), dtype=np.int32)
+        check(self.lib.mhx_overlap_pairs(self.handle, _ptr(hashes), MHX_U32 if hashes.dtype == np.uint32 else MHX_U64, _ptr(set_offsets),
+                                         set_offsets.size - 1, _ptr(pairs), pairs.shape[0], _ptr(out)))
+        return out
+
+    def overlap_pairs_dev(self, d_hv: Optional[int], hv_dtype: int, d_set_offsets: Optional[int], n_sets: int, max_set_items: int,
+                          d_pairs: Optional[int], n_pairs: int, d_counts: Optional[int], d_invalid: Optional[int] = None) -> None:
+        """mhx_overlap_pairs_dev on device arrays; enqueued.  ``d_invalid``: an int64 the caller zeroed, or None."""
+        check(self.lib.mhx_overlap_pairs_dev(self.handle, _vp(d_hv), hv_dtype, _vp(d_set_offsets), int(n_sets), int(max_set_items), _vp(d_pairs),
+                                             int(n_pairs), _vp(d_counts), _vp(d_invalid)))
+
+    def overlap_pairs_bytes(self, pairs, buf, byte_offsets, set_offsets, bits: int = 64) -> np.ndarray:
+        """Packed byte tokens -> sha1_hash32 / sha1_hash64 -> exact overlap counts of the listed pairs of sets, all on the device."""
+        code = self._hash_code(bits)
+        buf, byte_offsets, set_offsets = self._bytes_and_offsets(buf, byte_offsets, set_offsets)
+        pairs = self._pairs(pairs)
+        out = np.empty((pairs.shape[0], 3), dtype=np.int32)
+        check(self.lib.mhx_overlap_pairs_bytes(self.handle, _ptr(buf), _ptr(byte_offsets), byte_offsets.size - 1, code, _ptr(set_offsets),
+                                               set_offsets.size - 1, _ptr(pairs), pairs.shape[0], _ptr(out)))
+        return out
+
+    def overlap_pairs_windows(self, pairs, buf, doc_offsets, width: int, item_offsets=None, bits: int = 64) -> np.ndarray:
+        """Text -> shingles -> sha1_hash32 / sha1_hash64 -> exact overlap counts of the listed pairs of documents, all on the device."""
+        code = self._hash_code(bits)
+        buf, item_offsets, doc_offsets, n_items, n_docs = self._windows_corpus(buf, item_offsets, doc_offsets)
+        pairs = self._pairs(pairs)
+        out = np.empty((pairs.shape[0], 3), dtype=np.int32)
+        check(self.lib.mhx_overlap_pairs_windows(self.handle, _ptr(buf), _ptr(item_offsets), n_items, _ptr(doc_offsets), n_docs, int(width), code,
+                                                 _ptr(pairs), pairs.shape[0], _ptr(out)))
+        return out
+
+    def overlap_pairs_words(self, pairs, buf, doc_offsets, width: int, table, bits: int = 64) -> np.ndarray:
+        """Raw text -> words -> w-word shingles -> sha1_hash32 / sha1_hash64 -> exact overlap counts of the listed pairs of documents."""
+        code = self._hash_code(bits)
+        buf, doc_offsets, table, n_bytes, n_docs = self._words_corpus(buf, doc_offsets, table)
+        pairs = self._pairs(pairs)
+        out = np.empty((pairs.shape[0], 3), dtype=np.int32)
+        check(self.lib.mhx_overlap_pairs_words(self.handle, _ptr(buf), n_bytes, _ptr(doc_offsets), n_docs, _ptr(table), int(width), code,
+                                               _ptr(pairs), pairs.shape[0], _ptr(out)))
         return out
 
     def minhash_update_batch(self, permutations, hv: np.ndarray, hashvalues: np.ndarray) -> np.ndarray:

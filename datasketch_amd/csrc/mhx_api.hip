@@ -476,6 +476,7 @@ int mhx_ctx_set_option(mhx_ctx *ctx, const char *key, int64_t value) {
         {"lsh.merge_items", &mhx_ctx::opt_lsh_merge_items}, {"hll.split_tokens", &mhx_ctx::opt_hll_split_tokens},
         {"bloom.lanes", &mhx_ctx::opt_bloom_lanes},         {"jaccard.topk_path", &mhx_ctx::opt_jaccard_topk_path},
         {"jaccard.topk_segments", &mhx_ctx::opt_jaccard_topk_segments}, {"debug.cus", &mhx_ctx::opt_debug_cus},
+        {"overlap.bins", &mhx_ctx::opt_overlap_bins},
     };
     if (!ctx || !key) return fail(MHX_ERR_INVALID, "ctx/key is NULL");
     MHX_GUARD(ctx);
@@ -487,6 +488,7 @@ int mhx_ctx_set_option(mhx_ctx *ctx, const char *key, int64_t value) {
         if (o.field == &mhx_ctx::opt_bloom_lanes) MHX_REQUIRE(value == 0 || value == 1 || value == 16, "bloom.lanes must be 0, 1 or 16");
         if (o.field == &mhx_ctx::opt_jaccard_topk_path) MHX_REQUIRE(value >= 0 && value <= 2, "jaccard.topk_path must be 0, 1 or 2");
         if (o.field == &mhx_ctx::opt_jaccard_topk_segments) MHX_REQUIRE(value >= 0, "jaccard.topk_segments must be >= 0");
+        if (o.field == &mhx_ctx::opt_overlap_bins) MHX_REQUIRE(value >= 0 && value <= 2, "overlap.bins must be 0, 1 or 2");
         if (o.field == &mhx_ctx::opt_debug_cus)
             MHX_REQUIRE(value >= 0 && value <= ctx->hw_cus, "debug.cus must be 0 (the device's %d CUs) or in [1, %d], got %lld", ctx->hw_cus, ctx->hw_cus,
                         (long long)value);
@@ -1014,6 +1016,7 @@ namespace {
 //   reserve(s)               Aux pieces of the source's own in the SINK's Stage, behind init | hashes (one Stage per slot and
 //                            call: a slot that grows is reallocated)
 //   hash(s, dtype, d_hv)     the launches that fill d_hv; d_sets and n_hashes hold from then on
+//   host_sets()              the set offsets on the host, from hash() on: a sink that needs the size of a set reads it here
 
 // packed byte tokens: token i is bytes[byte_offsets[i] .. byte_offsets[i+1]], set j owns tokens set_offsets[j] .. set_offsets[j+1]
 // (set_offsets NULL: the tokens alone, for mhx_sha1_tokens).  Offsets: byte offsets | set offsets.
@@ -1035,6 +1038,7 @@ struct Tokens {
     }
     int64_t n_sets() const { return n; }
     int64_t max_hashes() const { return n_tokens; }
+    const int64_t *host_sets() const { return set_offsets; }
 
     int check_tokens() const {
         MHX_REQUIRE(byte_offsets, "byte_offsets is NULL");
@@ -2311,6 +2315,7 @@ struct Windows {
     int check_sizes() const { return check_windows(n_docs, width); }
     int64_t n_sets() const { return n_docs; }
     int64_t max_hashes() const { return n_hashes; }
+    const int64_t *host_sets() const { return set_offsets.data(); }
 
     int check_arrays() {
         MHX_REQUIRE(n_items >= 0, "n_items must be >= 0");
@@ -2440,6 +2445,7 @@ struct Words {
     }
     int64_t n_sets() const { return n_docs; }
     int64_t max_hashes() const { return n_words; }  // (a document has no more windows than words)
+    const int64_t *host_sets() const { return sets.data(); }  // (from hash() on)
 
     int check_arrays() const {
         MHX_REQUIRE(doc_offsets, "doc_offsets is NULL");
@@ -2523,7 +2529,7 @@ int mhx_words_normalize(mhx_ctx *ctx, const uint8_t *bytes, int64_t n_bytes, con
     return s.synchronize();
 }
 
-// ---- the two sinks, and the six entries: a source constructed, a sink called ------------------------------------------------------
+// ---- the sinks, and their entries: a source constructed, a sink called (the third sink, overlaps_of, is at the end of the file) ---
 extern "C++" {
 namespace {
 
@@ -2780,6 +2786,130 @@ int mhx_cc_pairs(mhx_ctx *ctx, const int64_t *pairs, int64_t n_pairs, const int3
     if (invalid) MHX_TRY(s.download(invalid, p_bad));
     if (n) return s.fetch(labels, p_labels);
     return s.synchronize();
+}
+
+// ---- Exact overlap of listed pairs (overlap_kernels.hip; datasketch_amd/overlap.py is the definition) ------------------------------
+#define MHX_CHECK_OVERLAP_PAIRS(n_pairs) MHX_REQUIRE((n_pairs) >= 0 && (n_pairs) < ((int64_t)1 << 31), "n_pairs must be in [0, 2^31-1]")
+
+int mhx_overlap_limits(int hv_dtype, int64_t lds_per_block, int64_t *lds_max_items) {
+    MHX_REQUIRE(lds_max_items, "lds_max_items is NULL");
+    MHX_CHECK_DTYPE(hv_dtype);
+    MHX_REQUIRE(lds_per_block >= 0, "lds_per_block must be >= 0");
+    *lds_max_items = mhx::overlap_lds_max_items(hv_dtype, lds_per_block);
+    return MHX_OK;
+}
+
+int mhx_overlap_pairs_dev(mhx_ctx *ctx, const void *d_hv, int hv_dtype, const int64_t *d_set_offsets, int64_t n_sets, int64_t max_set_items,
+                          const int64_t *d_pairs, int64_t n_pairs, int32_t *d_counts, int64_t *d_invalid) {
+    MHX_ENTER(ctx, ctx);
+    MHX_CHECK_DTYPE(hv_dtype);
+    MHX_REQUIRE(n_sets >= 0, "n_sets must be >= 0");
+    MHX_CHECK_OVERLAP_PAIRS(n_pairs);
+    MHX_REQUIRE(max_set_items >= 0 && max_set_items < ((int64_t)1 << 31), "max_set_items must be in [0, 2^31-1]: a set has fewer than 2^31 items");
+    if (n_pairs == 0 || n_sets == 0) return MHX_OK;
+    MHX_REQUIRE_POINTERS(d_set_offsets && d_pairs && d_counts && (d_hv || max_set_items == 0), kDevice);
+    MHX_TRY(ctx->activate());
+    return mhx::launch_overlap_pairs(ctx, d_hv, hv_dtype, d_set_offsets, n_sets, max_set_items, d_pairs, n_pairs, d_counts, d_invalid);
+}
+
+extern "C++" {
+namespace {
+
+// the pairs of a host entry against checked offsets: every index in range, and the largest named set (fewer than 2^31 items)
+int check_overlap_pairs(const int64_t *pairs, int64_t n_pairs, const int64_t *set_offsets, int64_t n_sets, int64_t *max_set_items) {
+    for (int64_t e = 0; e < 2 * n_pairs; ++e)
+        MHX_REQUIRE(pairs[e] >= 0 && pairs[e] < n_sets, "pair index out of range (pair %lld: %lld, %lld sets)", (long long)(e / 2),
+                    (long long)pairs[e], (long long)n_sets);
+    int64_t most = 0;
+    for (int64_t e = 0; e < 2 * n_pairs; ++e) most = std::max(most, set_offsets[pairs[e] + 1] - set_offsets[pairs[e]]);
+    MHX_REQUIRE(most < ((int64_t)1 << 31), "a set of 2^31 or more items (%lld)", (long long)most);
+    *max_set_items = most;
+    return MHX_OK;
+}
+
+// the third sink.  Aux: hashes (uint32 or uint64) | whatever the source reserves | pairs;  Out: counts
+template <class Source>
+int overlaps_of(mhx_ctx *ctx, Source &&src, int hash_dtype, const int64_t *pairs, int64_t n_pairs, int32_t *counts) {
+    MHX_REQUIRE(hash_dtype == MHX_U32 || hash_dtype == MHX_U64, "hash_dtype must be MHX_U32 (sha1_hash32) or MHX_U64 (sha1_hash64)");
+    MHX_CHECK_OVERLAP_PAIRS(n_pairs);
+    MHX_TRY(src.check_sizes());
+    if (n_pairs == 0) return MHX_OK;
+    MHX_REQUIRE(pairs && counts, "pairs/counts is NULL");
+    const int64_t n = src.n_sets();
+    MHX_REQUIRE(n > 0, "pair index out of range (the corpus has no set)");
+    for (int64_t e = 0; e < 2 * n_pairs; ++e)
+        MHX_REQUIRE(pairs[e] >= 0 && pairs[e] < n, "pair index out of range (pair %lld: %lld, %lld sets)", (long long)(e / 2), (long long)pairs[e],
+                    (long long)n);
+    MHX_TRY(src.check_arrays());
+    MHX_TRY(ctx->activate());
+    MHX_TRY(src.stage(ctx));
+    Stage s(ctx);
+    const auto p_hv = s.piece(Stage::Aux, (hash_dtype == MHX_U32 ? 4 : 8) * (size_t)src.max_hashes());
+    src.reserve(s);
+    const auto p_pairs = s.piece(Stage::Aux, sizeof(int64_t) * 2 * (size_t)n_pairs);
+    const auto p_out = s.piece(Stage::Out, sizeof(int32_t) * 3 * (size_t)n_pairs);
+    MHX_TRY(s.commit());
+    MHX_TRY(s.upload(p_pairs, pairs));
+    MHX_TRY(src.hash(s, hash_dtype, s.at<void>(p_hv)));
+    int64_t max_set_items = 0;
+    MHX_TRY(check_overlap_pairs(pairs, n_pairs, src.host_sets(), n, &max_set_items));
+    MHX_TRY(mhx::launch_overlap_pairs(ctx, s.at<void>(p_hv), hash_dtype, src.d_sets, n, max_set_items, s.at<int64_t>(p_pairs), n_pairs,
+                                      s.at<int32_t>(p_out), nullptr));
+    return s.fetch(counts, p_out);
+}
+
+}  // namespace
+}  // extern "C++"
+
+int mhx_overlap_pairs(mhx_ctx *ctx, const void *hv, int hv_dtype, const int64_t *set_offsets, int64_t n_sets, const int64_t *pairs,
+                      int64_t n_pairs, int32_t *counts) {
+    MHX_ENTER(ctx, ctx);
+    MHX_CHECK_DTYPE(hv_dtype);
+    MHX_REQUIRE(n_sets >= 0, "n_sets must be >= 0");
+    MHX_CHECK_OVERLAP_PAIRS(n_pairs);
+    if (n_pairs == 0) return MHX_OK;
+    MHX_REQUIRE_POINTERS(pairs && counts, kHost);
+    MHX_REQUIRE(n_sets > 0, "pair index out of range (there is no set)");
+    MHX_REQUIRE_POINTERS(set_offsets, kHost);
+    MHX_REQUIRE(set_offsets[0] == 0, "set_offsets[0] must be 0");
+    for (int64_t i = 0; i < n_sets; ++i)
+        MHX_REQUIRE(set_offsets[i + 1] >= set_offsets[i], "set_offsets must be non-decreasing (set %lld)", (long long)i);
+    const int64_t total = set_offsets[n_sets];
+    MHX_REQUIRE_POINTERS(hv || total == 0, kHost);
+    int64_t max_set_items = 0;
+    MHX_TRY(check_overlap_pairs(pairs, n_pairs, set_offsets, n_sets, &max_set_items));
+    MHX_TRY(ctx->activate());
+    Stage s(ctx);
+    const auto p_hv = s.piece(Stage::In, (hv_dtype == MHX_U32 ? 4 : 8) * (size_t)total);
+    if (total == 0) s.ask(Stage::In, 8);
+    const auto p_sets = s.piece(Stage::Offsets, sizeof(int64_t) * (size_t)(n_sets + 1));
+    const auto p_pairs = s.piece(Stage::Aux, sizeof(int64_t) * 2 * (size_t)n_pairs);
+    const auto p_out = s.piece(Stage::Out, sizeof(int32_t) * 3 * (size_t)n_pairs);
+    MHX_TRY(s.commit());
+    MHX_TRY(s.upload(p_hv, hv));
+    MHX_TRY(s.upload(p_sets, set_offsets));
+    MHX_TRY(s.upload(p_pairs, pairs));
+    MHX_TRY(mhx::launch_overlap_pairs(ctx, s.at<void>(p_hv), hv_dtype, s.at<int64_t>(p_sets), n_sets, max_set_items, s.at<int64_t>(p_pairs),
+                                      n_pairs, s.at<int32_t>(p_out), nullptr));
+    return s.fetch(counts, p_out);
+}
+
+int mhx_overlap_pairs_bytes(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens, int hash_dtype,
+                            const int64_t *set_offsets, int64_t n_sets, const int64_t *pairs, int64_t n_pairs, int32_t *counts) {
+    MHX_ENTER(ctx, ctx);
+    return overlaps_of(ctx, Tokens{bytes, byte_offsets, n_tokens, set_offsets, n_sets, /*aux_slack*/ 0}, hash_dtype, pairs, n_pairs, counts);
+}
+
+int mhx_overlap_pairs_windows(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items, const int64_t *doc_offsets,
+                              int64_t n_docs, int64_t width, int hash_dtype, const int64_t *pairs, int64_t n_pairs, int32_t *counts) {
+    MHX_ENTER(ctx, ctx);
+    return overlaps_of(ctx, Windows{bytes, item_offsets, n_items, doc_offsets, n_docs, width}, hash_dtype, pairs, n_pairs, counts);
+}
+
+int mhx_overlap_pairs_words(mhx_ctx *ctx, const uint8_t *bytes, int64_t n_bytes, const int64_t *doc_offsets, int64_t n_docs,
+                            const uint8_t *table, int64_t width, int hash_dtype, const int64_t *pairs, int64_t n_pairs, int32_t *counts) {
+    MHX_ENTER(ctx, ctx);
+    return overlaps_of(ctx, Words{bytes, n_bytes, doc_offsets, n_docs, table, width}, hash_dtype, pairs, n_pairs, counts);
 }
 
 }  // extern "C"

@@ -105,6 +105,7 @@ struct mhx_ctx {
     int64_t opt_bloom_lanes = 0;      // mhx_bloom_*: lanes per (row, band): 0 auto (insert 16: one lane per word of the block; query 1), 1 or 16 = both operations that way
     int64_t opt_jaccard_topk_path = 0;     // mhx_*jaccard_topk*: 0 auto (dense rows and few probes: the stream kernel), 1 strip kernel, 2 stream kernel wherever it exists (dense rows; b-bit rows always take the strip kernel) (A/B, tests)
     int64_t opt_jaccard_topk_segments = 0; // mhx_*jaccard_topk*: segments B is cut into: 0 auto (enough to fill the machine), n >= 1 = n, clamped to the number of 128-row tiles of B (tests)
+    int64_t opt_overlap_bins = 0;          // mhx_overlap_*: 0 auto (LDS pairs binned by table size, one launch per bin, one wave per pair in the smallest bin), 1 = one launch sized for the largest, 2 = bins, a workgroup per pair in every bin (A/B)
     int64_t opt_host_chunk_bytes = 0;  // mhx_minhash_bulk: bytes per pipelined piece; 0 auto (96 MiB, inputs > 256 MiB), < 0 never pipeline; mhx_*jaccard_topk (host forms): > 0 = bytes of B per row block, else 256 MiB
 
     // copy streams of the pipelined host entry point (created on first use)
@@ -279,6 +280,12 @@ int launch_cc_link_pairs(mhx_ctx *ctx, uint32_t *d_labels, int64_t n, const int6
 int launch_cc_link_bands(mhx_ctx *ctx, uint32_t *d_labels, int64_t n, const uint64_t *d_sorted_digests, const uint32_t *d_sorted_rows,
                          int64_t n_sigs, int32_t bands, int64_t *d_invalid);
 int launch_cc_finish(mhx_ctx *ctx, uint32_t *d_labels, int64_t n);
+
+// overlap_kernels.hip: exact overlap counts of listed pairs of hashed sets (mhx_overlap_*).  The launcher enqueues only; its
+// pair lists and the tables of its global class live in scratch[4].  d_invalid may be nullptr.
+int64_t overlap_lds_max_items(int hv_dtype, int64_t lds_per_block);  // the most items (both sets, repeats counted) of an LDS-class pair
+int launch_overlap_pairs(mhx_ctx *ctx, const void *d_hv, int hv_dtype, const int64_t *d_set_offsets, int64_t n_sets, int64_t max_set_items,
+                         const int64_t *d_pairs, int64_t n_pairs, int32_t *d_counts, int64_t *d_invalid);
 
 int bbit_slot_size(int b);
 

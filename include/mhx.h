@@ -119,7 +119,10 @@ MHX_API int mhx_ctx_device_info(mhx_ctx *ctx, char *name, int name_len, int *cus
  * ("hll.split_tokens", mhx_hll_bulk*: a set with more tokens than this is split over several workgroups and combined by a max,
  * 0 auto = 32768; results unaffected),
  * ("bloom.lanes", mhx_bloom_*: lanes per (row, band), 0 auto = 16 for the insert (one lane per word of the block) and 1 for the query, the faster
- * mapping of each; 1 / 16 = both operations that way; results unaffected). */
+ * mapping of each; 1 / 16 = both operations that way; results unaffected),
+ * ("overlap.bins", mhx_overlap_*: 0 auto = pairs whose table fits LDS are binned by table size, each bin is a launch with that
+ * much dynamic LDS and the pairs of the smallest bin get one wave each, 1 = one launch sized for the largest table of the call,
+ * 2 = the bins of 0 with a workgroup per pair in every bin; results unaffected). */
 MHX_API int mhx_ctx_set_option(mhx_ctx *ctx, const char *key, int64_t value);
 /* Kernel event counters since the last call (synchronises the stream, then resets them):
  *   out[0] sets the sieve launch left to the full launch (failed proof, or skipped by the back-off),
@@ -822,6 +825,52 @@ MHX_API_WORDS int mhx_minhash_bulk_words_typed(mhx_perm *perm, const uint8_t *by
 MHX_API_WORDS int mhx_hll_bulk_words(mhx_ctx *ctx, const uint8_t *bytes, int64_t n_bytes, const int64_t *doc_offsets, int64_t n_docs,
                                      const uint8_t *table, int64_t width, int32_t hash_bits, int32_t p, const uint8_t *init,
                                      int64_t init_stride, uint8_t *out);
+
+/* ---- Exact overlap of listed pairs: the verification step of deduplication ---------------------------------------------------
+ * Not in the reference; datasketch_amd/overlap.py (overlap_counts_host: Python sets) is the definition.  Set i is
+ * hv[set_offsets[i] .. set_offsets[i + 1]) of hv_dtype (MHX_U32 / MHX_U64) -- the arrays mhx_minhash_bulk_dev takes; values may
+ * repeat and any value may occur, 0 and all ones included.  For pair p = (pairs[2p], pairs[2p + 1]) = (i, j) the call writes three
+ * int32 counts of DISTINCT values,
+ *   counts[3p .. 3p + 2] = ( |Si n Sj|, |Si|, |Sj| ),
+ * from which union = a + b - inter, Jaccard = inter / union and containment = inter / a follow (both 1.0 at 0 / 0 by the
+ * convention of overlap.py).  i == j gives (a, a, a); pairs may repeat and come in any order.  Everything is exact on the hashed
+ * values: no sketch is involved.  One workgroup per pair (one wave for a pair of up to 512 items) builds a hash set of the pair in
+ * LDS (overlap_kernels.hip); a pair of more items than mhx_overlap_limits names builds it in device scratch instead.  n_pairs <
+ * 2^31; a set has fewer than 2^31 items.
+ *
+ * Exported through MHX_API_OVERLAP (the same visibility as MHX_API), bound from _native._PROTOTYPES_OVERLAP; declared = bound =
+ * exported is checked in tests/test_overlap_host.py, the argument checks in tests/test_gpu_overlap.py. */
+#define MHX_API_OVERLAP __attribute__((visibility("default")))
+/* Pure host logic, no device: *lds_max_items = the largest number of items of a pair (both sets, repeats counted) whose table --
+ * a 64-byte header, the power of two >= max(64, 2 items) of keys of hv_dtype, two bits per slot -- fits lds_per_block bytes
+ * (0: none does).  lds_per_block >= 0. */
+MHX_API_OVERLAP int mhx_overlap_limits(int hv_dtype, int64_t lds_per_block, int64_t *lds_max_items);
+/* Device arrays, enqueued on the ctx stream, no synchronisation (pair lists and large tables live in the context's scratch, which
+ * may grow).  max_set_items, in [0, 2^31 - 1], is the caller's bound on the items of any one named set: it sizes the tables of the
+ * large pairs.  A pair with an index outside [0, n_sets) or a set of more than max_set_items items is never followed: its counts
+ * are (-1, -1, -1) and it adds one to *d_invalid, an int64 on the device that the caller zeroes (may be NULL).  The offsets are
+ * otherwise TRUSTED.  n_pairs == 0 or n_sets == 0 launches nothing and needs no pointers. */
+MHX_API_OVERLAP int mhx_overlap_pairs_dev(mhx_ctx *ctx, const void *d_hv, int hv_dtype, const int64_t *d_set_offsets, int64_t n_sets,
+                                          int64_t max_set_items, const int64_t *d_pairs, int64_t n_pairs, int32_t *d_counts,
+                                          int64_t *d_invalid);
+/* Host arrays, blocking, checked: set_offsets starts at 0 and never decreases, every pair index is in [0, n_sets) and every named
+ * set has fewer than 2^31 items -- MHX_ERR_INVALID otherwise, and nothing is written.  n_pairs == 0 is a no-op. */
+MHX_API_OVERLAP int mhx_overlap_pairs(mhx_ctx *ctx, const void *hv, int hv_dtype, const int64_t *set_offsets, int64_t n_sets,
+                                      const int64_t *pairs, int64_t n_pairs, int32_t *counts);
+/* Text in, counts out: the third sink beside the MinHash and HyperLogLog twins -- the corpus goes up once, is hashed on the device
+ * with sha1_hash32 / sha1_hash64 (hash_dtype) and the pair kernels read the hashes where they lie; only the counts come back.
+ * A set is the tokens of a `packed=` triple (bytes), the windows of a document (windows) or its w-word shingles (words); the
+ * corpus arguments are those of mhx_minhash_bulk_bytes_typed, mhx_minhash_bulk_windows_typed and mhx_minhash_bulk_words_typed and
+ * are checked as there; the pairs as in mhx_overlap_pairs, against the number of sets / documents. */
+MHX_API_OVERLAP int mhx_overlap_pairs_bytes(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens, int hash_dtype,
+                                            const int64_t *set_offsets, int64_t n_sets, const int64_t *pairs, int64_t n_pairs,
+                                            int32_t *counts);
+MHX_API_OVERLAP int mhx_overlap_pairs_windows(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items,
+                                              const int64_t *doc_offsets, int64_t n_docs, int64_t width, int hash_dtype,
+                                              const int64_t *pairs, int64_t n_pairs, int32_t *counts);
+MHX_API_OVERLAP int mhx_overlap_pairs_words(mhx_ctx *ctx, const uint8_t *bytes, int64_t n_bytes, const int64_t *doc_offsets, int64_t n_docs,
+                                            const uint8_t *table, int64_t width, int hash_dtype, const int64_t *pairs, int64_t n_pairs,
+                                            int32_t *counts);
 
 /* ---- Multi-GPU: assemble the signature matrix (RCCL over xGMI) ----------------------------- */
 /* 128-byte RCCL unique id, created on rank 0 and distributed by the caller (env, file, socket). */
