@@ -20,8 +20,8 @@
  *   - device buffers handed to "_dev" entry points need NO slack: a kernel reads and writes only the bytes
  *     the argument list describes ([n_sigs, num_perm] elements, offsets[n_sets] tokens ...), and pointers need
  *     only the natural alignment of their element type (wider loads are used where the pointer allows them).
- *     tests/test_guard_pages.py holds the kernels to this with mhx_debug_guard_alloc (an unmapped page right
- *     behind -- or in front of -- every buffer).
+ *     tests/test_guard_pages.py and the `*_guard_cases.py` scripts hold the kernels to this with
+ *     mhx_debug_guard_alloc (an unmapped page right behind -- or in front of -- every buffer).
  *   - citations "ref:" are paths in the reference repository (ekzhu/datasketch v1.10.0).
  */
 #ifndef MHX_H_

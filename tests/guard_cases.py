@@ -1,5 +1,10 @@
-"""Every device entry point of include/mhx.h on buffers that abut an unmapped page (test infrastructure, run as a
-script in a process of its own by tests/test_guard_pages.py -- a kernel that over-reads kills the process).
+"""The MinHash, SHA-1, weighted, packing, bucketing, candidate-pair, bulk-query, listed-pair and Lean-record device entry
+points of include/mhx.h on buffers that abut an unmapped page (test infrastructure, run as a script in a process of its
+own by tests/test_guard_pages.py -- a kernel that over-reads kills the process).  The other `_dev` entry points have
+sibling scripts that borrow the helpers below, each with a driver of its own: jaccard_matrix_guard_cases.py (all-pairs
+matrix and threshold), jaccard_topk_guard_cases.py, index_guard_cases.py (bands merge, compaction, digest layouts, the
+fused pack), forest_ensemble_guard_cases.py, bloom_, hll_, cc_, shingle_, words_ and overlap_guard_cases.py;
+tests/test_guard_ledger.py fails when include/mhx.h declares a `_dev` entry point that none of them calls.
 
     python tests/guard_cases.py <align>            all cases; prints "GUARD OK <n> cases" and exits 0
     python tests/guard_cases.py <align> layout     the positive control, by query alone: the byte past every buffer's edge
@@ -27,6 +32,12 @@ from oracle import oracle as O  # noqa: E402
 _i64 = ctypes.c_int64
 CASES = 0
 BETWEEN = None  # tests/poison_cases.py: called with the name of every finished case, before the next one starts
+
+
+def _begin(name):
+    """The sibling scripts name a case before its call too: the last line of a child that died names what was running."""
+    if os.environ.get("GUARD_VERBOSE"):
+        print("case", name, flush=True)
 
 
 def _done(name):

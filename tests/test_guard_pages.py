@@ -5,9 +5,13 @@ page-aligned addresses -- the signature of a read just past a mapping -- and no 
 layout-dependent over-read.  These tests can: mhx_debug_guard_alloc (include/mhx.h) maps every device allocation of the
 library with the HIP virtual-memory API so that its last (or first) byte abuts an UNMAPPED page, and
 
-  * tests/guard_cases.py drives every `_dev` entry point -- MinHash dense / CSR with ragged tails / uint32, the dedup and
-    pairwise launches, SHA-1, weighted dense / CSR / every-element, b-bit pack, band keys / digests, both sorts, candidate
-    pairs, bulk query, Jaccard, Lean records -- on exact-size buffers, checking the results as well;
+  * tests/guard_cases.py drives the `_dev` entry points of the first rounds -- MinHash dense / CSR with ragged tails / uint32,
+    the dedup and pairwise launches, SHA-1, weighted dense / CSR / every-element, b-bit pack, band keys / digests, both sorts,
+    candidate pairs, bulk query, Jaccard of listed pairs, Lean records -- on exact-size buffers, checking the results as well;
+  * its sibling scripts do the same for the entry points added since, each run by a driver of its own that borrows `_run` and
+    the `vmm` fixture from here: jaccard_matrix_, jaccard_topk_, index_, forest_ensemble_, bloom_, hll_, cc_, shingle_, words_
+    and overlap_guard_cases.py (tests/test_gpu_*_guard.py); tests/test_guard_ledger.py checks that every `_dev` entry point
+    of include/mhx.h is called in one of them;
   * the GPU parity suite itself runs once more with MHX_GUARD_ALLOC set (its host entry points then stage through
     exact-size guarded scratch).
 
