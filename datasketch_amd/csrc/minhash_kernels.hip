@@ -281,7 +281,8 @@ __device__ __forceinline__ void hash_range(const TokT MHX_CONST_AS *hv, int64_t 
 // tokens is cut into rows of 16 consecutive tokens and the hot loop only keeps min M per row: one
 // v_mad_u64_u32 per pair and one v_min3_u32 per TWO pairs, instead of two multiplies, shift, add
 // and half a min3.  Finished rows are tagged with their index in the low 4 bits (key & ~15 | row)
-// and folded into the two smallest tagged values k1 < k2; k2 - k1 >= 32 proves that every token
+// and folded into the two smallest tagged values k1 < k2 (four rows at a time where that costs no register: Two::add4,
+// kFold4); k2 - k1 >= 32 proves that every token
 // outside the best row has M >= min M + 17.  The best row is then rescanned (16 keys, the same
 // k1/k2 fold over the column index): if its two smallest keys are also >= 32 apart, (best row,
 // best column) is the ONLY token with M <= min M + 16: it alone is hashed exactly.  The rescan
@@ -337,6 +338,16 @@ struct Two {
     __device__ __forceinline__ void add(uint32_t key) {
         k2 = umed3(k1, k2, key);
         k1 = min(k1, key);
+    }
+    // Four keys at once: 5 instructions where four add() take 8.  The largest of {x1, x2, x3} has two values at or below
+    // it, so it is never among the two smallest of the six; the smallest is the smallest of the three group leaders
+    // (k1, L, x4), the second smallest the smallest of {second of the leaders, k2, Mi}.  min3 / med3 order multisets:
+    // equal keys (the 2^32-1 a record starts from) come out as they do from four add().
+    __device__ __forceinline__ void add4(uint32_t x1, uint32_t x2, uint32_t x3, uint32_t x4) {
+        const uint32_t L = umin3(x1, x2, x3), Mi = umed3(x1, x2, x3);
+        const uint32_t t = umed3(k1, L, x4);
+        k1 = umin3(k1, L, x4);
+        k2 = umin3(k2, Mi, t);
     }
     __device__ __forceinline__ bool apart() const { return k2 - k1 >= 32u; }  // k2 >= k1 always
     __device__ __forceinline__ void merge_from_lane(int other) {  // this record and lane `other`'s (over disjoint rows)
@@ -548,6 +559,14 @@ __device__ __forceinline__ void share_last_slot(Rows &rec, const uint32_t *tile,
     for (uint32_t s = span; s < (uint32_t)kWave; s <<= 1) rec.merge_from_lane(lane ^ (int)s);
 }
 
+// Which row loops fold four rows at a time (Two::add4): those whose kernels pay no register for it -- no scratch, no more
+// spilled SGPRs, no wave per SIMD fewer (tools/kernel_regs.py; DESIGN.md section 3 lists the cases).  Three, the tie-tolerant
+// record, keeps its fold.
+template <int P, typename TokT, bool TIES, bool SHARE>
+constexpr bool kFold4 = !TIES && sizeof(TokT) == 8 && (P == 2 || (SHARE && P >= 3));  // sieve_range
+template <typename TokT>
+constexpr bool kDedupFold4 = sizeof(TokT) == 8;  // dedup_sieve_range
+
 // Exact minima over the first nrows*16 tokens of [beg, ...) into res (min-combined); returns true
 // in lanes whose proof failed (the caller redoes the range).  All arguments wave-uniform except the
 // per-lane permutation registers.
@@ -583,9 +602,8 @@ __device__ __forceinline__ bool sieve_range(const TokT MHX_CONST_AS *hv, const T
         const auto row_loop = [&](auto slots) {
             constexpr int PS = decltype(slots)::value;
             if constexpr (CPR == 2) {
-                // uint64 tokens: a row is the chunk pair (a, b); one row per iteration, nothing conditional
-                for (int r = 0; r < rb; ++r) {
-                    uint32_t row0[P];
+                // uint64 tokens: a row is the chunk pair (a, b), nothing conditional
+                const auto one_row = [&](uint32_t (&row0)[P]) {
                     a.arrived();
                     b.load(chunk_ptr(ci + 1));
                     __builtin_amdgcn_sched_barrier(0);
@@ -595,6 +613,31 @@ __device__ __forceinline__ bool sieve_range(const TokT MHX_CONST_AS *hv, const T
                     __builtin_amdgcn_sched_barrier(0);
                     sieve_chunk<P, TokT, false, PS>(b, sp, row0);
                     ci += 2;
+                };
+                int r = 0;
+                if constexpr (kFold4<P, TokT, TIES, SHARE>) {
+                    // Four rows at a time: their tagged minima go into the record with one add4 -- 4 tags + 5 instead of
+                    // 4 tags + 8 instructions per permutation.  The four row numbers are separate wave-uniform values the
+                    // optimiser cannot merge: derived from one another (r | 1, ...) most of the tags become v_and_b32 +
+                    // v_or3_b32 instead of one v_and_or_b32 with a scalar operand.
+                    for (; r + 4 <= rb; r += 4) {
+                        uint32_t tagged[4][P];
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            uint32_t row0[P];
+                            one_row(row0);
+                            uint32_t rj = (uint32_t)(r + j);
+                            asm("" : "+s"(rj));
+#pragma unroll
+                            for (int q = 0; q < PS; ++q) tagged[j][q] = tag16(row0[q], rj);
+                        }
+#pragma unroll
+                        for (int q = 0; q < PS; ++q) rows[q].add4(tagged[0][q], tagged[1][q], tagged[2][q], tagged[3][q]);
+                    }
+                }
+                for (; r < rb; ++r) {  // the rows left over (all of them where the record keeps the one-row fold)
+                    uint32_t row0[P];
+                    one_row(row0);
 #pragma unroll
                     for (int q = 0; q < PS; ++q) rows[q].add(tag16(row0[q], (uint32_t)r));
                 }
@@ -745,9 +788,8 @@ __device__ __forceinline__ bool dedup_sieve_range(const TokT *hv_vec, int64_t be
         // sieve over the rows of the compacted tile: wave-uniform LDS addresses = broadcast reads
         const int nrows = kept >> 4, rest = kept & 15;
         Two rows[P];
-        for (int r = 0; r < nrows; ++r) {
+        const auto row_minima = [&](int r, uint32_t (&row)[P]) {
             const uint4 *rowq = reinterpret_cast<const uint4 *>(tile + r * STRIDE);
-            uint32_t row[P];
 #pragma unroll
             for (int half = 0; half < 2; ++half) {
                 uint4 two[4];
@@ -764,6 +806,27 @@ __device__ __forceinline__ bool dedup_sieve_range(const TokT *hv_vec, int64_t be
                 }
                 __builtin_amdgcn_sched_barrier(0);  // eight tokens in registers at a time
             }
+        };
+        int r = 0;
+        if constexpr (kDedupFold4<TokT>) {  // four rows at a time, as in sieve_range
+            for (; r + 4 <= nrows; r += 4) {
+                uint32_t tagged[4][P];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    uint32_t row[P];
+                    row_minima(r + j, row);
+                    uint32_t rj = (uint32_t)(r + j);
+                    asm("" : "+s"(rj));
+#pragma unroll
+                    for (int q = 0; q < P; ++q) tagged[j][q] = tag16(row[q], rj);
+                }
+#pragma unroll
+                for (int q = 0; q < P; ++q) rows[q].add4(tagged[0][q], tagged[1][q], tagged[2][q], tagged[3][q]);
+            }
+        }
+        for (; r < nrows; ++r) {
+            uint32_t row[P];
+            row_minima(r, row);
 #pragma unroll
             for (int q = 0; q < P; ++q) rows[q].add(tag16(row[q], (uint32_t)r));
         }

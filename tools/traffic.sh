@@ -8,7 +8,8 @@ mkdir -p "${OUT}"
 export TMPDIR=/tmp
 pass() { local name="$1"; shift
   timeout 90 rocprofv3 --pmc "$@" -d "${OUT}/${name}" -o pmc -- python tools/traffic_probe.py > "${OUT}/${name}.log" 2>&1
-  echo "${name} rc=$?"; }
+  local rc=$?; echo "${name} rc=${rc}"
+  [[ ${rc} -eq 0 ]] || exit "${rc}"; }  # nothing more on a GPU after a pass that failed
 pass rd  TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum TCC_EA0_RDREQ_DRAM_sum
 pass wr  TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum TCC_EA0_WRREQ_DRAM_sum
 pass fetch FETCH_SIZE
