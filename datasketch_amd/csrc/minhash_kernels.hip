@@ -102,6 +102,27 @@ __device__ __forceinline__ uint32_t fold_fast(uint32_t s_lo, uint32_t s_hi) {
     return s_lo + (s_hi >> 29);
 }
 
+// Exact fold of a candidate that a sieve proof covers: two instructions instead of eight.  A passing proof puts the
+// candidate's key M = lo32(s_lo + 8) into [16, 2^32 - 1] (finish_block: cols.k1 >= 16; finish_block_ties: see there), so
+// 8 <= s_lo <= 2^32 - 9.  With top = s >> 61 <= 7 then
+//   * s_lo + top <= 2^32 - 2: nothing carries out of the low word, so low61(s) + top == (hi29 << 32) + (s_lo + top);
+//   * that is at most (2^29 - 1) * 2^32 + 2^32 - 2 == 2^61 - 2 < p: the "-p" correction of fold_exact is 0.
+// Hence fold_exact(s) == s_lo + top, exactly.  Without the guard it is false (s_lo = 2^32 - 3, top = 5, hi29 = 2^29 - 1:
+// M = 5, the sum carries up to 2^61 + 1 >= p and the correction is due), which is why this is used ONLY where a failed
+// proof keeps the value out of memory: the set is deferred and its store is skipped.  tests/proven_fold_check.cpp checks
+// the identity and the counter-example on the host.
+// (The same two instructions as fold_fast above; the two differ in contract, not in code: fold_fast takes s + 1 and
+// yields a value that is exact minus one unless it is <= 7, fold_proven takes s itself under a proof and is exact.)
+__device__ __forceinline__ uint32_t fold_proven(uint32_t s_lo, uint32_t s_hi) {
+    return s_lo + (s_hi >> 29);
+}
+
+// SHORT: the kernel took the short fold (kShortFold, by the register rule of DESIGN.md section 3)
+template <bool SHORT>
+__device__ __forceinline__ uint32_t fold_candidate(uint32_t s_lo, uint32_t s_hi) {
+    return SHORT ? fold_proven(s_lo, s_hi) : fold_exact(s_lo, s_hi);
+}
+
 template <bool EXACT>
 __device__ __forceinline__ uint32_t fold(uint32_t s_lo, uint32_t s_hi) {
     return EXACT ? fold_exact(s_lo, s_hi) : fold_fast(s_lo, s_hi);
@@ -404,7 +425,13 @@ __device__ __forceinline__ void sieve_chunk(const Chunk<TokT> &c, const SievePer
 // WPT dwords per token), prove uniqueness, hash the one candidate exactly.  Returns the lanes whose
 // proof failed.  PARTIAL: row `last_row` holds only `last_cols` tokens (the dedup launch's compacted tile);
 // the cells behind them are stale and their keys are replaced by 2^32-1.
-template <int P, int STRIDE, int WPT, bool PARTIAL = false>
+// The candidate's hash needs no Mersenne correction (SHORT, fold_proven): the value counts only where ok holds, ok
+// includes cols[q].k1 >= 16, the tag leaves the key's upper 28 bits alone, so the candidate's key M is >= 16 and
+// s_lo = M - 8 lies in [8, 2^32 - 9]: s_lo + top cannot carry and low61(s) + top stays below 2^61 - 1.  Where ok does not
+// hold the lane reports a failure (or holds no permutation), the caller defers the set or leaves the lane out of the
+// store: the value never reaches memory.  The same holds for PARTIAL: a masked cell's key 2^32-1 as the best key fails
+// cols[q].apart().
+template <int P, int STRIDE, int WPT, bool PARTIAL = false, bool SHORT = true>
 __device__ __forceinline__ bool finish_block(const Two (&rows)[P], const uint32_t *tile, const Perms<P> &pm,
                                              const SievePerms<P> &sp, uint32_t (&res)[P], uint32_t last_row = 16,
                                              uint32_t last_cols = 16) {
@@ -455,7 +482,8 @@ __device__ __forceinline__ bool finish_block(const Two (&rows)[P], const uint32_
                 cols[q].add(tag16(m, (uint32_t)c));
             }
         }
-        const uint32_t j1 = cols[q].k1 & 15u;
+        uint32_t j1 = cols[q].k1 & 15u;
+        asm("" : "+v"(j1));  // the column first, then one shift-add onto the row's address (not shift, mask, add)
         best[q] = WPT == 2 ? *reinterpret_cast<const uint64_t *>(rowp + 2 * j1) : (uint64_t)rowp[j1];
         __builtin_amdgcn_sched_barrier(0);  // one permutation's 16 LDS words at a time (registers)
     }
@@ -466,7 +494,7 @@ __device__ __forceinline__ bool finish_block(const Two (&rows)[P], const uint32_
         fail |= sp.active[q] && !ok;
         uint32_t l0, h0;
         mad_wide((uint32_t)best[q], (uint32_t)(best[q] >> 32), pm.a_lo[q], pm.a_hi[q], pm.b[q], l0, h0);
-        res[q] = min(res[q], fold_exact(l0, h0));
+        res[q] = min(res[q], fold_candidate<SHORT>(l0, h0));  // exact where ok; where not, the set is deferred and res never stored
     }
     return fail;
 }
@@ -481,7 +509,7 @@ __device__ __forceinline__ bool finish_block(const Two (&rows)[P], const uint32_
 // the first launch on real token lists -- and two genuinely close keys, at ~1.2x the instructions of the plain sieve
 // instead of the dedup pass's 1.55x.  Three or more in the window (a token occurring three times): the set goes on
 // to the dedup pass.  (Keys near 2^32 are refused so that the 2^32-1 a fold starts from never looks like a tie.)
-template <int P, int STRIDE, int WPT>
+template <int P, int STRIDE, int WPT, bool SHORT = true>
 __device__ __forceinline__ bool finish_block_ties(const Three (&rows)[P], const uint32_t *tile, const Perms<P> &pm,
                                                   const SievePerms<P> &sp, uint32_t (&res)[P], bool *tied = nullptr) {
     bool fail = false;
@@ -522,7 +550,11 @@ __device__ __forceinline__ bool finish_block_ties(const Three (&rows)[P], const 
         uint32_t l0, h0, l1, h1;
         mad_wide((uint32_t)t1, (uint32_t)(t1 >> 32), pm.a_lo[q], pm.a_hi[q], pm.b[q], l0, h0);
         mad_wide((uint32_t)t2, (uint32_t)(t2 >> 32), pm.a_lo[q], pm.a_hi[q], pm.b[q], l1, h1);
-        res[q] = umin3(res[q], fold_exact(l0, h0), fold_exact(l1, h1));
+        // Both candidates are covered by the proof: ok has 16 <= base <= 0xFFFFFF00, t1's key is rows[q].k1's, in
+        // [base, base + 16), and t2 is t1 again or the cell of cols.k2 (col_tie) or of rows[q].k2 (row_tie), whose tagged
+        // key is below base + 32 and a multiple of 16 away from its key's: both keys lie in [16, 2^32 - 0xE0), which is
+        // what fold_proven needs.  Where ok is false the value is never stored (fail defers the set).
+        res[q] = umin3(res[q], fold_candidate<SHORT>(l0, h0), fold_candidate<SHORT>(l1, h1));
         __builtin_amdgcn_sched_barrier(0);  // one permutation at a time (registers)
     }
     return fail;
@@ -566,11 +598,14 @@ template <int P, typename TokT, bool TIES, bool SHARE>
 constexpr bool kFold4 = !TIES && sizeof(TokT) == 8 && (P == 2 || (SHARE && P >= 3));  // sieve_range
 template <typename TokT>
 constexpr bool kDedupFold4 = sizeof(TokT) == 8;  // dedup_sieve_range
+// Which sieve_range stages the tile's rows beyond the block without zeroing them first (same rule, same table)
+template <int P, bool TIES, bool SHARE>
+constexpr bool kStageNoFill = !(TIES && SHARE && P == 4);
 
 // Exact minima over the first nrows*16 tokens of [beg, ...) into res (min-combined); returns true
 // in lanes whose proof failed (the caller redoes the range).  All arguments wave-uniform except the
 // per-lane permutation registers.
-template <int P, typename TokT, bool TIES = false, bool SHARE = false>
+template <int P, typename TokT, bool TIES = false, bool SHARE = false, bool SHORT = true>
 __device__ __forceinline__ bool sieve_range(const TokT MHX_CONST_AS *hv, const TokT *hv_vec, int64_t beg,
                                             int nrows, const Perms<P> &pm, const SievePerms<P> &sp,
                                             uint32_t *lds, int lane, uint32_t (&res)[P], int &nblocks, bool *tied = nullptr) {
@@ -590,7 +625,25 @@ __device__ __forceinline__ bool sieve_range(const TokT MHX_CONST_AS *hv, const T
         // the block's tokens for the LDS tile: lane l carries 4 tokens (a quarter row); requested now,
         // needed after the row loop
         const int my_row = lane >> 2, my_part = lane & 3;
-        uint4 st0 = {0, 0, 0, 0}, st1 = {0, 0, 0, 0};
+        // Rows at or beyond rb are not loaded and not zeroed: the tile gets whatever the lane's registers hold there ("stale"
+        // below), and no reader lets that reach a result or a flag.  finish_block and the first row of finish_block_ties read row
+        // (k1 & 15) of a record that holds a tagged key of every row < rb, all of them below the 2^32-1 a record starts
+        // from unless that is row 15's own tag: the best row is a row of this block.  share_last_slot reads rows up to
+        // rb - 1 + groups and replaces what it computed from a row >= rb by 2^32-1 before the record sees it.  The second
+        // row of finish_block_ties is row (k2 & 15), stale only when k2 is still 2^32-1 (rb == 1); what is read there is
+        // used under row_tie alone, and k2 - base < 32 with k2 == 2^32-1 means base > 0xFFFFFF00: ok is already false
+        // and the set is deferred.
+        // (The write below stays unconditional and the registers of a lane with my_row >= rb hold "some value", defined
+        // by an empty asm that emits nothing: putting the write under my_row < rb as well cost the headline kernel
+        // 6 VGPRs, 59 -> 65, and with them a wave per SIMD.  Four permutations per lane with Three records and a shared
+        // last slot keep the zero fill: 127 -> 130 VGPRs without it, 4 -> 3 waves.)
+        uint4 st0, st1;
+        if constexpr (kStageNoFill<P, TIES, SHARE>) {
+            asm("" : "=v"(st0.x), "=v"(st0.y), "=v"(st0.z), "=v"(st0.w));
+            asm("" : "=v"(st1.x), "=v"(st1.y), "=v"(st1.z), "=v"(st1.w));
+        } else {
+            st0 = st1 = uint4{0, 0, 0, 0};
+        }
         if (my_row < rb) {
             const uint4 *src = reinterpret_cast<const uint4 *>(hv_vec + blk + 4 * lane);
             st0 = src[0];
@@ -675,9 +728,9 @@ __device__ __forceinline__ bool sieve_range(const TokT MHX_CONST_AS *hv, const T
         }
         if constexpr (kShare) share_last_slot<P, STRIDE, WPT>(rows[P - 1], lds, sp, rb, lane);
         if constexpr (TIES)
-            fail |= finish_block_ties<P, STRIDE, WPT>(rows, lds, pm, sp, res, tied);
+            fail |= finish_block_ties<P, STRIDE, WPT, SHORT>(rows, lds, pm, sp, res, tied);
         else
-            fail |= finish_block<P, STRIDE, WPT>(rows, lds, pm, sp, res);
+            fail |= finish_block<P, STRIDE, WPT, false, SHORT>(rows, lds, pm, sp, res);
         ++nblocks;
     }
     return fail;
@@ -707,7 +760,7 @@ __device__ __forceinline__ void load_quad(const TokT *hv_vec, int64_t blk, int64
 
 // `first`: the quad of the first block, loaded by the caller (fetching the NEXT flagged set's quad a set ahead was
 // measured: 8 VGPRs live across the whole loop, 92 -> 100, and 1-2 % slower on every corpus)
-template <int P, typename TokT>
+template <int P, typename TokT, bool SHORT = true>
 __device__ __forceinline__ bool dedup_sieve_range(const TokT *hv_vec, int64_t beg, int64_t end, const Perms<P> &pm,
                                                   const SievePerms<P> &sp, uint32_t *lds, int lane,
                                                   const uint64_t (&first)[4], uint32_t (&res)[P]) {
@@ -842,7 +895,7 @@ __device__ __forceinline__ bool dedup_sieve_range(const TokT *hv_vec, int64_t be
 #pragma unroll
             for (int q = 0; q < P; ++q) rows[q].add(tag16(row[q], (uint32_t)nrows));
         }
-        if (kept > 0) fail |= finish_block<P, STRIDE, 2, true>(rows, tile, pm, sp, res, (uint32_t)nrows, (uint32_t)rest);
+        if (kept > 0) fail |= finish_block<P, STRIDE, 2, true, SHORT>(rows, tile, pm, sp, res, (uint32_t)nrows, (uint32_t)rest);
     }
     return fail;
 }
@@ -904,7 +957,7 @@ __device__ __forceinline__ Minima<P> full_minima(const TokT *hv_vec, int64_t beg
 // Sieve over the full 16-token rows of [beg,end) plus fast fold for the ragged tail.  Returns true
 // (wave-uniform) when a proof failed or a tail minimum is ambiguous: the caller then redoes the
 // range with full_minima.
-template <int P, typename TokT, bool TAIL = true, bool TIES = false, bool SHARE = false>
+template <int P, typename TokT, bool TAIL = true, bool TIES = false, bool SHARE = false, bool SHORT = true>
 __device__ __forceinline__ bool sieve_minima(const TokT MHX_CONST_AS *hv, const TokT *hv_vec, int64_t beg,
                                              int64_t end, const Perms<P> &pm, const Perms<P> &pm_biased,
                                              const SievePerms<P> &sp, unsigned long long *stats, int lane,
@@ -916,7 +969,7 @@ __device__ __forceinline__ bool sieve_minima(const TokT MHX_CONST_AS *hv, const 
     bool bad = false;
     if (nrows > 0) {
         int nblocks = 0;
-        bad = sieve_range<P, TokT, TIES, SHARE>(hv, hv_vec, beg, nrows, pm, sp, lds, lane, res, nblocks, tied);
+        bad = sieve_range<P, TokT, TIES, SHARE, SHORT>(hv, hv_vec, beg, nrows, pm, sp, lds, lane, res, nblocks, tied);
         if (stats && lane == 0) atomicAdd(stats + 2, (unsigned long long)nblocks);
     }
     const int64_t tail = beg + (int64_t)nrows * kRowTokens;
@@ -1063,6 +1116,12 @@ __global__ __launch_bounds__(256) void minhash_bulk_kernel(const BulkArgs args_i
     // leave the per-set path (spilled SGPRs 49 -> 32 -> 4, VGPRs 78 -> 73 -> 53): 3 % of the headline launch.
     BulkArgs args = args_in;
     constexpr bool kSieve = MODE == MODE_SIEVE || MODE == MODE_SIEVE_TIES;
+    // The short fold of a proven candidate (fold_proven) everywhere but in three kernels where it costs a spilled SGPR or
+    // more (tools/kernel_regs.py; the table in DESIGN.md section 3): they keep fold_exact in their finishes.
+    constexpr bool kT32 = sizeof(TokT) == 4, kO32 = sizeof(OutT) == 4;
+    constexpr bool kShortFold = !(MODE == MODE_DEDUP && P == 2 && kT32 && !kO32) &&
+                                !(MODE == MODE_SIEVE_TIES && SHAPE == SHAPE_GENERAL && P == 4 && !kT32 && !kO32 && SHARE) &&
+                                !(MODE == MODE_SIEVE_TIES && SHAPE == SHAPE_GENERAL && P == 1 && kT32 && kO32);
     if (kSieve && args.mode_word) {  // (wave-uniform) the first launch that the corpus calls for works, the other one leaves
         const unsigned int want_ties = *as_const(args.mode_word);
         if ((want_ties == 1u) != (MODE == MODE_SIEVE_TIES)) return;
@@ -1234,9 +1293,12 @@ __global__ __launch_bounds__(256) void minhash_bulk_kernel(const BulkArgs args_i
             uint32_t res[P];
             if (kSieve) {
                 if (kchunks > 1) load_perms<P, SHARE>(args, kc * (kWave * P), lane, pm, pm_biased, sp, kidx);
-                if (end > beg) {
+                if (end <= beg) {  // an empty set stores 2^32-1 (or its state): set here, off the per-set path, not selected per store
+#pragma unroll
+                    for (int p = 0; p < P; ++p) res[p] = kMaxHash;
+                } else {
                     bool tied = false;
-                    defer = sieve_minima<P, TokT, SHAPE != SHAPE_PLAIN_FIXED_ROWS, MODE == MODE_SIEVE_TIES, SHARE>(hv, hv_vec, beg, end, pm, pm_biased, sp, args.stats, lane, lds, res,
+                    defer = sieve_minima<P, TokT, SHAPE != SHAPE_PLAIN_FIXED_ROWS, MODE == MODE_SIEVE_TIES, SHARE, kShortFold>(hv, hv_vec, beg, end, pm, pm_biased, sp, args.stats, lane, lds, res,
                                                                                                           MODE == MODE_SIEVE_TIES ? &tied : nullptr);
                     if (kc == 0) ++tried;
                     if (MODE == MODE_SIEVE_TIES) {  // "failed" = the one-candidate proof would have: the corpus still calls for this kernel
@@ -1271,7 +1333,7 @@ __global__ __launch_bounds__(256) void minhash_bulk_kernel(const BulkArgs args_i
                         } else if (ties.skip > 0) {
                             if (kc == kchunks - 1) --ties.skip;
                         } else {
-                            open = sieve_minima<P, TokT, true, true>(hv, hv_vec, beg, end, pm, pm_biased, sp, nullptr, lane, lds, res);
+                            open = sieve_minima<P, TokT, true, true, false, kShortFold>(hv, hv_vec, beg, end, pm, pm_biased, sp, nullptr, lane, lds, res);
                             if (kc == 0) ++tried, failed += open ? 1 : 0;
                             if (open) ties.failed(); else ties.succeeded();
                         }
@@ -1280,7 +1342,7 @@ __global__ __launch_bounds__(256) void minhash_bulk_kernel(const BulkArgs args_i
                         for (int p = 0; p < P; ++p) res[p] = kMaxHash;
                         uint64_t cur[4];
                         load_quad<TokT>(hv_vec, beg, end, lane, cur);
-                        defer = __any(dedup_sieve_range<P, TokT>(hv_vec, beg, end, pm, sp, lds, lane, cur, res));
+                        defer = __any(dedup_sieve_range<P, TokT, kShortFold>(hv_vec, beg, end, pm, sp, lds, lane, cur, res));
                         if (defer) {
                             if (args.stats && lane == 0) atomicAdd(args.stats + 3, 1ull);
                             break;
@@ -1307,10 +1369,13 @@ __global__ __launch_bounds__(256) void minhash_bulk_kernel(const BulkArgs args_i
                         v = iv;  // empty set: state untouched (minhash.py:265-266)
                     }
                 } else {
-                    v = end > beg ? res[p] : kMaxHash;
+                    v = (kSieve || end > beg) ? res[p] : kMaxHash;  // (the sieve launches have set res for an empty set)
                 }
                 if (sizeof(OutT) == 4) v = v > kMaxHash ? kMaxHash : v;
-                out[set * args.num_perm + kidx[p]] = (OutT)v;
+                // the row's address is wave-uniform (SGPRs) and the lane's part an unsigned 32-bit byte offset: a store with
+                // a scalar base, no 64-bit address per lane
+                char *row_out = reinterpret_cast<char *>(out + set * args.num_perm);
+                *reinterpret_cast<OutT *>(row_out + (uint32_t)kidx[p] * (uint32_t)sizeof(OutT)) = (OutT)v;
             }
         }
         if (kSieve && lane == 0) {
