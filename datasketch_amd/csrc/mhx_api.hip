@@ -548,7 +548,9 @@ int mhx_ctx_counters(mhx_ctx *ctx, int enable, uint64_t out[MHX_NUM_COUNTERS]) {
         MHX_HIP_CHECK(mhx::dev_free(ctx->d_stats));
         ctx->d_stats = nullptr;
     }
-    if (ctx->d_stats) MHX_HIP_CHECK(hipMemset(ctx->d_stats, 0, sizeof(uint64_t) * MHX_NUM_COUNTERS));
+    // on the kernels' own stream, as ensure_work()'s: the launches that count are ordered behind the reset by the stream, not by
+    // whether a null-stream memset happens to have finished when it returns (tests/stream_order_cases.py: reset, call, read)
+    if (ctx->d_stats) MHX_HIP_CHECK(hipMemsetAsync(ctx->d_stats, 0, sizeof(uint64_t) * MHX_NUM_COUNTERS, ctx->stream));
     return MHX_OK;
 }
 

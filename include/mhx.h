@@ -22,6 +22,9 @@
  *     only the natural alignment of their element type (wider loads are used where the pointer allows them).
  *     tests/test_guard_pages.py and the `*_guard_cases.py` scripts hold the kernels to this with
  *     mhx_debug_guard_alloc (an unmapped page right behind -- or in front of -- every buffer).
+ *     tests/test_gpu_stream_order.py (cases in tests/stream_order_cases.py) holds the "_dev" entry points to the three ordering
+ *     promises above -- enqueued without synchronising unless the entry's comment says that it blocks, no host pointer kept after the
+ *     return, the work of successive calls on one context taking effect in call order -- by running each behind in-flight work.
  *   - citations "ref:" are paths in the reference repository (ekzhu/datasketch v1.10.0).
  */
 #ifndef MHX_H_
