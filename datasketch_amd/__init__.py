@@ -10,7 +10,7 @@ from datasketch_amd import lsh_bulk
 from datasketch_amd import hyperloglog
 from datasketch_amd import shingle
 from datasketch_amd import overlap
-from datasketch_amd.hashfunc import prehashed, sha1_hash32, sha1_hash64, sha1_hash_many
+from datasketch_amd.hashfunc import hash_many, prehashed, sha1_hash32, sha1_hash64, sha1_hash_many, xxh32_hash32, xxh64_hash64
 from datasketch_amd.hyperloglog import HyperLogLog
 from datasketch_amd.lean_minhash import LeanMinHash
 from datasketch_amd.lsh import MinHashLSH
@@ -38,6 +38,9 @@ __all__ = [
     "sha1_hash32",
     "sha1_hash64",
     "sha1_hash_many",
+    "xxh32_hash32",
+    "xxh64_hash64",
+    "hash_many",
     "hyperloglog",
     "lsh_bulk",
     "shingle",

@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("MHX_LIBRARY") or os.path.join(_HERE, "libmhx.so")  # 
 
 MHX_OK, MHX_ERR_NO_DEVICE, MHX_ERR_INVALID, MHX_ERR_HIP, MHX_ERR_OOM, MHX_ERR_UNSUPPORTED, MHX_ERR_COMM, MHX_ERR_CAPACITY = range(8)
 MHX_U64, MHX_U32 = 0, 1
+MHX_HASH_SHA1, MHX_HASH_XXH = 0, 1  # the token hash of a text entry (include/mhx.h): sha1_hash32 / 64, or xxh32_hash32 / xxh64_hash64
 MHX_TOPK_MAX = 64  # include/mhx.h: the longest list of the top-k Jaccard entries
 COMM_ID_BYTES = 128
 ROW_MAJOR, BAND_MAJOR = 0, 1  # layouts of a band-digest matrix on the device (include/mhx.h)
@@ -205,6 +206,21 @@ _PROTOTYPES_OVERLAP = {
     "mhx_overlap_pairs_windows": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _vp, _i64, _vp],
     "mhx_overlap_pairs_words": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _int, _vp, _i64, _vp],
 }
+# Entry points declared MHX_API_XXH (the hash family named: SHA-1 or xxHash on every text path): a ninth list for the same reason;
+# declared = bound = exported is checked in tests/test_xxh_host.py, the argument checks in tests/test_gpu_xxh.py.
+_PROTOTYPES_XXH = {
+    "mhx_hash_tokens": [_vp, _vp, _vp, _i64, _int, _int, _vp],
+    "mhx_hash_windows": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _int, _vp],
+    "mhx_minhash_bulk_bytes_typed_hashed": [_vp, _vp, _vp, _i64, _int, _int, _vp, _i64, _vp, _i64, _vp],
+    "mhx_minhash_bulk_windows_typed_hashed": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _int, _vp, _i64, _vp, _int],
+    "mhx_minhash_bulk_words_typed_hashed": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _int, _int, _vp, _i64, _vp, _int],
+    "mhx_hll_bulk_bytes_hashed": [_vp, _vp, _vp, _i64, _i32, _int, _vp, _i64, _i32, _vp, _i64, _vp],
+    "mhx_hll_bulk_windows_hashed": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _i32, _int, _i32, _vp, _i64, _vp],
+    "mhx_hll_bulk_words_hashed": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _i32, _int, _i32, _vp, _i64, _vp],
+    "mhx_overlap_pairs_bytes_hashed": [_vp, _vp, _vp, _i64, _int, _int, _vp, _i64, _vp, _i64, _vp],
+    "mhx_overlap_pairs_windows_hashed": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _int, _vp, _i64, _vp],
+    "mhx_overlap_pairs_words_hashed": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _int, _int, _vp, _i64, _vp],
+}
 _RESTYPE = {"mhx_last_error": ctypes.c_char_p, "mhx_version": ctypes.c_char_p}
 
 EXPORTED_SYMBOLS = sorted(list(_PROTOTYPES) + list(_RESTYPE))
@@ -215,6 +231,7 @@ EXPORTED_SYMBOLS_CC = sorted(_PROTOTYPES_CC)
 EXPORTED_SYMBOLS_SHINGLE = sorted(_PROTOTYPES_SHINGLE)
 EXPORTED_SYMBOLS_WORDS = sorted(_PROTOTYPES_WORDS)
 EXPORTED_SYMBOLS_OVERLAP = sorted(_PROTOTYPES_OVERLAP)
+EXPORTED_SYMBOLS_XXH = sorted(_PROTOTYPES_XXH)
 
 
 try:  # CPython helper (csrc/pack_module.c): ~10 ns per token instead of ~180 in the interpreter
@@ -255,7 +272,7 @@ def load():
             raise MhxError(_lib_error) from e
         for name, argtypes in (list(_PROTOTYPES.items()) + list(_PROTOTYPES_EXT.items()) + list(_PROTOTYPES_BLOOM.items())
                                + list(_PROTOTYPES_TOPK.items()) + list(_PROTOTYPES_CC.items()) + list(_PROTOTYPES_SHINGLE.items())
-                               + list(_PROTOTYPES_WORDS.items()) + list(_PROTOTYPES_OVERLAP.items())):
+                               + list(_PROTOTYPES_WORDS.items()) + list(_PROTOTYPES_OVERLAP.items()) + list(_PROTOTYPES_XXH.items())):
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = _int
@@ -703,8 +720,27 @@ class Context:
         check(self.lib.mhx_sha1_tokens(self.handle, _ptr(buf), _ptr(byte_offsets), n, MHX_U32 if bits == 32 else MHX_U64, _ptr(out)))
         return out
 
+    def hash_tokens(self, buf: np.ndarray, byte_offsets: np.ndarray, bits: int = 32, kind: int = MHX_HASH_SHA1) -> np.ndarray:
+        """The hash of family ``kind`` (MHX_HASH_*) and ``bits`` of every token of a packed byte corpus: mhx_hash_tokens."""
+        code = self._hash_code(bits)
+        n = byte_offsets.size - 1
+        out = np.empty(n, dtype=np.uint32 if bits == 32 else np.uint64)
+        buf, byte_offsets = self._bytes_and_offsets(buf, byte_offsets)
+        check(self.lib.mhx_hash_tokens(self.handle, _ptr(buf), _ptr(byte_offsets), n, int(kind), code, _ptr(out)))
+        return out
+
+    def hash_windows(self, buf, doc_offsets, width: int, item_offsets=None, bits: int = 32, kind: int = MHX_HASH_SHA1):
+        """(the hash of family ``kind`` and ``bits`` of every shingle of a corpus, set_offsets): mhx_hash_windows."""
+        code = self._hash_code(bits)
+        buf, item_offsets, doc_offsets, n_items, n_docs = self._windows_corpus(buf, item_offsets, doc_offsets)
+        set_offsets = window_offsets(doc_offsets, width)
+        out = np.empty(int(set_offsets[-1]), dtype=np.uint32 if bits == 32 else np.uint64)
+        check(self.lib.mhx_hash_windows(self.handle, _ptr(buf), _ptr(item_offsets), n_items, _ptr(doc_offsets), n_docs, int(width), int(kind), code,
+                                        _ptr(out)))
+        return out, set_offsets
+
     def minhash_bulk_bytes(self, permutations, buf: np.ndarray, byte_offsets: np.ndarray, set_offsets: np.ndarray,
-                           init: Optional[np.ndarray] = None, bits: int = 32, out_dtype=np.uint64) -> np.ndarray:
+                           init: Optional[np.ndarray] = None, bits: int = 32, out_dtype=np.uint64, kind: int = MHX_HASH_SHA1) -> np.ndarray:
         """Raw byte tokens -> sha1_hash32 (``bits=32``) or sha1_hash64 (``bits=64``) -> [n_sets, K] signatures, all on the
         device.  (This entry writes uint64; any other ``out_dtype`` is a conversion here.)"""
         code = self._hash_code(bits)
@@ -714,8 +750,8 @@ class Context:
         n_sets, n_tokens = set_offsets.size - 1, byte_offsets.size - 1
         init, stride = self._minhash_init(init, n_sets, k)
         out = np.empty((n_sets, k), dtype=np.uint64)
-        check(self.lib.mhx_minhash_bulk_bytes_typed(perm, _ptr(buf), _ptr(byte_offsets), n_tokens, code, _ptr(set_offsets), n_sets, _ptr(init),
-                                                    stride, _ptr(out)))
+        check(self.lib.mhx_minhash_bulk_bytes_typed_hashed(perm, _ptr(buf), _ptr(byte_offsets), n_tokens, code, int(kind), _ptr(set_offsets), n_sets,
+                                                           _ptr(init), stride, _ptr(out)))
         return out.astype(out_dtype, copy=False)
 
     @staticmethod
@@ -753,7 +789,7 @@ class Context:
                                             int(n_windows), int(width), out_dtype, _vp(d_out)))
 
     def minhash_bulk_windows(self, permutations, buf, doc_offsets, width: int, item_offsets=None, init: Optional[np.ndarray] = None,
-                             bits: int = 32, out_dtype=np.uint64) -> np.ndarray:
+                             bits: int = 32, out_dtype=np.uint64, kind: int = MHX_HASH_SHA1) -> np.ndarray:
         """Text -> shingles -> sha1_hash32 / sha1_hash64 -> [n_docs, K] signatures, all on the device (mhx_minhash_bulk_windows_typed)."""
         code = self._hash_code(bits)
         perm = self.perm_handle(permutations)
@@ -761,18 +797,19 @@ class Context:
         buf, item_offsets, doc_offsets, n_items, n_docs = self._windows_corpus(buf, item_offsets, doc_offsets)
         init, stride = self._minhash_init(init, n_docs, k)
         out = np.empty((n_docs, k), dtype=out_dtype)
-        check(self.lib.mhx_minhash_bulk_windows_typed(perm, _ptr(buf), _ptr(item_offsets), n_items, _ptr(doc_offsets), n_docs, int(width), code,
-                                                      _ptr(init), stride, _ptr(out), MHX_U32 if np.dtype(out_dtype) == np.uint32 else MHX_U64))
+        check(self.lib.mhx_minhash_bulk_windows_typed_hashed(perm, _ptr(buf), _ptr(item_offsets), n_items, _ptr(doc_offsets), n_docs, int(width),
+                                                             code, int(kind), _ptr(init), stride, _ptr(out),
+                                                             MHX_U32 if np.dtype(out_dtype) == np.uint32 else MHX_U64))
         return out
 
     def hll_bulk_windows(self, buf, doc_offsets, width: int, p: int, item_offsets=None, hash_bits: int = 32,
-                         init: Optional[np.ndarray] = None) -> np.ndarray:
+                         init: Optional[np.ndarray] = None, kind: int = MHX_HASH_SHA1) -> np.ndarray:
         """Text -> shingles -> sha1_hash32 / sha1_hash64 (``hash_bits``) -> uint8 [n_docs, 2**p] registers, all on the device."""
         buf, item_offsets, doc_offsets, n_items, n_docs = self._windows_corpus(buf, item_offsets, doc_offsets)
         init, stride = self._hll_init(init, n_docs, 1 << int(p))
         out = np.empty((n_docs, 1 << int(p)), dtype=np.uint8)
-        check(self.lib.mhx_hll_bulk_windows(self.handle, _ptr(buf), _ptr(item_offsets), n_items, _ptr(doc_offsets), n_docs, int(width),
-                                            int(hash_bits), int(p), _ptr(init), stride, _ptr(out)))
+        check(self.lib.mhx_hll_bulk_windows_hashed(self.handle, _ptr(buf), _ptr(item_offsets), n_items, _ptr(doc_offsets), n_docs, int(width),
+                                                   int(hash_bits), int(kind), int(p), _ptr(init), stride, _ptr(out)))
         return out
 
     @staticmethod
@@ -816,7 +853,7 @@ class Context:
         return rc, n_words.value, n_out.value
 
     def minhash_bulk_words(self, permutations, buf, doc_offsets, width: int, table, init: Optional[np.ndarray] = None, bits: int = 32,
-                           out_dtype=np.uint64) -> np.ndarray:
+                           out_dtype=np.uint64, kind: int = MHX_HASH_SHA1) -> np.ndarray:
         """Raw text -> words -> w-word shingles -> sha1_hash32 / sha1_hash64 -> [n_docs, K] signatures, all on the device
         (mhx_minhash_bulk_words_typed)."""
         code = self._hash_code(bits)
@@ -825,17 +862,19 @@ class Context:
         buf, doc_offsets, table, n_bytes, n_docs = self._words_corpus(buf, doc_offsets, table)
         init, stride = self._minhash_init(init, n_docs, k)
         out = np.empty((n_docs, k), dtype=out_dtype)
-        check(self.lib.mhx_minhash_bulk_words_typed(perm, _ptr(buf), n_bytes, _ptr(doc_offsets), n_docs, _ptr(table), int(width), code,
-                                                    _ptr(init), stride, _ptr(out), MHX_U32 if np.dtype(out_dtype) == np.uint32 else MHX_U64))
+        check(self.lib.mhx_minhash_bulk_words_typed_hashed(perm, _ptr(buf), n_bytes, _ptr(doc_offsets), n_docs, _ptr(table), int(width), code,
+                                                           int(kind), _ptr(init), stride, _ptr(out),
+                                                           MHX_U32 if np.dtype(out_dtype) == np.uint32 else MHX_U64))
         return out
 
-    def hll_bulk_words(self, buf, doc_offsets, width: int, p: int, table, hash_bits: int = 32, init: Optional[np.ndarray] = None) -> np.ndarray:
+    def hll_bulk_words(self, buf, doc_offsets, width: int, p: int, table, hash_bits: int = 32, init: Optional[np.ndarray] = None,
+                       kind: int = MHX_HASH_SHA1) -> np.ndarray:
         """Raw text -> words -> w-word shingles -> sha1_hash32 / sha1_hash64 (``hash_bits``) -> uint8 [n_docs, 2**p] registers."""
         buf, doc_offsets, table, n_bytes, n_docs = self._words_corpus(buf, doc_offsets, table)
         init, stride = self._hll_init(init, n_docs, 1 << int(p))
         out = np.empty((n_docs, 1 << int(p)), dtype=np.uint8)
-        check(self.lib.mhx_hll_bulk_words(self.handle, _ptr(buf), n_bytes, _ptr(doc_offsets), n_docs, _ptr(table), int(width), int(hash_bits),
-                                          int(p), _ptr(init), stride, _ptr(out)))
+        check(self.lib.mhx_hll_bulk_words_hashed(self.handle, _ptr(buf), n_bytes, _ptr(doc_offsets), n_docs, _ptr(table), int(width), int(hash_bits),
+                                                 int(kind), int(p), _ptr(init), stride, _ptr(out)))
         return out
 
     # -- exact overlap counts of listed pairs (overlap_kernels.hip; datasketch_amd/overlap.py is the definition)
@@ -867,34 +906,34 @@ class Context:
         check(self.lib.mhx_overlap_pairs_dev(self.handle, _vp(d_hv), hv_dtype, _vp(d_set_offsets), int(n_sets), int(max_set_items), _vp(d_pairs),
                                              int(n_pairs), _vp(d_counts), _vp(d_invalid)))
 
-    def overlap_pairs_bytes(self, pairs, buf, byte_offsets, set_offsets, bits: int = 64) -> np.ndarray:
+    def overlap_pairs_bytes(self, pairs, buf, byte_offsets, set_offsets, bits: int = 64, kind: int = MHX_HASH_SHA1) -> np.ndarray:
         """Packed byte tokens -> sha1_hash32 / sha1_hash64 -> exact overlap counts of the listed pairs of sets, all on the device."""
         code = self._hash_code(bits)
         buf, byte_offsets, set_offsets = self._bytes_and_offsets(buf, byte_offsets, set_offsets)
         pairs = self._pairs(pairs)
         out = np.empty((pairs.shape[0], 3), dtype=np.int32)
-        check(self.lib.mhx_overlap_pairs_bytes(self.handle, _ptr(buf), _ptr(byte_offsets), byte_offsets.size - 1, code, _ptr(set_offsets),
-                                               set_offsets.size - 1, _ptr(pairs), pairs.shape[0], _ptr(out)))
+        check(self.lib.mhx_overlap_pairs_bytes_hashed(self.handle, _ptr(buf), _ptr(byte_offsets), byte_offsets.size - 1, code, int(kind),
+                                                      _ptr(set_offsets), set_offsets.size - 1, _ptr(pairs), pairs.shape[0], _ptr(out)))
         return out
 
-    def overlap_pairs_windows(self, pairs, buf, doc_offsets, width: int, item_offsets=None, bits: int = 64) -> np.ndarray:
+    def overlap_pairs_windows(self, pairs, buf, doc_offsets, width: int, item_offsets=None, bits: int = 64, kind: int = MHX_HASH_SHA1) -> np.ndarray:
         """Text -> shingles -> sha1_hash32 / sha1_hash64 -> exact overlap counts of the listed pairs of documents, all on the device."""
         code = self._hash_code(bits)
         buf, item_offsets, doc_offsets, n_items, n_docs = self._windows_corpus(buf, item_offsets, doc_offsets)
         pairs = self._pairs(pairs)
         out = np.empty((pairs.shape[0], 3), dtype=np.int32)
-        check(self.lib.mhx_overlap_pairs_windows(self.handle, _ptr(buf), _ptr(item_offsets), n_items, _ptr(doc_offsets), n_docs, int(width), code,
-                                                 _ptr(pairs), pairs.shape[0], _ptr(out)))
+        check(self.lib.mhx_overlap_pairs_windows_hashed(self.handle, _ptr(buf), _ptr(item_offsets), n_items, _ptr(doc_offsets), n_docs, int(width),
+                                                        code, int(kind), _ptr(pairs), pairs.shape[0], _ptr(out)))
         return out
 
-    def overlap_pairs_words(self, pairs, buf, doc_offsets, width: int, table, bits: int = 64) -> np.ndarray:
+    def overlap_pairs_words(self, pairs, buf, doc_offsets, width: int, table, bits: int = 64, kind: int = MHX_HASH_SHA1) -> np.ndarray:
         """Raw text -> words -> w-word shingles -> sha1_hash32 / sha1_hash64 -> exact overlap counts of the listed pairs of documents."""
         code = self._hash_code(bits)
         buf, doc_offsets, table, n_bytes, n_docs = self._words_corpus(buf, doc_offsets, table)
         pairs = self._pairs(pairs)
         out = np.empty((pairs.shape[0], 3), dtype=np.int32)
-        check(self.lib.mhx_overlap_pairs_words(self.handle, _ptr(buf), n_bytes, _ptr(doc_offsets), n_docs, _ptr(table), int(width), code,
-                                               _ptr(pairs), pairs.shape[0], _ptr(out)))
+        check(self.lib.mhx_overlap_pairs_words_hashed(self.handle, _ptr(buf), n_bytes, _ptr(doc_offsets), n_docs, _ptr(table), int(width), code,
+                                                      int(kind), _ptr(pairs), pairs.shape[0], _ptr(out)))
         return out
 
     def minhash_update_batch(self, permutations, hv: np.ndarray, hashvalues: np.ndarray) -> np.ndarray:
@@ -1396,14 +1435,14 @@ class Context:
         return out, int(overflow.value)
 
     def hll_bulk_bytes(self, buf: np.ndarray, byte_offsets: np.ndarray, set_offsets: np.ndarray, p: int, hash_bits: int = 32,
-                       init: Optional[np.ndarray] = None) -> np.ndarray:
+                       init: Optional[np.ndarray] = None, kind: int = MHX_HASH_SHA1) -> np.ndarray:
         """Packed byte tokens -> sha1_hash32 / sha1_hash64 (``hash_bits``) -> uint8 [n_sets, 2**p] registers, all on the device."""
         buf, byte_offsets, set_offsets = self._bytes_and_offsets(buf, byte_offsets, set_offsets)
         n_sets, n_tokens = set_offsets.size - 1, byte_offsets.size - 1
         init, stride = self._hll_init(init, n_sets, 1 << int(p))
         out = np.empty((n_sets, 1 << int(p)), dtype=np.uint8)
-        check(self.lib.mhx_hll_bulk_bytes(self.handle, _ptr(buf), _ptr(byte_offsets), n_tokens, int(hash_bits), _ptr(set_offsets), n_sets, int(p),
-                                          _ptr(init), stride, _ptr(out)))
+        check(self.lib.mhx_hll_bulk_bytes_hashed(self.handle, _ptr(buf), _ptr(byte_offsets), n_tokens, int(hash_bits), int(kind), _ptr(set_offsets),
+                                                 n_sets, int(p), _ptr(init), stride, _ptr(out)))
         return out
 
     def hll_histogram(self, reg: np.ndarray):

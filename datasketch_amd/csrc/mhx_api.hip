@@ -995,6 +995,9 @@ static int check_sha1(int64_t n_tokens, int out_dtype) {
     return MHX_OK;
 }
 
+// the token hash of a text source (MHX_HASH_*): checked in the entry, dispatched on in Source::hash() and nowhere else
+#define MHX_CHECK_HASH_KIND(kind) MHX_REQUIRE((kind) == MHX_HASH_SHA1 || (kind) == MHX_HASH_XXH, "unknown hash_kind %d", kind)
+
 int mhx_sha1_tokens_dev(mhx_ctx *ctx, const uint8_t *d_bytes, const int64_t *d_byte_offsets, int64_t n_tokens, int out_dtype, void *d_out) {
     MHX_ENTER(ctx, ctx);
     MHX_TRY(check_sha1(n_tokens, out_dtype));
@@ -1020,6 +1023,11 @@ namespace {
 //   hash(s, dtype, d_hv)     the launches that fill d_hv; d_sets and n_hashes hold from then on
 //   host_sets()              the set offsets on the host, from hash() on: a sink that needs the size of a set reads it here
 
+// The slack behind the staged bytes of a Tokens source.  The SHA-1 entries keep the 256 bytes they have always had; the xxHash
+// kernels get none, so that the byte slot ends with the last token and tests/xxh_guard_cases.py holds xxh_tokens_kernel to the
+// last byte of an exact-size allocation.
+constexpr size_t tokens_in_slack(int hash_kind) { return hash_kind == MHX_HASH_XXH ? 0 : 256; }
+
 // packed byte tokens: token i is bytes[byte_offsets[i] .. byte_offsets[i+1]], set j owns tokens set_offsets[j] .. set_offsets[j+1]
 // (set_offsets NULL: the tokens alone, for mhx_sha1_tokens).  Offsets: byte offsets | set offsets.
 struct Tokens {
@@ -1030,6 +1038,8 @@ struct Tokens {
     const int64_t *set_offsets;
     int64_t n;
     size_t aux_slack;  // the slack reserve() leaves behind the hashes (see Stage::ask): its entry says how much it has always carried
+    int hash_kind = MHX_HASH_SHA1;
+    size_t in_slack = 256;  // what stage() leaves behind the bytes: 256 is what the SHA-1 entries have always carried (see tokens_in_slack)
     uint8_t *d_bytes = nullptr;
     int64_t *d_boffs = nullptr, *d_sets = nullptr;
     int64_t n_hashes = 0;
@@ -1063,7 +1073,7 @@ struct Tokens {
         Stage::Piece p_bytes{Stage::In, 0, 0}, p_boffs{Stage::Offsets, 0, 0}, p_sets{Stage::Offsets, 0, 0};
         if (n_tokens > 0) {
             p_bytes = s.piece(Stage::In, (size_t)byte_offsets[n_tokens]);
-            s.ask(Stage::In, p_bytes.bytes + 256);
+            s.ask(Stage::In, std::max<size_t>(p_bytes.bytes + in_slack, 8));
             p_boffs = s.piece(Stage::Offsets, sizeof(int64_t) * (size_t)(n_tokens + 1));
         }
         if (set_offsets) p_sets = s.piece(Stage::Offsets, sizeof(int64_t) * (size_t)(n + 1));
@@ -1082,6 +1092,7 @@ struct Tokens {
     }
     int hash(const Stage &s, int dtype, void *d_hv) {
         n_hashes = n_tokens;
+        if (hash_kind == MHX_HASH_XXH) return mhx::launch_xxh_tokens(s.ctx, d_bytes, d_boffs, n_tokens, dtype, d_hv);
         return mhx::launch_sha1_tokens(s.ctx, d_bytes, d_boffs, n_tokens, dtype, d_hv);
     }
 };
@@ -1090,12 +1101,17 @@ struct Tokens {
 }  // extern "C++"
 
 int mhx_sha1_tokens(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens, int out_dtype, void *out) {
+    return mhx_hash_tokens(ctx, bytes, byte_offsets, n_tokens, MHX_HASH_SHA1, out_dtype, out);
+}
+
+int mhx_hash_tokens(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens, int hash_kind, int out_dtype, void *out) {
     MHX_ENTER(ctx, ctx);
+    MHX_CHECK_HASH_KIND(hash_kind);
     MHX_TRY(check_sha1(n_tokens, out_dtype));
     if (n_tokens == 0) return MHX_OK;
     MHX_REQUIRE(out, "out is NULL");
     MHX_TRY(ctx->activate());
-    Tokens src{bytes, byte_offsets, n_tokens, nullptr, 0, 0};
+    Tokens src{bytes, byte_offsets, n_tokens, nullptr, 0, 0, hash_kind, tokens_in_slack(hash_kind)};
     MHX_TRY(src.check_tokens());
     MHX_TRY(src.stage(ctx));
     Stage s(ctx);
@@ -2309,6 +2325,7 @@ struct Windows {
     int64_t n_items;
     const int64_t *doc_offsets;
     int64_t n_docs, width;
+    int hash_kind = MHX_HASH_SHA1;
     std::vector<int64_t> set_offsets;  // (alive until the call has synchronised: it is uploaded from)
     int64_t n_bytes = 0, n_hashes = 0;  // n_hashes: the number of windows, known from check_arrays() on
     uint8_t *d_bytes = nullptr;
@@ -2355,6 +2372,7 @@ struct Windows {
     }
     void reserve(Stage &) const {}
     int hash(const Stage &s, int dtype, void *d_hv) const {
+        if (hash_kind == MHX_HASH_XXH) return mhx::launch_xxh_windows(s.ctx, d_bytes, d_items, d_docs, d_sets, n_docs, n_hashes, width, dtype, d_hv);
         return mhx::launch_sha1_windows(s.ctx, d_bytes, d_items, d_docs, d_sets, n_docs, n_hashes, width, dtype, d_hv);
     }
 };
@@ -2364,8 +2382,14 @@ struct Windows {
 
 int mhx_sha1_windows(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items, const int64_t *doc_offsets,
                      int64_t n_docs, int64_t width, int out_dtype, void *out) {
+    return mhx_hash_windows(ctx, bytes, item_offsets, n_items, doc_offsets, n_docs, width, MHX_HASH_SHA1, out_dtype, out);
+}
+
+int mhx_hash_windows(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items, const int64_t *doc_offsets,
+                     int64_t n_docs, int64_t width, int hash_kind, int out_dtype, void *out) {
     MHX_ENTER(ctx, ctx);
-    Windows src{bytes, item_offsets, n_items, doc_offsets, n_docs, width};
+    MHX_CHECK_HASH_KIND(hash_kind);
+    Windows src{bytes, item_offsets, n_items, doc_offsets, n_docs, width, hash_kind};
     MHX_TRY(src.check_sizes());
     MHX_CHECK_DTYPE(out_dtype);
     if (n_docs == 0) return MHX_OK;
@@ -2435,6 +2459,7 @@ struct Words {
     int64_t n_docs;
     const uint8_t *table;
     int64_t width;
+    int hash_kind = MHX_HASH_SHA1;
     int64_t n_words = 0, n_out_bytes = 0, n_hashes = 0;
     uint8_t *d_bytes = nullptr;
     int64_t *d_docs = nullptr, *d_wdocs = nullptr, *d_sets = nullptr;
@@ -2496,6 +2521,8 @@ struct Words {
     int hash(const Stage &s, int dtype, void *d_hv) {
         MHX_TRY(emit(s.ctx, s.at<uint8_t>(p_text), s.at<int64_t>(p_items)));
         MHX_TRY(window_offsets(s.ctx));
+        if (hash_kind == MHX_HASH_XXH)
+            return mhx::launch_xxh_windows(s.ctx, s.at<uint8_t>(p_text), s.at<int64_t>(p_items), d_wdocs, d_sets, n_docs, n_hashes, width, dtype, d_hv);
         return mhx::launch_sha1_windows(s.ctx, s.at<uint8_t>(p_text), s.at<int64_t>(p_items), d_wdocs, d_sets, n_docs, n_hashes, width, dtype, d_hv);
     }
 };
@@ -2599,41 +2626,85 @@ int mhx_minhash_bulk_bytes(mhx_perm *perm, const uint8_t *bytes, const int64_t *
 
 int mhx_minhash_bulk_bytes_typed(mhx_perm *perm, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens, int hash_dtype,
                                  const int64_t *set_offsets, int64_t n_sets, const uint64_t *init, int64_t init_stride, uint64_t *out) {
+    return mhx_minhash_bulk_bytes_typed_hashed(perm, bytes, byte_offsets, n_tokens, hash_dtype, MHX_HASH_SHA1, set_offsets, n_sets, init, init_stride, out);
+}
+
+int mhx_minhash_bulk_bytes_typed_hashed(mhx_perm *perm, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens, int hash_dtype,
+                                        int hash_kind, const int64_t *set_offsets, int64_t n_sets, const uint64_t *init, int64_t init_stride,
+                                        uint64_t *out) {
     MHX_ENTER(perm, perm->ctx);
-    return minhash_of(perm, Tokens{bytes, byte_offsets, n_tokens, set_offsets, n_sets, /*aux_slack*/ 256}, hash_dtype, init, init_stride, out, MHX_U64);
+    MHX_CHECK_HASH_KIND(hash_kind);
+    return minhash_of(perm, Tokens{bytes, byte_offsets, n_tokens, set_offsets, n_sets, /*aux_slack*/ 256, hash_kind, tokens_in_slack(hash_kind)}, hash_dtype, init, init_stride, out,
+                      MHX_U64);
 }
 
 int mhx_hll_bulk_bytes(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens, int32_t hash_bits,
                        const int64_t *set_offsets, int64_t n_sets, int32_t p, const uint8_t *init, int64_t init_stride, uint8_t *out) {
+    return mhx_hll_bulk_bytes_hashed(ctx, bytes, byte_offsets, n_tokens, hash_bits, MHX_HASH_SHA1, set_offsets, n_sets, p, init, init_stride, out);
+}
+
+int mhx_hll_bulk_bytes_hashed(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens, int32_t hash_bits, int hash_kind,
+                              const int64_t *set_offsets, int64_t n_sets, int32_t p, const uint8_t *init, int64_t init_stride, uint8_t *out) {
     MHX_ENTER(ctx, ctx);
-    return hll_of(ctx, Tokens{bytes, byte_offsets, n_tokens, set_offsets, n_sets, /*aux_slack*/ 0}, hash_bits, p, init, init_stride, out);
+    MHX_CHECK_HASH_KIND(hash_kind);
+    return hll_of(ctx, Tokens{bytes, byte_offsets, n_tokens, set_offsets, n_sets, /*aux_slack*/ 0, hash_kind, tokens_in_slack(hash_kind)}, hash_bits, p, init, init_stride, out);
 }
 
 int mhx_minhash_bulk_windows_typed(mhx_perm *perm, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items,
                                    const int64_t *doc_offsets, int64_t n_docs, int64_t width, int hash_dtype, const uint64_t *init,
                                    int64_t init_stride, void *out, int out_dtype) {
+    return mhx_minhash_bulk_windows_typed_hashed(perm, bytes, item_offsets, n_items, doc_offsets, n_docs, width, hash_dtype, MHX_HASH_SHA1, init,
+                                                 init_stride, out, out_dtype);
+}
+
+int mhx_minhash_bulk_windows_typed_hashed(mhx_perm *perm, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items,
+                                          const int64_t *doc_offsets, int64_t n_docs, int64_t width, int hash_dtype, int hash_kind,
+                                          const uint64_t *init, int64_t init_stride, void *out, int out_dtype) {
     MHX_ENTER(perm, perm->ctx);
-    return minhash_of(perm, Windows{bytes, item_offsets, n_items, doc_offsets, n_docs, width}, hash_dtype, init, init_stride, out, out_dtype);
+    MHX_CHECK_HASH_KIND(hash_kind);
+    return minhash_of(perm, Windows{bytes, item_offsets, n_items, doc_offsets, n_docs, width, hash_kind}, hash_dtype, init, init_stride, out, out_dtype);
 }
 
 int mhx_hll_bulk_windows(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items, const int64_t *doc_offsets,
                          int64_t n_docs, int64_t width, int32_t hash_bits, int32_t p, const uint8_t *init, int64_t init_stride, uint8_t *out) {
+    return mhx_hll_bulk_windows_hashed(ctx, bytes, item_offsets, n_items, doc_offsets, n_docs, width, hash_bits, MHX_HASH_SHA1, p, init, init_stride, out);
+}
+
+int mhx_hll_bulk_windows_hashed(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items, const int64_t *doc_offsets,
+                                int64_t n_docs, int64_t width, int32_t hash_bits, int hash_kind, int32_t p, const uint8_t *init,
+                                int64_t init_stride, uint8_t *out) {
     MHX_ENTER(ctx, ctx);
-    return hll_of(ctx, Windows{bytes, item_offsets, n_items, doc_offsets, n_docs, width}, hash_bits, p, init, init_stride, out);
+    MHX_CHECK_HASH_KIND(hash_kind);
+    return hll_of(ctx, Windows{bytes, item_offsets, n_items, doc_offsets, n_docs, width, hash_kind}, hash_bits, p, init, init_stride, out);
 }
 
 int mhx_minhash_bulk_words_typed(mhx_perm *perm, const uint8_t *bytes, int64_t n_bytes, const int64_t *doc_offsets, int64_t n_docs,
                                  const uint8_t *table, int64_t width, int hash_dtype, const uint64_t *init, int64_t init_stride, void *out,
                                  int out_dtype) {
+    return mhx_minhash_bulk_words_typed_hashed(perm, bytes, n_bytes, doc_offsets, n_docs, table, width, hash_dtype, MHX_HASH_SHA1, init, init_stride,
+                                               out, out_dtype);
+}
+
+int mhx_minhash_bulk_words_typed_hashed(mhx_perm *perm, const uint8_t *bytes, int64_t n_bytes, const int64_t *doc_offsets, int64_t n_docs,
+                                        const uint8_t *table, int64_t width, int hash_dtype, int hash_kind, const uint64_t *init,
+                                        int64_t init_stride, void *out, int out_dtype) {
     MHX_ENTER(perm, perm->ctx);
-    return minhash_of(perm, Words{bytes, n_bytes, doc_offsets, n_docs, table, width}, hash_dtype, init, init_stride, out, out_dtype);
+    MHX_CHECK_HASH_KIND(hash_kind);
+    return minhash_of(perm, Words{bytes, n_bytes, doc_offsets, n_docs, table, width, hash_kind}, hash_dtype, init, init_stride, out, out_dtype);
 }
 
 int mhx_hll_bulk_words(mhx_ctx *ctx, const uint8_t *bytes, int64_t n_bytes, const int64_t *doc_offsets, int64_t n_docs,
                        const uint8_t *table, int64_t width, int32_t hash_bits, int32_t p, const uint8_t *init, int64_t init_stride,
                        uint8_t *out) {
+    return mhx_hll_bulk_words_hashed(ctx, bytes, n_bytes, doc_offsets, n_docs, table, width, hash_bits, MHX_HASH_SHA1, p, init, init_stride, out);
+}
+
+int mhx_hll_bulk_words_hashed(mhx_ctx *ctx, const uint8_t *bytes, int64_t n_bytes, const int64_t *doc_offsets, int64_t n_docs,
+                              const uint8_t *table, int64_t width, int32_t hash_bits, int hash_kind, int32_t p, const uint8_t *init,
+                              int64_t init_stride, uint8_t *out) {
     MHX_ENTER(ctx, ctx);
-    return hll_of(ctx, Words{bytes, n_bytes, doc_offsets, n_docs, table, width}, hash_bits, p, init, init_stride, out);
+    MHX_CHECK_HASH_KIND(hash_kind);
+    return hll_of(ctx, Words{bytes, n_bytes, doc_offsets, n_docs, table, width, hash_kind}, hash_bits, p, init, init_stride, out);
 }
 
 // ---- MinHashLSHBloom: per-band Bloom filters (ref: datasketch/lsh_bloom.py) ----------------------------------------------
@@ -2898,20 +2969,40 @@ int mhx_overlap_pairs(mhx_ctx *ctx, const void *hv, int hv_dtype, const int64_t 
 
 int mhx_overlap_pairs_bytes(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens, int hash_dtype,
                             const int64_t *set_offsets, int64_t n_sets, const int64_t *pairs, int64_t n_pairs, int32_t *counts) {
+    return mhx_overlap_pairs_bytes_hashed(ctx, bytes, byte_offsets, n_tokens, hash_dtype, MHX_HASH_SHA1, set_offsets, n_sets, pairs, n_pairs, counts);
+}
+
+int mhx_overlap_pairs_bytes_hashed(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens, int hash_dtype, int hash_kind,
+                                   const int64_t *set_offsets, int64_t n_sets, const int64_t *pairs, int64_t n_pairs, int32_t *counts) {
     MHX_ENTER(ctx, ctx);
-    return overlaps_of(ctx, Tokens{bytes, byte_offsets, n_tokens, set_offsets, n_sets, /*aux_slack*/ 0}, hash_dtype, pairs, n_pairs, counts);
+    MHX_CHECK_HASH_KIND(hash_kind);
+    return overlaps_of(ctx, Tokens{bytes, byte_offsets, n_tokens, set_offsets, n_sets, /*aux_slack*/ 0, hash_kind, tokens_in_slack(hash_kind)}, hash_dtype, pairs, n_pairs, counts);
 }
 
 int mhx_overlap_pairs_windows(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items, const int64_t *doc_offsets,
                               int64_t n_docs, int64_t width, int hash_dtype, const int64_t *pairs, int64_t n_pairs, int32_t *counts) {
+    return mhx_overlap_pairs_windows_hashed(ctx, bytes, item_offsets, n_items, doc_offsets, n_docs, width, hash_dtype, MHX_HASH_SHA1, pairs, n_pairs, counts);
+}
+
+int mhx_overlap_pairs_windows_hashed(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items, const int64_t *doc_offsets,
+                                     int64_t n_docs, int64_t width, int hash_dtype, int hash_kind, const int64_t *pairs, int64_t n_pairs,
+                                     int32_t *counts) {
     MHX_ENTER(ctx, ctx);
-    return overlaps_of(ctx, Windows{bytes, item_offsets, n_items, doc_offsets, n_docs, width}, hash_dtype, pairs, n_pairs, counts);
+    MHX_CHECK_HASH_KIND(hash_kind);
+    return overlaps_of(ctx, Windows{bytes, item_offsets, n_items, doc_offsets, n_docs, width, hash_kind}, hash_dtype, pairs, n_pairs, counts);
 }
 
 int mhx_overlap_pairs_words(mhx_ctx *ctx, const uint8_t *bytes, int64_t n_bytes, const int64_t *doc_offsets, int64_t n_docs,
                             const uint8_t *table, int64_t width, int hash_dtype, const int64_t *pairs, int64_t n_pairs, int32_t *counts) {
+    return mhx_overlap_pairs_words_hashed(ctx, bytes, n_bytes, doc_offsets, n_docs, table, width, hash_dtype, MHX_HASH_SHA1, pairs, n_pairs, counts);
+}
+
+int mhx_overlap_pairs_words_hashed(mhx_ctx *ctx, const uint8_t *bytes, int64_t n_bytes, const int64_t *doc_offsets, int64_t n_docs,
+                                   const uint8_t *table, int64_t width, int hash_dtype, int hash_kind, const int64_t *pairs, int64_t n_pairs,
+                                   int32_t *counts) {
     MHX_ENTER(ctx, ctx);
-    return overlaps_of(ctx, Words{bytes, n_bytes, doc_offsets, n_docs, table, width}, hash_dtype, pairs, n_pairs, counts);
+    MHX_CHECK_HASH_KIND(hash_kind);
+    return overlaps_of(ctx, Words{bytes, n_bytes, doc_offsets, n_docs, table, width, hash_kind}, hash_dtype, pairs, n_pairs, counts);
 }
 
 }  // extern "C"

@@ -176,6 +176,10 @@ int launch_sha1_tokens(mhx_ctx *ctx, const uint8_t *d_bytes, const int64_t *d_of
 // shingles hashed in place: d_item_offsets == nullptr = windows of bytes; d_set_offsets = the first window of every document
 int launch_sha1_windows(mhx_ctx *ctx, const uint8_t *d_bytes, const int64_t *d_item_offsets, const int64_t *d_doc_offsets,
                         const int64_t *d_set_offsets, int64_t n_docs, int64_t n_windows, int64_t width, int out_dtype, void *d_out);
+// xxh_kernels.hip: the twins of the two SHA-1 launchers with XXH32 (MHX_U32) / XXH64 (MHX_U64), seed 0, as the hash
+int launch_xxh_tokens(mhx_ctx *ctx, const uint8_t *d_bytes, const int64_t *d_offsets, int64_t n_tokens, int out_dtype, void *d_out);
+int launch_xxh_windows(mhx_ctx *ctx, const uint8_t *d_bytes, const int64_t *d_item_offsets, const int64_t *d_doc_offsets,
+                       const int64_t *d_set_offsets, int64_t n_docs, int64_t n_windows, int64_t width, int out_dtype, void *d_out);
 // words_kernels.hip: a byte-mode corpus to its normal form (every word translated and followed by one space).  Count blocks (it
 // reads the two totals back); emit enqueues, for the corpus and table just counted, scratch[4] untouched in between.
 int launch_words_count(mhx_ctx *ctx, const uint8_t *d_bytes, int64_t n_bytes, const int64_t *d_doc_offsets, int64_t n_docs,

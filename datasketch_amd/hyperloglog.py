@@ -27,7 +27,7 @@ import numpy as np
 
 from datasketch_amd import _native
 from datasketch_amd import shingle as _shingle
-from datasketch_amd.hashfunc import prehashed, sha1_hash32, sha1_hash64
+from datasketch_amd.hashfunc import device_hash, prehashed, sha1_hash32, sha1_hash64
 from datasketch_amd.minhash import _no_device_error
 
 # update_batch: below this many tokens the batch stays on the host whatever ``gpu_mode='detect'`` finds -- the vectorised numpy
@@ -267,7 +267,7 @@ class HyperLogLog:
 
     def update_batch(self, b: Iterable) -> None:
         """Add many tokens with one max-update of the registers (not in the reference).  With ``hashfunc=prehashed`` a numpy
-        integer array goes in as it is; byte tokens under the default ``sha1_hash32`` are hashed on the device when the batch
+        integer array goes in as it is; byte tokens under the default ``sha1_hash32`` (or ``xxh32_hash32`` / ``xxh64_hash64`` at their width) are hashed on the device when the batch
         goes there; any other ``hashfunc`` is applied per token on the host.  Batches below ``UPDATE_BATCH_HOST_TOKENS`` stay on
         the host under ``'detect'``."""
         bits, p = self._hash_range_bit, self.p
@@ -278,9 +278,10 @@ class HyperLogLog:
             return
         device = self._gpu_mode == "always" and _use_gpu("always") or (self._gpu_mode == "detect" and n >= UPDATE_BATCH_HOST_TOKENS and _use_gpu("detect"))
         init = np.ascontiguousarray(self.reg).astype(np.int8, copy=False).view(np.uint8).reshape(-1)
-        if device and self.hashfunc is sha1_hash32 and not isinstance(b, np.ndarray):
+        known = device_hash(self.hashfunc)
+        if device and known and known[1] == bits and not isinstance(b, np.ndarray):
             buf, offs = _native.Context.pack_tokens(b)
-            reg = _native.context().hll_bulk_bytes(buf, offs, np.array([0, n], dtype=np.int64), p, bits, init)
+            reg = _native.context().hll_bulk_bytes(buf, offs, np.array([0, n], dtype=np.int64), p, bits, init, kind=known[0])
         else:
             hv = _as_hashes(b if self.hashfunc is prehashed else [self.hashfunc(t) for t in b], bits, p)
             if device:
@@ -407,8 +408,8 @@ class HyperLogLog:
         ``b``: any iterable of token iterables; with ``hashfunc=prehashed`` also a 2-D integer array (fixed-length sets; uint32
         and uint64 travel as they are) or a ``(values, offsets)`` CSR pair of hashes.  ``packed=(buf, byte_offsets,
         set_offsets)`` instead: byte tokens packed back to back, as for ``MinHash.bulk_signatures``.  Byte tokens are hashed on
-        the device when ``hashfunc is sha1_hash32`` with ``hash_bits=32``, or ``sha1_hash64`` with ``hash_bits=64``; any other
-        callable is applied per token on the host and the integers go to the device.  ``hash_bits=64`` gives the registers of
+        the device when ``hashfunc is sha1_hash32`` or ``xxh32_hash32`` with ``hash_bits=32``, or ``sha1_hash64`` or ``xxh64_hash64``
+        with ``hash_bits=64``; any other callable, or any other pairing, is applied per token on the host and the integers go to the device.  ``hash_bits=64`` gives the registers of
         the reference's ``HyperLogLogPlusPlus``.  A hash that does not fit ``hash_bits`` raises ``ValueError``, as the
         reference's ``update`` does.
 
@@ -435,8 +436,9 @@ class HyperLogLog:
         if table is not None and documents is None:
             raise ValueError("words= goes with documents= and shingle=w, the number of words per shingle")
         device = _use_gpu(gpu_mode)
-        sha1_bits = 32 if hashfunc is sha1_hash32 else 64 if hashfunc is sha1_hash64 else 0
-        device_sha1 = device and sha1_bits == hash_bits
+        known = device_hash(hashfunc)  # (hash_kind, bits): on the device where the function's width is hash_bits
+        hash_on_device = device and known is not None and known[1] == hash_bits
+        kind = known[0] if hash_on_device else 0
         m = 1 << p
         max_sets = max(1, _BULK_CHUNK_BYTES // m)
 
@@ -451,8 +453,8 @@ class HyperLogLog:
         blocks = []
         if b is None:
             for piece in _shingle.text_corpus(packed, documents, shingle, table).chunks(max_sets, _BULK_CHUNK_TOKENS):
-                if device_sha1:
-                    blocks.append(getattr(_native.context(), "hll_bulk_" + piece.native)(p=p, hash_bits=hash_bits, **piece.arrays()))
+                if hash_on_device:
+                    blocks.append(getattr(_native.context(), "hll_bulk_" + piece.native)(p=p, hash_bits=hash_bits, kind=kind, **piece.arrays()))
                     continue
                 flat, offsets = _shingle.flatten(piece.host_sets())
                 blocks.append(from_hashes(_as_hashes([hashfunc(t) for t in flat], hash_bits, p), offsets, 0, offsets.size - 1))
@@ -472,8 +474,8 @@ class HyperLogLog:
             chunk, tokens = [], 0
 
             def flush():
-                if device_sha1:
-                    blocks.append(_native.context().hll_bulk_bytes(*_native.Context.pack_sets(chunk), p, hash_bits))
+                if hash_on_device:
+                    blocks.append(_native.context().hll_bulk_bytes(*_native.Context.pack_sets(chunk), p, hash_bits, kind=kind))
                     return
                 lens = np.fromiter(map(len, chunk), dtype=np.int64, count=len(chunk))
                 offsets = np.zeros(len(chunk) + 1, dtype=np.int64)

@@ -26,7 +26,7 @@ import numpy as np
 
 from datasketch_amd import _native
 from datasketch_amd import shingle as _shingle  # (bulk_signatures has a parameter called shingle)
-from datasketch_amd.hashfunc import prehashed, sha1_hash32, sha1_hash64
+from datasketch_amd.hashfunc import device_hash, prehashed, sha1_hash32, sha1_hash64
 
 # The size of a hash value in number of bytes (reference: datasketch/minhash.py:27)
 hashvalue_byte_size = len(bytes(np.int64(42).data))
@@ -160,17 +160,18 @@ class MinHash:
             hv_list = b
             if b.size == 0:
                 return
-        elif self.hashfunc in (sha1_hash32, sha1_hash64) and self._use_gpu():
-            # the reference's default hash, for the whole batch at once on the device
+        elif device_hash(self.hashfunc) and self._use_gpu():
+            # the reference's default hash (or one of the xxHash pair), for the whole batch at once on the device
             b = b if isinstance(b, (list, tuple)) else list(b)
             if not b:
                 return
+            kind, bits = device_hash(self.hashfunc)
             buf, offs = _native.Context.pack_tokens(b)
-            if self.hashfunc is sha1_hash32:  # one call: bytes up, SHA-1 + permutations + min on the device, K values back
+            if bits == 32:  # one call: bytes up, hash + permutations + min on the device, K values back
                 one_set = np.array([0, len(b)], dtype=np.int64)
-                self.hashvalues = _native.context().minhash_bulk_bytes(self.permutations, buf, offs, one_set, self.hashvalues)[0]
+                self.hashvalues = _native.context().minhash_bulk_bytes(self.permutations, buf, offs, one_set, self.hashvalues, kind=kind)[0]
                 return
-            hv_list = _native.context().sha1_tokens(buf, offs, 64)
+            hv_list = _native.context().hash_tokens(buf, offs, 64, kind)
         else:
             hv_list = [self.hashfunc(_b) for _b in b]
             if not hv_list:  # empty batch is a no-op (minhash.py:265-266)
@@ -305,10 +306,8 @@ class MinHash:
                 yield self._signatures_csr(values[offsets[s] : offsets[e]], local, 0, e - s, init, out_dtype)
                 s = e
             return
-        # the reference's two default token hashes run on the device (32: hashfunc.py:5-15, 64: :17-28)
-        device_sha1 = 32 if self.hashfunc is sha1_hash32 else 64 if self.hashfunc is sha1_hash64 else 0
-        if device_sha1 and not self._use_gpu():
-            device_sha1 = 0
+        # the reference's two default token hashes (32: hashfunc.py:5-15, 64: :17-28) and the xxHash pair run on the device
+        on_device = device_hash(self.hashfunc) if self._use_gpu() else None  # (hash_kind, bits), whichever family it is
         chunk: List = []
         tokens = 0
         for s in b:
@@ -316,20 +315,22 @@ class MinHash:
             chunk.append(s)
             tokens += len(s)
             if len(chunk) >= _BULK_CHUNK_SETS or tokens >= _BULK_CHUNK_TOKENS:
-                yield self._signatures_of_sets(chunk, init, device_sha1).astype(out_dtype, copy=False)
+                yield self._signatures_of_sets(chunk, init, on_device).astype(out_dtype, copy=False)
                 chunk, tokens = [], 0
         if chunk:
-            yield self._signatures_of_sets(chunk, init, device_sha1).astype(out_dtype, copy=False)
+            yield self._signatures_of_sets(chunk, init, on_device).astype(out_dtype, copy=False)
 
-    def _signatures_of_sets(self, sets: List, init, device_sha1: int) -> np.ndarray:
-        if not device_sha1:
+    def _signatures_of_sets(self, sets: List, init, on_device) -> np.ndarray:
+        """``on_device``: ``(hash_kind, bits)`` when the token hash runs on the device, else ``None``."""
+        if not on_device:
             hv, offsets = self._hash_sets(sets)
             return self._signatures_csr(hv, offsets, 0, len(sets), init)
-        # default hashfunc + device: pack the byte tokens once, SHA-1 and MinHash both on the device
+        # a device hash + device: pack the byte tokens once, the hash and MinHash both on the device
         # (repeated tokens are left in: dropping them here costs more host time per set -- a dict per set --
         # than the kernel's slow path for such sets costs on the device)
         buf, byte_offsets, set_offsets = _native.Context.pack_sets(sets)
-        return _native.context().minhash_bulk_bytes(self.permutations, buf, byte_offsets, set_offsets, init, bits=device_sha1)
+        kind, bits = on_device
+        return _native.context().minhash_bulk_bytes(self.permutations, buf, byte_offsets, set_offsets, init, bits=bits, kind=kind)
 
     def _signatures_csr(self, hv, offsets, fixed_len, n_sets, init, out_dtype=np.uint64) -> np.ndarray:
         if self._use_gpu():
@@ -378,7 +379,7 @@ class MinHash:
         token ``i`` is ``buf[byte_offsets[i]:byte_offsets[i+1]]``, set ``j`` owns tokens ``set_offsets[j] ..
         set_offsets[j+1]`` (what a tokenizer writing into one buffer produces; the layout of
         ``mhx_minhash_bulk_bytes``).  No per-object packing on the host at all: with the default ``hashfunc``
-        (``sha1_hash32``, or ``sha1_hash64``) SHA-1 and MinHash both run on the device; any other ``hashfunc``, or
+        (``sha1_hash32``, or ``sha1_hash64``, ``xxh32_hash32``, ``xxh64_hash64``) the hash and MinHash both run on the device; any other ``hashfunc``, or
         ``gpu_mode='disable'``, is applied per token on the host (ref: minhash.py:262-263).
 
         Text: ``documents=`` with ``shingle=k`` takes the sets to be the ``k``-byte shingles of the documents
@@ -386,7 +387,7 @@ class MinHash:
         shorter).  ``documents`` is a ``(buf, doc_offsets)`` pair -- document ``d`` is ``buf[doc_offsets[d]:doc_offsets[d+1]]`` -- or
         a list of ``bytes`` / ``str``, joined on the host; a ``str`` is shingled over its UTF-8 bytes, not its characters.
         ``packed=`` with ``shingle=w`` takes the sets to be the shingles of ``w`` consecutive tokens
-        (:func:`datasketch_amd.shingle.token_shingles`).  With ``sha1_hash32`` / ``sha1_hash64`` on the device the windows are hashed
+        (:func:`datasketch_amd.shingle.token_shingles`).  With one of those four hashes on the device the windows are hashed
         where they lie -- nothing is materialised; any other ``hashfunc``, or ``gpu_mode='disable'``, is applied to the shingles of
         :mod:`datasketch_amd.shingle` on the host.
 
@@ -421,12 +422,12 @@ class MinHash:
         """Signature blocks of a text corpus (one of the kinds of :mod:`datasketch_amd.shingle`), in chunks of whole sets: SHA-1 and
         MinHash both on the device, or ``hashfunc`` applied to the sets on the host (see :meth:`bulk_signatures`)."""
         init = None if self.is_empty() else self.hashvalues
-        bits = 32 if self.hashfunc is sha1_hash32 else 64 if self.hashfunc is sha1_hash64 else 0
-        on_device = bits and self._use_gpu()
+        on_device = device_hash(self.hashfunc) if self._use_gpu() else None
         for piece in corpus.chunks(_BULK_CHUNK_SETS, _BULK_CHUNK_TOKENS):
             if on_device:
+                kind, bits = on_device
                 call = getattr(_native.context(), "minhash_bulk_" + piece.native)
-                yield call(self.permutations, init=init, bits=bits, out_dtype=out_dtype, **piece.arrays())
+                yield call(self.permutations, init=init, bits=bits, kind=kind, out_dtype=out_dtype, **piece.arrays())
                 continue
             f = self.hashfunc
             flat, offsets = _shingle.flatten(piece.host_sets())

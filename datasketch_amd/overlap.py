@@ -29,7 +29,7 @@ import numpy as np
 
 from datasketch_amd import _native
 from datasketch_amd import shingle as _shingle
-from datasketch_amd.hashfunc import sha1_hash32, sha1_hash64
+from datasketch_amd.hashfunc import HASH_SHA1, device_hash, hash_function
 
 
 def _check_pairs(pairs, n_sets: int) -> np.ndarray:
@@ -110,15 +110,44 @@ def overlap_counts(hashes, set_offsets, pairs, gpu_mode: str = "detect") -> np.n
     return overlap_counts_host(hashes, set_offsets, pairs)
 
 
-def text_overlap_counts(pairs, packed=None, documents=None, shingle=None, words=None, bits: int = 64, gpu_mode: str = "detect") -> np.ndarray:
+class _DefaultBits(int):
+    """The default of ``bits=``: the integer 64 for everything that reads it, and an object of its own, so that a call that gives
+    ``bits=64`` can be told from a call that gives nothing."""
+
+
+_BITS_NOT_GIVEN = _DefaultBits(64)
+
+
+def _hash_choice(hashfunc, bits):
+    """``(callable, (hash_kind, bits) or None)`` of the ``hashfunc=`` / ``bits=`` pair of the text calls.  ``hashfunc=None`` keeps
+    the meaning of ``bits`` (SHA-1 of that width, 64 when not given); one of the four device hashes fixes hash and width, and a
+    ``bits`` that the caller gave and that says otherwise -- in either direction -- is an error; any other callable is applied on
+    the host."""
+    if bits not in (32, 64):
+        raise ValueError("bits must be 32 or 64")
+    if hashfunc is None:
+        return hash_function(HASH_SHA1, int(bits)), (HASH_SHA1, int(bits))
+    if not callable(hashfunc):
+        raise ValueError("The hashfunc must be a callable.")
+    known = device_hash(hashfunc)
+    if known is not None and bits is not _BITS_NOT_GIVEN and bits != known[1]:
+        raise ValueError("bits=%d contradicts hashfunc=%s, a %d-bit hash" % (bits, hashfunc.__name__, known[1]))
+    return hashfunc, known
+
+
+def text_overlap_counts(pairs, packed=None, documents=None, shingle=None, words=None, bits: int = _BITS_NOT_GIVEN, gpu_mode: str = "detect",
+                        hashfunc=None) -> np.ndarray:
     """int32 ``[P, 3]`` overlap counts of the listed pairs of sets of a text corpus, given as in ``MinHash.bulk_signatures``:
     ``packed=(buf, byte_offsets, set_offsets)`` (a set is its tokens, or with ``shingle=w`` its shingles of ``w`` tokens),
     ``documents=`` with ``shingle=k`` (``k``-byte shingles) and, with ``words=True`` or a table, shingles of ``k`` words.  The sets
-    are hashed with ``sha1_hash32`` (``bits=32``) or ``sha1_hash64`` (``bits=64``).  On the device the corpus goes up once, is hashed
+    are hashed with ``sha1_hash32`` (``bits=32``) or ``sha1_hash64`` (``bits=64``, the default).  On the device the corpus goes up once, is hashed
     there and only the counts come back; ``gpu_mode='disable'`` hashes the sets of :mod:`datasketch_amd.shingle` with hashlib and
-    applies :func:`overlap_counts_host`.  The corpus is one device call (see the module docstring): ``MemoryError`` if it does not fit."""
-    if bits not in (32, 64):
-        raise ValueError("bits must be 32 or 64")
+    applies :func:`overlap_counts_host`.  The corpus is one device call (see the module docstring): ``MemoryError`` if it does not fit.
+
+    ``hashfunc=``: ``None`` keeps the meaning of ``bits``.  One of ``sha1_hash32``, ``sha1_hash64``, ``xxh32_hash32``,
+    ``xxh64_hash64`` fixes both the hash and its width (a ``bits`` that contradicts it is a ``ValueError``) and runs on the device
+    like the default; any other callable (returning integers below 2**64) is applied per set element on the host."""
+    f, known = _hash_choice(hashfunc, bits)
     if (packed is not None) + (documents is not None) != 1:
         raise ValueError("give the corpus as exactly one of packed=(buf, byte_offsets, set_offsets) and documents=")
     if documents is not None and shingle is None:
@@ -130,20 +159,21 @@ def text_overlap_counts(pairs, packed=None, documents=None, shingle=None, words=
     pairs = _check_pairs(pairs, corpus.doc_offsets.size - 1)
     if pairs.shape[0] == 0:
         return np.empty((0, 3), dtype=np.int32)
-    if _use_gpu(gpu_mode):
-        return getattr(_native.context(), "overlap_pairs_" + corpus.native)(pairs, bits=bits, **corpus.arrays())
-    f = sha1_hash32 if bits == 32 else sha1_hash64
+    if _use_gpu(gpu_mode) and known:
+        return getattr(_native.context(), "overlap_pairs_" + corpus.native)(pairs, bits=known[1], kind=known[0], **corpus.arrays())
     flat, offsets = _shingle.flatten(corpus.host_sets())
-    return overlap_counts_host(np.array([f(t) for t in flat], dtype=np.uint32 if bits == 32 else np.uint64), offsets, pairs)
+    return overlap_counts_host(np.array([f(t) for t in flat], dtype=np.uint32 if known and known[1] == 32 else np.uint64), offsets, pairs)
 
 
-def exact_jaccard_pairs(pairs, packed=None, documents=None, shingle=None, words=None, bits: int = 64, gpu_mode: str = "detect") -> np.ndarray:
+def exact_jaccard_pairs(pairs, packed=None, documents=None, shingle=None, words=None, bits: int = _BITS_NOT_GIVEN, gpu_mode: str = "detect",
+                        hashfunc=None) -> np.ndarray:
     """float64 ``[P]``: the exact Jaccard of every listed pair (:func:`jaccard_of` of :func:`text_overlap_counts`) -- what
     ``jaccard_pairs`` estimates from the signatures.  ``connected_components(pairs, n, keep=exact >= threshold)`` takes the mask."""
-    return jaccard_of(text_overlap_counts(pairs, packed, documents, shingle, words, bits, gpu_mode))
+    return jaccard_of(text_overlap_counts(pairs, packed, documents, shingle, words, bits, gpu_mode, hashfunc))
 
 
-def exact_containment_pairs(pairs, packed=None, documents=None, shingle=None, words=None, bits: int = 64, gpu_mode: str = "detect") -> np.ndarray:
+def exact_containment_pairs(pairs, packed=None, documents=None, shingle=None, words=None, bits: int = _BITS_NOT_GIVEN, gpu_mode: str = "detect",
+                            hashfunc=None) -> np.ndarray:
     """float64 ``[P]``: the exact containment ``|A & B| / |A|`` of the first document of every listed pair in the second -- the
     quantity ``MinHashLSHEnsemble`` searches by."""
-    return containment_of(text_overlap_counts(pairs, packed, documents, shingle, words, bits, gpu_mode))
+    return containment_of(text_overlap_counts(pairs, packed, documents, shingle, words, bits, gpu_mode, hashfunc))

@@ -30,7 +30,7 @@ from typing import Iterator, List, Optional, Sequence, Tuple
 import numpy as np
 
 from datasketch_amd import _native
-from datasketch_amd.hashfunc import sha1_hash32, sha1_hash64
+from datasketch_amd.hashfunc import device_hash, sha1_hash32, sha1_hash64
 
 
 def _check_width(width) -> int:
@@ -315,3 +315,20 @@ def sha1_windows(buf, doc_offsets, width: int, item_offsets=None, bits: int = 32
     f = sha1_hash32 if bits == 32 else sha1_hash64
     flat = [f(s) for doc in host_shingles(buf, item_offsets, doc_offsets, width) for s in doc]
     return np.array(flat, dtype=np.uint32 if bits == 32 else np.uint64), window_offsets(doc_offsets, width)
+
+
+def hash_windows(buf, doc_offsets, width: int, item_offsets=None, hashfunc=sha1_hash32, gpu_mode: str = "detect") -> Tuple[np.ndarray, np.ndarray]:
+    """:func:`sha1_windows` with the hash named by its function: ``(hashes, set_offsets)`` of every shingle of the corpus under
+    ``hashfunc``.  One of ``sha1_hash32``, ``sha1_hash64``, ``xxh32_hash32``, ``xxh64_hash64`` is one kernel on the device (uint32
+    hashes for the 32-bit two, else uint64); any other callable, or ``gpu_mode='disable'``, is applied to the shingles of this
+    module on the host."""
+    from datasketch_amd.hyperloglog import _use_gpu
+
+    if not callable(hashfunc):
+        raise ValueError("The hashfunc must be a callable.")
+    buf, item_offsets, doc_offsets, width = check_corpus(buf, item_offsets, doc_offsets, width)
+    known = device_hash(hashfunc)
+    if _use_gpu(gpu_mode) and known:
+        return _native.context().hash_windows(buf, doc_offsets, width, item_offsets, known[1], known[0])
+    flat = [hashfunc(s) for doc in host_shingles(buf, item_offsets, doc_offsets, width) for s in doc]
+    return np.array(flat, dtype=np.uint32 if known and known[1] == 32 else np.uint64), window_offsets(doc_offsets, width)

@@ -875,6 +875,61 @@ MHX_API_OVERLAP int mhx_overlap_pairs_words(mhx_ctx *ctx, const uint8_t *bytes, 
                                             const uint8_t *table, int64_t width, int hash_dtype, const int64_t *pairs, int64_t n_pairs,
                                             int32_t *counts);
 
+/* ---- xxHash: a second, cheap token hash for every text path -------------------------------------------------------------------
+ * The reference hashes tokens with whatever `hashfunc` the caller passes; SHA-1 is only its default, and at corpus scale the usual
+ * choice is a non-cryptographic hash.  datasketch_amd/hashfunc.py (xxh32_hash32, xxh64_hash64: XXH32 / XXH64 with seed 0, the
+ * canonical integer values of the published algorithm) is the definition.  hash_kind selects the family, the width argument of
+ * the entry selects the function inside it, as it always did for SHA-1:
+ *   MHX_HASH_SHA1   MHX_U32 / hash_bits 32: sha1_hash32     MHX_U64 / hash_bits 64: sha1_hash64
+ *   MHX_HASH_XXH    MHX_U32 / hash_bits 32: xxh32_hash32    MHX_U64 / hash_bits 64: xxh64_hash64
+ * Any other hash_kind is MHX_ERR_INVALID ("unknown hash_kind <value>"), checked before every other argument but the handle.
+ * Every entry below takes the arguments of the entry it is named after plus hash_kind -- in front of out_dtype for the two hash
+ * entries, directly behind the hash width (hash_dtype / hash_bits) for the nine chains -- and is checked, staged and computed by
+ * the same core: with MHX_HASH_SHA1 it IS the older entry, which is now a call of it.  The xxHash kernels (xxh_kernels.hip) read
+ * under the rule of the SHA-1 kernels: no byte outside the aligned dwords that hold a byte of a token.
+ *
+ * Host forms only: a device-pointer form of the two hash entries would have to stand in tests/stream_order_cases.py first.
+ *
+ * Exported through MHX_API_XXH (the same visibility as MHX_API), bound from _native._PROTOTYPES_XXH; declared = bound = exported
+ * is checked in tests/test_xxh_host.py, the argument checks in tests/test_gpu_xxh.py. */
+enum { MHX_HASH_SHA1 = 0, MHX_HASH_XXH = 1 };
+#define MHX_API_XXH __attribute__((visibility("default")))
+/* mhx_sha1_tokens / mhx_sha1_windows with the hash named: one hash per token / window of out_dtype. */
+MHX_API_XXH int mhx_hash_tokens(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens, int hash_kind,
+                                int out_dtype, void *out);
+MHX_API_XXH int mhx_hash_windows(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items,
+                                 const int64_t *doc_offsets, int64_t n_docs, int64_t width, int hash_kind, int out_dtype, void *out);
+/* The MinHash chains: mhx_minhash_bulk_bytes_typed, mhx_minhash_bulk_windows_typed, mhx_minhash_bulk_words_typed. */
+MHX_API_XXH int mhx_minhash_bulk_bytes_typed_hashed(mhx_perm *perm, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens,
+                                                    int hash_dtype, int hash_kind, const int64_t *set_offsets, int64_t n_sets,
+                                                    const uint64_t *init, int64_t init_stride, uint64_t *out);
+MHX_API_XXH int mhx_minhash_bulk_windows_typed_hashed(mhx_perm *perm, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items,
+                                                      const int64_t *doc_offsets, int64_t n_docs, int64_t width, int hash_dtype,
+                                                      int hash_kind, const uint64_t *init, int64_t init_stride, void *out, int out_dtype);
+MHX_API_XXH int mhx_minhash_bulk_words_typed_hashed(mhx_perm *perm, const uint8_t *bytes, int64_t n_bytes, const int64_t *doc_offsets,
+                                                    int64_t n_docs, const uint8_t *table, int64_t width, int hash_dtype, int hash_kind,
+                                                    const uint64_t *init, int64_t init_stride, void *out, int out_dtype);
+/* The HyperLogLog chains: mhx_hll_bulk_bytes, mhx_hll_bulk_windows, mhx_hll_bulk_words. */
+MHX_API_XXH int mhx_hll_bulk_bytes_hashed(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens,
+                                          int32_t hash_bits, int hash_kind, const int64_t *set_offsets, int64_t n_sets, int32_t p,
+                                          const uint8_t *init, int64_t init_stride, uint8_t *out);
+MHX_API_XXH int mhx_hll_bulk_windows_hashed(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items,
+                                            const int64_t *doc_offsets, int64_t n_docs, int64_t width, int32_t hash_bits, int hash_kind,
+                                            int32_t p, const uint8_t *init, int64_t init_stride, uint8_t *out);
+MHX_API_XXH int mhx_hll_bulk_words_hashed(mhx_ctx *ctx, const uint8_t *bytes, int64_t n_bytes, const int64_t *doc_offsets, int64_t n_docs,
+                                          const uint8_t *table, int64_t width, int32_t hash_bits, int hash_kind, int32_t p,
+                                          const uint8_t *init, int64_t init_stride, uint8_t *out);
+/* The overlap chains: mhx_overlap_pairs_bytes, mhx_overlap_pairs_windows, mhx_overlap_pairs_words. */
+MHX_API_XXH int mhx_overlap_pairs_bytes_hashed(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *byte_offsets, int64_t n_tokens,
+                                               int hash_dtype, int hash_kind, const int64_t *set_offsets, int64_t n_sets,
+                                               const int64_t *pairs, int64_t n_pairs, int32_t *counts);
+MHX_API_XXH int mhx_overlap_pairs_windows_hashed(mhx_ctx *ctx, const uint8_t *bytes, const int64_t *item_offsets, int64_t n_items,
+                                                 const int64_t *doc_offsets, int64_t n_docs, int64_t width, int hash_dtype, int hash_kind,
+                                                 const int64_t *pairs, int64_t n_pairs, int32_t *counts);
+MHX_API_XXH int mhx_overlap_pairs_words_hashed(mhx_ctx *ctx, const uint8_t *bytes, int64_t n_bytes, const int64_t *doc_offsets,
+                                               int64_t n_docs, const uint8_t *table, int64_t width, int hash_dtype, int hash_kind,
+                                               const int64_t *pairs, int64_t n_pairs, int32_t *counts);
+
 /* ---- Multi-GPU: assemble the signature matrix (RCCL over xGMI) ----------------------------- */
 /* 128-byte RCCL unique id, created on rank 0 and distributed by the caller (env, file, socket). */
 #define MHX_COMM_ID_BYTES 128
