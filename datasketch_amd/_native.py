@@ -221,6 +221,19 @@ _PROTOTYPES_XXH = {
     "mhx_overlap_pairs_windows_hashed": [_vp, _vp, _vp, _i64, _vp, _i64, _i64, _int, _int, _vp, _i64, _vp],
     "mhx_overlap_pairs_words_hashed": [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _int, _int, _vp, _i64, _vp],
 }
+# Entry points declared MHX_API_WJ in include/mhx_weighted_jaccard.h (WeightedMinHash.jaccard of listed pairs, all pairs, thresholded
+# and top-k): a tenth list for the same reason; declared = bound = exported is checked in tests/test_weighted_jaccard_host.py, the
+# argument checks in tests/test_gpu_weighted_jaccard.py.
+_PROTOTYPES_WJ = {
+    "mhx_weighted_jaccard_pairs_dev": [_vp, _vp, _vp, _i32, _vp, _i64, _vp],
+    "mhx_weighted_jaccard_pairs": [_vp, _vp, _i64, _i32, _vp, _i64, _vp],
+    "mhx_weighted_jaccard_matrix_dev": [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _i64],
+    "mhx_weighted_jaccard_matrix": [_vp, _vp, _i64, _vp, _i64, _i32, _vp],
+    "mhx_weighted_jaccard_threshold_pairs_dev": [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _i64, ctypes.POINTER(_i64)],
+    "mhx_weighted_jaccard_threshold_pairs": [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _i64, ctypes.POINTER(_i64)],
+    "mhx_weighted_jaccard_topk_dev": [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _i32, _i32, _vp, _vp],
+    "mhx_weighted_jaccard_topk": [_vp, _vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _vp],
+}
 _RESTYPE = {"mhx_last_error": ctypes.c_char_p, "mhx_version": ctypes.c_char_p}
 
 EXPORTED_SYMBOLS = sorted(list(_PROTOTYPES) + list(_RESTYPE))
@@ -232,6 +245,7 @@ EXPORTED_SYMBOLS_SHINGLE = sorted(_PROTOTYPES_SHINGLE)
 EXPORTED_SYMBOLS_WORDS = sorted(_PROTOTYPES_WORDS)
 EXPORTED_SYMBOLS_OVERLAP = sorted(_PROTOTYPES_OVERLAP)
 EXPORTED_SYMBOLS_XXH = sorted(_PROTOTYPES_XXH)
+EXPORTED_SYMBOLS_WJ = sorted(_PROTOTYPES_WJ)
 
 
 try:  # CPython helper (csrc/pack_module.c): ~10 ns per token instead of ~180 in the interpreter
@@ -272,7 +286,8 @@ def load():
             raise MhxError(_lib_error) from e
         for name, argtypes in (list(_PROTOTYPES.items()) + list(_PROTOTYPES_EXT.items()) + list(_PROTOTYPES_BLOOM.items())
                                + list(_PROTOTYPES_TOPK.items()) + list(_PROTOTYPES_CC.items()) + list(_PROTOTYPES_SHINGLE.items())
-                               + list(_PROTOTYPES_WORDS.items()) + list(_PROTOTYPES_OVERLAP.items()) + list(_PROTOTYPES_XXH.items())):
+                               + list(_PROTOTYPES_WORDS.items()) + list(_PROTOTYPES_OVERLAP.items()) + list(_PROTOTYPES_XXH.items())
+                               + list(_PROTOTYPES_WJ.items())):
             fn = getattr(lib, name)
             fn.argtypes = argtypes
             fn.restype = _int
@@ -1262,6 +1277,76 @@ class Context:
         check(self.lib.mhx_bbit_jaccard_topk(self.handle, _ptr(a), a.shape[0], _ptr(b), n_b, int(num_perm), int(bits), int(min_count),
                                              int(k), _ptr(rows), _ptr(counts)))
         return rows, counts
+
+    # -- WeightedMinHash.jaccard (include/mhx_weighted_jaccard.h): rows are int64 [n, samples, 2]
+    @staticmethod
+    def _weighted_args(a, b):
+        a = np.ascontiguousarray(a, dtype=np.int64)
+        if a.ndim != 3 or a.shape[2] != 2:
+            raise ValueError("rows must be [n, samples, 2]")
+        if b is not None:
+            b = np.ascontiguousarray(b, dtype=np.int64)
+            if b.ndim != 3 or b.shape[1:] != a.shape[1:]:
+                raise ValueError("rows must be [n, %d, 2]" % a.shape[1])
+        return a, b
+
+    def weighted_jaccard_pairs(self, sig: np.ndarray, pairs: np.ndarray) -> np.ndarray:
+        """int32 counts of equal (k, t) samples for rows (pairs[:,0], pairs[:,1]) of one [n, samples, 2] matrix."""
+        sig, _ = self._weighted_args(sig, None)
+        pairs = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
+        out = np.empty(pairs.shape[0], dtype=np.int32)
+        check(self.lib.mhx_weighted_jaccard_pairs(self.handle, _ptr(sig), sig.shape[0], sig.shape[1], _ptr(pairs), pairs.shape[0], _ptr(out)))
+        return out
+
+    def weighted_jaccard_matrix(self, a: np.ndarray, b: Optional[np.ndarray] = None) -> np.ndarray:
+        """int32 [n_a, n_b]: equal samples of every row of A against every row of B (mhx_weighted_jaccard_matrix)."""
+        a, b = self._weighted_args(a, b)
+        n_b = a.shape[0] if b is None else b.shape[0]
+        out = np.empty((a.shape[0], n_b), dtype=np.int32)
+        check(self.lib.mhx_weighted_jaccard_matrix(self.handle, _ptr(a), a.shape[0], _ptr(b), n_b, a.shape[1], _ptr(out)))
+        return out
+
+    def weighted_jaccard_threshold_pairs(self, a: np.ndarray, b: Optional[np.ndarray], min_count: int, capacity: Optional[int] = None):
+        """(pairs int64 [P, 2] ascending, counts int32 [P]) of the pairs whose equal samples reach ``min_count``
+        (mhx_weighted_jaccard_threshold_pairs); b=None: pairs i < j of A."""
+        a, b = self._weighted_args(a, b)
+        n_b = a.shape[0] if b is None else b.shape[0]
+        return self._threshold_retry(lambda p, c, cap, found: self.lib.mhx_weighted_jaccard_threshold_pairs(
+            self.handle, _ptr(a), a.shape[0], _ptr(b), n_b, a.shape[1], int(min_count), p, c, cap, found),
+            capacity if capacity is not None else max(a.shape[0], 1 << 12))
+
+    def weighted_jaccard_topk(self, a: np.ndarray, b: Optional[np.ndarray], k: int, min_count: int = 0):
+        """(rows int64 [n_a, k], counts int32 [n_a, k]) as :meth:`jaccard_topk`, by equal samples (mhx_weighted_jaccard_topk)."""
+        a, b = self._weighted_args(a, b)
+        n_b = a.shape[0] if b is None else b.shape[0]
+        rows, counts = np.empty((a.shape[0], int(k)), dtype=np.int64), np.empty((a.shape[0], int(k)), dtype=np.int32)
+        check(self.lib.mhx_weighted_jaccard_topk(self.handle, _ptr(a), a.shape[0], _ptr(b), n_b, a.shape[1], int(min_count), int(k),
+                                                 _ptr(rows), _ptr(counts)))
+        return rows, counts
+
+    def weighted_jaccard_pairs_dev(self, d_sig_a: int, d_sig_b: int, samples: int, d_pairs: int, n_pairs: int, d_counts: int) -> None:
+        """mhx_weighted_jaccard_pairs_dev: int32 counts of equal samples of the listed rows of resident matrices; enqueued."""
+        check(self.lib.mhx_weighted_jaccard_pairs_dev(self.handle, _vp(d_sig_a), _vp(d_sig_b), int(samples), _vp(d_pairs), int(n_pairs),
+                                                      _vp(d_counts)))
+
+    def weighted_jaccard_matrix_dev(self, d_a: int, n_a: int, d_b: Optional[int], n_b: int, samples: int, d_counts: int, ldc: int) -> None:
+        check(self.lib.mhx_weighted_jaccard_matrix_dev(self.handle, _vp(d_a), int(n_a), _vp(d_b), int(n_b), int(samples), _vp(d_counts),
+                                                       int(ldc)))
+
+    def weighted_jaccard_threshold_pairs_dev(self, d_a: int, n_a: int, d_b: Optional[int], n_b: int, samples: int, min_count: int,
+                                             d_pairs: Optional[int], d_counts: Optional[int], capacity: int) -> int:
+        """Total number of qualifying pairs (written to d_pairs / d_counts when it is <= capacity)."""
+        found = _i64(0)
+        check(self.lib.mhx_weighted_jaccard_threshold_pairs_dev(self.handle, _vp(d_a), int(n_a), _vp(d_b), int(n_b), int(samples),
+                                                                int(min_count), _vp(d_pairs), _vp(d_counts), int(capacity),
+                                                                ctypes.byref(found)))
+        return int(found.value)
+
+    def weighted_jaccard_topk_dev(self, d_a: int, n_a: int, d_b: Optional[int], n_b: int, samples: int, d_b_live_bits: Optional[int],
+                                  min_count: int, k: int, d_rows: int, d_counts: int) -> None:
+        """mhx_weighted_jaccard_topk_dev: rows int64 [n_a, k] / counts int32 [n_a, k] on the device; enqueued."""
+        check(self.lib.mhx_weighted_jaccard_topk_dev(self.handle, _vp(d_a), int(n_a), _vp(d_b), int(n_b), int(samples), _vp(d_b_live_bits),
+                                                     int(min_count), int(k), _vp(d_rows), _vp(d_counts)))
 
     def jaccard_topk_dev(self, d_a: int, n_a: int, d_b: Optional[int], n_b: int, sig_dtype: int, num_perm: int,
                          d_b_live_bits: Optional[int], min_count: int, k: int, d_rows: int, d_counts: int) -> None:

@@ -60,7 +60,7 @@ struct EmitArgs {
     int64_t capacity;
 };
 
-// SLOT 0: dense equality (WIDE: uint64 elements, else uint32).  SLOT > 0: b-bit blocks, counted as differing slots.
+// SLOT 0: dense equality (WIDE: uint64 elements, else uint32).  SLOT > 0: b-bit blocks, counted as differing slots.  SLOT -1: weighted (k, t) samples.
 // W: 32-bit words per row of A / B (dense uint64: elements per row).  k: num_perm.
 template <int SLOT, bool WIDE, bool EMIT>
 __global__ __launch_bounds__(kThreads, 2) void jaccard_tile_kernel(const uint32_t *__restrict__ a, int64_t n_a,
@@ -74,7 +74,7 @@ __global__ __launch_bounds__(kThreads, 2) void jaccard_tile_kernel(const uint32_
     const int tid = threadIdx.x;
     const int ty = tid >> 4, tx = tid & 15;
     // words past the end of a row: never equal in the dense kinds (A 0, B 1), equal (no differing slot) in the b-bit kind
-    const uint32_t pad_b = SLOT == 0 ? 1u : 0u;
+    const uint32_t pad_b = SLOT <= 0 ? 1u : 0u;
     const int64_t n_tiles = space.count();
     const int chunks = (W + kChunk - 1) / kChunk;
 
@@ -98,7 +98,7 @@ __global__ __launch_bounds__(kThreads, 2) void jaccard_tile_kernel(const uint32_
                     const int64_t j = j0 + rowof(tx, 4 * h);
                     int32_t v[4];
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) v[q] = SLOT == 0 ? (int32_t)acc[r][4 * h + q] : k - (int32_t)acc[r][4 * h + q];
+                    for (int q = 0; q < 4; ++q) v[q] = SLOT <= 0 ? (int32_t)acc[r][4 * h + q] : k - (int32_t)acc[r][4 * h + q];
                     if (vec_store && j + 3 < n_b) {
                         *reinterpret_cast<int4 *>(dst + j) = make_int4(v[0], v[1], v[2], v[3]);
                     } else {
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(kThreads, 2) void jaccard_tile_kernel(const uint32_
 #pragma unroll
                 for (int q = 0; q < 8; ++q) {
                     const int64_t i = i0 + rowof(ty, r), j = j0 + rowof(tx, q);
-                    const int32_t cnt = SLOT == 0 ? (int32_t)acc[r][q] : k - (int32_t)acc[r][q];
+                    const int32_t cnt = SLOT <= 0 ? (int32_t)acc[r][q] : k - (int32_t)acc[r][q];
                     const bool ok = i < n_a && j < n_b && cnt >= em.min_count && (!em.self || i < j);
                     hits += ok ? 1u : 0u;
                 }
@@ -138,7 +138,7 @@ __global__ __launch_bounds__(kThreads, 2) void jaccard_tile_kernel(const uint32_
 #pragma unroll
                         for (int q = 0; q < 8; ++q) {
                             const int64_t i = i0 + rowof(ty, r), j = j0 + rowof(tx, q);
-                            const int32_t cnt = SLOT == 0 ? (int32_t)acc[r][q] : k - (int32_t)acc[r][q];
+                            const int32_t cnt = SLOT <= 0 ? (int32_t)acc[r][q] : k - (int32_t)acc[r][q];
                             if (i < n_a && j < n_b && cnt >= em.min_count && (!em.self || i < j)) {
                                 if (slot < em.capacity) {
                                     em.keys[slot] = ((uint64_t)i << 32) | (uint64_t)j;
@@ -174,6 +174,7 @@ int launch_tiles(mhx_ctx *ctx, const Shape &s, const void *d_a, int64_t n_a, con
 #define MHX_TILES(S, WD) \
     hipLaunchKernelGGL((jaccard_tile_kernel<S, WD, EMIT>), grid, dim3(kThreads), 0, ctx->stream, a, n_a, b, n_b, s.W, k, space, d_out, ldc, vec_store, em)
     switch (s.slot) {
+        case -1: MHX_TILES(-1, false); break;
         case 0: if (s.wide) MHX_TILES(0, true); else MHX_TILES(0, false); break;
         case 1: MHX_TILES(1, false); break;
         case 2: MHX_TILES(2, false); break;
@@ -207,8 +208,7 @@ int launch_jaccard_threshold(mhx_ctx *ctx, const void *d_a, int64_t n_a, const v
         n_b = n_a;
     }
     const Shape s = shape_of(sig_dtype, k, b);
-    // scratch[4]: the pair counter
-    if (int rc = ctx->ensure_scratch(4, 256)) return rc;
+    if (int rc = ctx->ensure_scratch(4, 256)) return rc;  // scratch[4]: the pair counter
     unsigned long long *d_total = (unsigned long long *)ctx->scratch[4];
     MHX_HIP_CHECK(hipMemsetAsync(d_total, 0, sizeof(unsigned long long), ctx->stream));
     const TileSpace space{(n_a + kTile - 1) / kTile, (n_b + kTile - 1) / kTile, self};

@@ -14,7 +14,9 @@ constexpr int kLdsRow = kTile + 4; // [word][row] stride in words: 16-byte align
 constexpr int kThreads = 256;
 constexpr int kStage = kChunk * kTile / kThreads;  // words of A (and of B) one thread stages per chunk
 
-// Kind of row: dense uint32 (SLOT 0, !WIDE), dense uint64 (SLOT 0, WIDE), b-bit packed blocks (SLOT = slot width).
+// Kind of row: dense uint32 (SLOT 0, !WIDE), dense uint64 (SLOT 0, WIDE), b-bit packed blocks (SLOT = slot width), weighted
+// (SLOT -1, !WIDE): int64 (k, t) samples, a row of S samples is 4 S 32-bit words and a position agrees when all four words of
+// the sample do -- a sample never straddles a 16-word chunk, and the padding words (A 0, B 1) fill whole samples.
 template <int SLOT>
 __device__ __forceinline__ uint32_t slot_low_bits() {
     return SLOT == 1 ? 0xFFFFFFFFu : SLOT == 2 ? 0x55555555u : SLOT == 4 ? 0x11111111u : SLOT == 8 ? 0x01010101u
@@ -33,14 +35,16 @@ __device__ __forceinline__ uint32_t differing_slots(uint32_t x, uint32_t y) {
 // sub-tile element (r, q) of thread (ty, tx) is pair (i0 + rowof(ty, r), j0 + rowof(tx, q))
 __device__ __forceinline__ int rowof(int t4, int r) { return (r < 4 ? 0 : 64) + t4 * 4 + (r & 3); }
 
-// words per row and kernel selection shared by the launchers.  b < 0: dense rows of sig_dtype; else b-bit blocks.
+// words per row and kernel selection shared by the launchers.  b == kWeightedRows: k samples of (k, t); any other b < 0: dense rows
+// of sig_dtype; else b-bit blocks.
 struct Shape {
-    int slot;   // 0 dense
+    int slot;   // 0 dense, -1 weighted
     bool wide;  // dense uint64
     int32_t W;
 };
 
 inline Shape shape_of(int sig_dtype, int32_t k, int32_t b) {
+    if (b == kWeightedRows) return Shape{-1, false, 4 * k};
     if (b < 0) return Shape{0, sig_dtype == MHX_U64, k};
     const int slot = bbit_slot_size(b);
     const int per = 64 / slot;

@@ -3,6 +3,7 @@
 // function: handed the accumulators by reference the compiler keeps a second copy of the 64 registers around the chunk loop.
 // In scope at the point of inclusion: template parameters SLOT, WIDE; a, n_a, b, n_b, W; the tile origin i0, j0; tid, ty, tx;
 // pad_b, chunks; the LDS stages As, Bs, Ah, Bh.  Defines acc[8][8], the thread's 8 x 8 counts (b-bit kinds: differing slots).
+// SLOT < 0: weighted rows, staged word by word like uint32 rows and counted sample by sample (4 words, see jaccard_tile.h).
 // Holds barriers: every thread of the workgroup passes through it.
     // staging: thread tid moves word (tid & 15) of the chunk for rows (tid >> 4) + 16 e of the A and the B tile
     const int srow = tid >> 4, sw = tid & 15;
@@ -65,7 +66,29 @@
         if (c + 1 < chunks) fetch(c + 1);  // in flight while this chunk is counted
         const int kn = min(kChunk, W - c * kChunk);  // words of this chunk (b = 1, K = 128 rows are 4 words)
 
-        if (!WIDE || !high) {  // (uint64 chunks whose high words are all zero take the 32-bit comparison)
+        if (SLOT < 0) {  // a (k, t) sample is words kk .. kk + 3 of the chunk (kn is a multiple of 4): equal when all four are
+#pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
+            for (int kk = 0; kk < kn; kk += 4) {
+                uint32_t x[4][8], y[4][8];
+#pragma unroll
+                for (int w = 0; w < 4; ++w) {
+                    *reinterpret_cast<uint4 *>(&x[w][0]) = *reinterpret_cast<const uint4 *>(&As[kk + w][ty * 4]);
+                    *reinterpret_cast<uint4 *>(&x[w][4]) = *reinterpret_cast<const uint4 *>(&As[kk + w][64 + ty * 4]);
+                    *reinterpret_cast<uint4 *>(&y[w][0]) = *reinterpret_cast<const uint4 *>(&Bs[kk + w][tx * 4]);
+                    *reinterpret_cast<uint4 *>(&y[w][4]) = *reinterpret_cast<const uint4 *>(&Bs[kk + w][64 + tx * 4]);
+                }
+#pragma unroll
+                for (int r = 0; r < 8; ++r)
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) {
+                        uint32_t d = (x[0][r] ^ y[0][q]) | (x[1][r] ^ y[1][q]) | (x[2][r] ^ y[2][q]) | (x[3][r] ^ y[3][q]);
+                        // (opaque: left to itself the compiler compares word by word, 4 v_cmp and 3 ANDs of lane masks per cell
+                        // -- more masks in flight than there are scalar registers, 214 lane spills per trip)
+                        asm("" : "+v"(d));
+                        acc[r][q] += d == 0 ? 1u : 0u;
+                    }
+            }
+        } else if (!WIDE || !high) {  // (uint64 chunks whose high words are all zero take the 32-bit comparison)
 #pragma clang loop unroll(disable) vectorize(disable) interleave(disable)
             for (int kk = 0; kk < kn; ++kk) {
                 uint32_t x[8], y[8];

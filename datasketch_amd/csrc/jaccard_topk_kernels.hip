@@ -77,7 +77,7 @@ __global__ __launch_bounds__(kThreads, 2) void jaccard_topk_strip_kernel(const u
     const int64_t i0 = ti * kTile;
     const int64_t tiles_n = (n_b + kTile - 1) / kTile;
     // words past the end of a row: never equal in the dense kinds (A 0, B 1), equal (no differing slot) in the b-bit kind
-    const uint32_t pad_b = SLOT == 0 ? 1u : 0u;
+    const uint32_t pad_b = SLOT <= 0 ? 1u : 0u;
     const int chunks = (W + kChunk - 1) / kChunk;
     const int64_t t_begin = seg * tk.seg_tiles, t_end = min(tiles_n, t_begin + tk.seg_tiles);
 
@@ -104,7 +104,7 @@ __global__ __launch_bounds__(kThreads, 2) void jaccard_topk_strip_kernel(const u
             col_ok |= (j < n_b && row_live(tk.live, j) ? 1u : 0u) << r;
         }
         const bool diagonal = tk.self && i0 == j0 && ty == tx;  // element (r, r) of this thread is a row against itself
-        auto count_of = [&](int r, int q) { return SLOT == 0 ? acc[r][q] : (uint32_t)num_perm - acc[r][q]; };
+        auto count_of = [&](int r, int q) { return SLOT <= 0 ? acc[r][q] : (uint32_t)num_perm - acc[r][q]; };
         auto key_of = [&](int r, int q) { return ((uint64_t)count_of(r, q) << 32) | low[q]; };
         auto passes = [&](int r, int q) {
             const uint32_t c = count_of(r, q);
@@ -169,14 +169,14 @@ __global__ __launch_bounds__(kThreads, 2) void jaccard_topk_strip_kernel(const u
 
 // One wave per segment of B's rows, up to kStreamProbes probes (rows q0 .. q0 + nq - 1 of A).  L lanes share a row of B
 // (a power of two), a lane reads the 16-byte pieces l, l + L, ... of the row; VEC: rows are multiples of 16 bytes at 16-byte
-// aligned addresses.  Dynamic LDS: the probes, nq rows of W elements.
-template <bool WIDE>
+// aligned addresses.  Dynamic LDS: the probes, nq rows of W elements.  QUAD: weighted rows, an element is one 16-byte (k, t) sample.
+template <bool WIDE, bool QUAD = false>
 __global__ __launch_bounds__(256) void jaccard_topk_stream_kernel(const uint32_t *__restrict__ a, int64_t n_a, int64_t q0, int nq,
                                                                   const uint32_t *__restrict__ b, int64_t n_b, int32_t W, int L,
                                                                   int vec, int64_t seg_rows, TopkArgs tk) {
     extern __shared__ __attribute__((aligned(16))) uint32_t probes[];
-    constexpr int kPer = WIDE ? 2 : 4;             // elements per 16-byte piece
-    constexpr int kWordsPer = WIDE ? 2 : 1;        // 32-bit words per element
+    constexpr int kPer = QUAD ? 1 : WIDE ? 2 : 4;       // elements per 16-byte piece
+    constexpr int kWordsPer = QUAD ? 4 : WIDE ? 2 : 1;  // 32-bit words per element
     const int tid = threadIdx.x, lane = tid & 63;
     const int topk = tk.topk;
     const int pieces = (W + kPer - 1) / kPer;       // per row
@@ -212,6 +212,7 @@ __global__ __launch_bounds__(256) void jaccard_topk_stream_kernel(const uint32_t
     }
 
     auto equal_in = [](uint32_t x0, uint32_t x1, uint32_t x2, uint32_t x3, uint32_t y0, uint32_t y1, uint32_t y2, uint32_t y3) -> uint32_t {
+        if (QUAD) return (uint32_t)(x0 == y0 && x1 == y1 && x2 == y2 && x3 == y3);
         if (WIDE) return (uint32_t)(x0 == y0 && x1 == y1) + (uint32_t)(x2 == y2 && x3 == y3);
         return (uint32_t)(x0 == y0) + (uint32_t)(x1 == y1) + (uint32_t)(x2 == y2) + (uint32_t)(x3 == y3);
     };
@@ -353,11 +354,13 @@ int launch_jaccard_topk(mhx_ctx *ctx, const void *d_a, int64_t n_a, const void *
         // (uint32, K = 128, k = 10): 16 probes take 2.27 ms on the stream kernel and 2.56 ms on the strip kernel against 10^6 rows,
         // 7.67 ms and 11.56 ms against 10^7; 32 probes take 4.52 / 2.77 ms and 15.31 / 11.79 ms.
         const int64_t kStreamBelow = 16;
-        const int per = s.wide ? 2 : 4, words_per = s.wide ? 2 : 1;
-        const int pieces = (s.W + per - 1) / per;  // 16-byte pieces of a dense row
+        const bool quad = s.slot < 0;  // weighted rows: the stream kernel's element is a sample, s.W / 4 of them per row
+        const int per = quad ? 1 : s.wide ? 2 : 4, words_per = quad ? 4 : s.wide ? 2 : 1;
+        const int32_t elems = quad ? s.W / 4 : s.W;
+        const int pieces = (elems + per - 1) / per;  // 16-byte pieces of a dense row
         const size_t stream_lds = sizeof(uint32_t) * 4 * (size_t)pieces * kStreamProbes;
-        // (path 2 asks for the stream kernel wherever it exists: dense rows whose probes fit in 64 KiB of LDS)
-        const bool stream = s.slot == 0 && stream_lds <= (64u << 10) &&
+        // (path 2 asks for the stream kernel wherever it exists: dense and weighted rows whose probes fit in 64 KiB of LDS)
+        const bool stream = s.slot <= 0 && stream_lds <= (64u << 10) &&
                             (ctx->opt_jaccard_topk_path == 2 || (ctx->opt_jaccard_topk_path == 0 && n_a <= kStreamBelow));
         TopkArgs tk{};
         tk.live = d_live;
@@ -375,13 +378,16 @@ int launch_jaccard_topk(mhx_ctx *ctx, const void *d_a, int64_t n_a, const void *
             if (int rc = ctx->ensure_scratch(4, sizeof(uint64_t) * (size_t)segments * (size_t)n_a * (size_t)topk)) return rc;
             tk.partial = (uint64_t *)ctx->scratch[4];
             const int L = std::min(64, next_pow2(pieces));
-            const size_t row_bytes = sizeof(uint32_t) * (size_t)s.W * words_per;
+            const size_t row_bytes = sizeof(uint32_t) * (size_t)elems * words_per;
             const int vec = (row_bytes % 16 == 0 && ((uintptr_t)d_b & 15) == 0) ? 1 : 0;
             const size_t lds = stream_lds;
             const dim3 grid((unsigned)((segments + 3) / 4));
             for (int64_t q0 = 0; q0 < n_a; q0 += kStreamProbes) {
                 const int nq = (int)std::min<int64_t>(kStreamProbes, n_a - q0);
-                if (s.wide)
+                if (quad)
+                    hipLaunchKernelGGL((jaccard_topk_stream_kernel<false, true>), grid, dim3(256), lds, ctx->stream, (const uint32_t *)d_a, n_a, q0, nq,
+                                       (const uint32_t *)d_b, n_b, elems, L, vec, seg_rows, tk);
+                else if (s.wide)
                     hipLaunchKernelGGL(jaccard_topk_stream_kernel<true>, grid, dim3(256), lds, ctx->stream, (const uint32_t *)d_a, n_a, q0, nq,
                                        (const uint32_t *)d_b, n_b, s.W, L, vec, seg_rows, tk);
                 else
@@ -412,6 +418,7 @@ int launch_jaccard_topk(mhx_ctx *ctx, const void *d_a, int64_t n_a, const void *
         hipLaunchKernelGGL((jaccard_topk_strip_kernel<S, WD>), grid, dim3(kThreads), lds, ctx->stream, a, n_a, b, n_b, s.W, num_perm, tk); \
     } while (0)
             switch (s.slot) {
+                case -1: MHX_STRIP(-1, false); break;
                 case 0: if (s.wide) MHX_STRIP(0, true); else MHX_STRIP(0, false); break;
                 case 1: MHX_STRIP(1, false); break;
                 case 2: MHX_STRIP(2, false); break;

@@ -1426,8 +1426,13 @@ int mhx_lsh_ensemble_query_dev(mhx_ctx *ctx, const mhx_ensemble_level *levels, i
                                           n_params, d_pairs, capacity, n_pairs);
 }
 
-// Agreeing positions of listed pairs.  b < 0: dense rows of sig_dtype, else b-bit blocks.  The host form takes the n rows
-// both ends of a pair index (In), the pairs (Aux) and returns the counts (Out).
+// uint64 words per row of the Jaccard cores: k dense elements, the blocks of k b-bit values, or k weighted (k, t) samples
+static size_t jaccard_row_words(int32_t k, int32_t b) {
+    return b == mhx::kWeightedRows ? 2 * (size_t)k : b < 0 ? (size_t)k : (size_t)num_blocks(k, b);
+}
+
+// Agreeing positions of listed pairs.  b < 0: dense rows of sig_dtype (kWeightedRows: weighted rows of k samples), else b-bit
+// blocks.  The host form takes the n rows both ends of a pair index (In), the pairs (Aux) and returns the counts (Out).
 static int listed_pairs(mhx_ctx *ctx, const void *rows_a, const void *rows_b, int64_t n, int sig_dtype, int32_t k, int32_t b,
                         const int64_t *pairs, int64_t n_pairs, int32_t *counts, Where where) {
     MHX_ENTER(ctx, ctx);
@@ -1442,7 +1447,7 @@ static int listed_pairs(mhx_ctx *ctx, const void *rows_a, const void *rows_b, in
     if (where == kHost) {
         for (int64_t p = 0; p < 2 * n_pairs; ++p)
             MHX_REQUIRE(pairs[p] >= 0 && pairs[p] < n, "pair index %lld out of range [0,%lld)", (long long)pairs[p], (long long)n);
-        const auto p_rows = s.piece(Stage::In, sizeof(uint64_t) * (size_t)n * (size_t)(b < 0 ? k : num_blocks(k, b)));
+        const auto p_rows = s.piece(Stage::In, sizeof(uint64_t) * (size_t)n * jaccard_row_words(k, b));
         const auto p_pairs = s.piece(Stage::Aux, sizeof(int64_t) * 2 * (size_t)n_pairs);
         p_counts = s.piece(Stage::Out, sizeof(int32_t) * (size_t)n_pairs);
         MHX_TRY(s.commit());
@@ -1452,7 +1457,8 @@ static int listed_pairs(mhx_ctx *ctx, const void *rows_a, const void *rows_b, in
         pairs = s.at<int64_t>(p_pairs);
     }
     int32_t *d_counts = where == kHost ? s.at<int32_t>(p_counts) : counts;
-    if (b < 0) MHX_TRY(mhx::launch_jaccard_pairs(ctx, rows_a, rows_b, sig_dtype, k, pairs, n_pairs, d_counts));
+    if (b == mhx::kWeightedRows) MHX_TRY(mhx::launch_weighted_jaccard_pairs(ctx, rows_a, rows_b, k, pairs, n_pairs, d_counts));
+    else if (b < 0) MHX_TRY(mhx::launch_jaccard_pairs(ctx, rows_a, rows_b, sig_dtype, k, pairs, n_pairs, d_counts));
     else MHX_TRY(mhx::launch_bbit_jaccard(ctx, (const uint64_t *)rows_a, (const uint64_t *)rows_b, k, b, pairs, n_pairs, d_counts));
     return where == kHost ? s.fetch(counts, p_counts) : MHX_OK;
 }
@@ -1853,11 +1859,11 @@ int mhx_weighted_minhash_many_dense(mhx_wgen *gen, const float *x, int values_ar
 }
 
 // ---- all-pairs Jaccard (jaccard_kernels.hip) -------------------------------------------------
-// Shared argument checks.  b < 0: dense rows of sig_dtype, else b-bit blocks.
+// Shared argument checks.  b < 0: dense rows of sig_dtype (kWeightedRows: weighted rows of k samples), else b-bit blocks.
 static int check_all_pairs(int64_t n_a, int64_t n_b, int sig_dtype, int32_t k, int32_t b) {
     MHX_CHECK_DTYPE(sig_dtype);
     if (b >= 0) MHX_CHECK_B(b);
-    MHX_REQUIRE(k > 0, "num_perm must be positive");
+    MHX_REQUIRE(k > 0, "%s must be positive", b == mhx::kWeightedRows ? "samples" : "num_perm");
     MHX_REQUIRE(n_a >= 0 && n_b >= 0, "bad shape");
     MHX_CHECK_ROWS32(n_a);
     MHX_CHECK_ROWS32(n_b);
@@ -1879,7 +1885,7 @@ static int all_pairs_matrix(mhx_ctx *ctx, const void *a, int64_t n_a, const void
     MHX_REQUIRE_POINTERS(a && counts, where);
     MHX_TRY(ctx->activate());
     if (where == kDevice) return mhx::launch_jaccard_matrix(ctx, a, n_a, b, n_b, sig_dtype, k, bb, counts, ldc);
-    const size_t row_bytes = sizeof(uint64_t) * (size_t)(bb < 0 ? k : num_blocks(k, bb));
+    const size_t row_bytes = sizeof(uint64_t) * jaccard_row_words(k, bb);
     const size_t out_row = sizeof(int32_t) * (size_t)n_b;
     const int64_t block = std::max<int64_t>(1, std::min<int64_t>(n_a, (int64_t)((256ull << 20) / out_row)));
     Stage s(ctx);
@@ -1912,7 +1918,7 @@ static int all_pairs_threshold(mhx_ctx *ctx, const void *a, int64_t n_a, const v
     MHX_TRY(ctx->activate());
     if (where == kDevice)
         return mhx::launch_jaccard_threshold(ctx, a, n_a, b, n_b, sig_dtype, k, bb, min_count, pairs, counts, capacity, n_pairs);
-    const size_t row_bytes = sizeof(uint64_t) * (size_t)(bb < 0 ? k : num_blocks(k, bb));
+    const size_t row_bytes = sizeof(uint64_t) * jaccard_row_words(k, bb);
     Stage s(ctx);
     const auto p_a = s.piece(Stage::In, row_bytes * (size_t)n_a);
     const auto p_b = b ? s.piece(Stage::Aux, row_bytes * (size_t)n_b) : Stage::Piece{};
@@ -1947,7 +1953,7 @@ static int all_pairs_topk(mhx_ctx *ctx, const void *a, int64_t n_a, const void *
     if (where == kDevice)
         return mhx::launch_jaccard_topk(ctx, a, n_a, self ? a : b, n_b, sig_dtype, k, bb, live_bits, min_count, topk, self, nullptr, 0, nullptr,
                                         rows, counts);
-    const size_t row_bytes = sizeof(uint64_t) * (size_t)(bb < 0 ? k : num_blocks(k, bb));
+    const size_t row_bytes = sizeof(uint64_t) * jaccard_row_words(k, bb);
     const size_t list_bytes = (size_t)n_a * (size_t)topk;
     const size_t block_bytes = ctx->opt_host_chunk_bytes > 0 ? (size_t)ctx->opt_host_chunk_bytes : (size_t)256 << 20;
     const int64_t block = self ? n_b : std::max<int64_t>(1, std::min<int64_t>(n_b, (int64_t)(block_bytes / row_bytes)));
@@ -2040,6 +2046,48 @@ int mhx_bbit_jaccard_topk(mhx_ctx *ctx, const uint64_t *a, int64_t n_a, const ui
                           int32_t min_count, int32_t k, int64_t *rows, int32_t *counts) {
     MHX_CHECK_B(b);
     return all_pairs_topk(ctx, a, n_a, b_blocks, n_b, MHX_U64, num_perm, b, nullptr, min_count, k, rows, counts, kHost);
+}
+
+// ---- weighted Jaccard (mhx_weighted_jaccard.h): the cores above on rows of (k, t) samples --------
+int mhx_weighted_jaccard_pairs_dev(mhx_ctx *ctx, const int64_t *d_sig_a, const int64_t *d_sig_b, int32_t samples, const int64_t *d_pairs,
+                                   int64_t n_pairs, int32_t *d_counts) {
+    return listed_pairs(ctx, d_sig_a, d_sig_b, 0, MHX_U64, samples, mhx::kWeightedRows, d_pairs, n_pairs, d_counts, kDevice);
+}
+
+int mhx_weighted_jaccard_pairs(mhx_ctx *ctx, const int64_t *sig, int64_t n, int32_t samples, const int64_t *pairs, int64_t n_pairs,
+                               int32_t *counts) {
+    return listed_pairs(ctx, sig, sig, n, MHX_U64, samples, mhx::kWeightedRows, pairs, n_pairs, counts, kHost);
+}
+
+int mhx_weighted_jaccard_matrix_dev(mhx_ctx *ctx, const int64_t *d_a, int64_t n_a, const int64_t *d_b, int64_t n_b, int32_t samples,
+                                    int32_t *d_counts, int64_t ldc) {
+    return all_pairs_matrix(ctx, d_a, n_a, d_b, n_b, MHX_U64, samples, mhx::kWeightedRows, d_counts, ldc, kDevice);
+}
+
+int mhx_weighted_jaccard_matrix(mhx_ctx *ctx, const int64_t *a, int64_t n_a, const int64_t *b, int64_t n_b, int32_t samples,
+                                int32_t *counts) {
+    return all_pairs_matrix(ctx, a, n_a, b, n_b, MHX_U64, samples, mhx::kWeightedRows, counts, 0, kHost);
+}
+
+int mhx_weighted_jaccard_threshold_pairs_dev(mhx_ctx *ctx, const int64_t *d_a, int64_t n_a, const int64_t *d_b, int64_t n_b, int32_t samples,
+                                             int32_t min_count, int64_t *d_pairs, int32_t *d_counts, int64_t capacity, int64_t *n_pairs) {
+    return all_pairs_threshold(ctx, d_a, n_a, d_b, n_b, MHX_U64, samples, mhx::kWeightedRows, min_count, d_pairs, d_counts, capacity, n_pairs,
+                               kDevice);
+}
+
+int mhx_weighted_jaccard_threshold_pairs(mhx_ctx *ctx, const int64_t *a, int64_t n_a, const int64_t *b, int64_t n_b, int32_t samples,
+                                         int32_t min_count, int64_t *pairs, int32_t *counts, int64_t capacity, int64_t *n_pairs) {
+    return all_pairs_threshold(ctx, a, n_a, b, n_b, MHX_U64, samples, mhx::kWeightedRows, min_count, pairs, counts, capacity, n_pairs, kHost);
+}
+
+int mhx_weighted_jaccard_topk_dev(mhx_ctx *ctx, const int64_t *d_a, int64_t n_a, const int64_t *d_b, int64_t n_b, int32_t samples,
+                                  const uint32_t *d_b_live_bits, int32_t min_count, int32_t k, int64_t *d_rows, int32_t *d_counts) {
+    return all_pairs_topk(ctx, d_a, n_a, d_b, n_b, MHX_U64, samples, mhx::kWeightedRows, d_b_live_bits, min_count, k, d_rows, d_counts, kDevice);
+}
+
+int mhx_weighted_jaccard_topk(mhx_ctx *ctx, const int64_t *a, int64_t n_a, const int64_t *b, int64_t n_b, int32_t samples, int32_t min_count,
+                              int32_t k, int64_t *rows, int32_t *counts) {
+    return all_pairs_topk(ctx, a, n_a, b, n_b, MHX_U64, samples, mhx::kWeightedRows, nullptr, min_count, k, rows, counts, kHost);
 }
 
 int mhx_lsh_bands_merge_dev(mhx_ctx *ctx, const uint64_t *d_dig_a, const uint32_t *d_rows_a, int64_t n_a, const uint64_t *d_dig_b,

@@ -34,6 +34,9 @@ void forgive();  // a failure the caller tolerates (an optional buffer that coul
 // internal "signature type" of launch_lsh_sort_bands: the matrix holds band digests already ([n, bands] uint64)
 constexpr int kSigDigests = 2;
 constexpr int kSigDigestsBM = 3;  // ... band-major ([bands, n])
+// internal value of the `b` of the Jaccard cores and launchers (b < 0: dense rows): the rows are WeightedMinHash signatures,
+// [k samples][2] int64 (k, t), and a position is a whole sample (mhx_weighted_jaccard_*)
+constexpr int32_t kWeightedRows = -2;
 
 // mhx_ctx::d_work: 16 counter words, then the list of sets the second MinHash launch leaves to the pairwise one
 constexpr unsigned int kPairListCap = 16384;
@@ -203,6 +206,9 @@ int launch_bbit_digest_fused(mhx_ctx *ctx, const void *d_sig, int sig_dtype, int
                              int32_t r, uint64_t *d_blocks, uint64_t *d_digests, int layout, bool *done);
 int launch_jaccard_pairs(mhx_ctx *ctx, const void *d_a, const void *d_b, int sig_dtype, int32_t k, const int64_t *d_pairs,
                          int64_t m, int32_t *d_counts);
+// weighted_jaccard_kernels.hip: agreeing (k, t) samples of listed pairs of [*, samples, 2] int64 rows
+int launch_weighted_jaccard_pairs(mhx_ctx *ctx, const void *d_a, const void *d_b, int32_t samples, const int64_t *d_pairs, int64_t m,
+                                  int32_t *d_counts);
 int launch_weighted_dense(mhx_wgen *gen, const float *d_x, int values_are_logs, int64_t n_rows, int64_t *d_out,
                           uint8_t *d_nonempty);
 // lsh_kernels.hip builds sorted bands (launch_lsh_sort_bands); lsh_query_kernels.hip reads them (candidate pairs and the two queries)
@@ -225,7 +231,8 @@ int launch_lean_deserialize(mhx_ctx *ctx, const uint8_t *d_records, int64_t n, i
                             int64_t *d_seeds, unsigned int *d_bad);
 int launch_bbit_unpack(mhx_ctx *ctx, const uint64_t *d_blocks, int64_t n, int32_t k, int32_t b, uint32_t *d_out);
 
-// jaccard_kernels.hip: all-pairs counts.  b < 0: dense rows of sig_dtype; b in [0, 32]: b-bit blocks (mhx_bbit_pack*).
+// jaccard_kernels.hip: all-pairs counts.  b < 0: dense rows of sig_dtype; b in [0, 32]: b-bit blocks (mhx_bbit_pack*);
+// b == kWeightedRows: weighted rows of k samples.
 int launch_jaccard_matrix(mhx_ctx *ctx, const void *d_a, int64_t n_a, const void *d_b, int64_t n_b, int sig_dtype, int32_t k,
                           int32_t b, int32_t *d_counts, int64_t ldc);
 // d_b == nullptr: self-join of A (pairs i < j).  Blocking: *n_pairs comes back to the host.

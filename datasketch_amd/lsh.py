@@ -107,8 +107,8 @@ class _HostBands(HostRows):
     def bands(self):
         return self.dig, self.rows
 
-    def clusters(self, threshold, extra) -> np.ndarray:
-        return lsh_bulk.bands_clusters_host(self.sig, self.dig, self.rows, threshold, extra)
+    def clusters(self, threshold, extra, words: int = 1) -> np.ndarray:
+        return lsh_bulk.bands_clusters_host(self.sig, self.dig, self.rows, threshold, extra, words=words)
 
 
 class _DeviceBands(DeviceRows):
@@ -180,8 +180,8 @@ class _DeviceBands(DeviceRows):
             return np.empty((self.b, 0), dtype=np.uint64), np.empty((self.b, 0), dtype=np.uint32)
         return self.d_dig.download((self.b, self.n), np.uint64), self.d_rows.download((self.b, self.n), np.uint32)
 
-    def clusters(self, threshold, extra) -> np.ndarray:
-        return lsh_bulk.rows_clusters(self, self.d_dig.ptr, self.d_rows.ptr, self.b, self.kw, threshold, extra)
+    def clusters(self, threshold, extra, words: int = 1) -> np.ndarray:
+        return lsh_bulk.rows_clusters(self, self.d_dig.ptr, self.d_rows.ptr, self.b, self.kw, threshold, extra, words=words)
 
 
 class MinHashLSH:
@@ -511,13 +511,16 @@ class MinHashLSH:
         ``(key, jaccard)``, best first, ties by the earlier insertion; keys as :meth:`query` returns them.  Exact -- every live
         row of the index is compared, no banding in front.  ``threshold``: only keys whose Jaccard is ``>= threshold``.  A key
         inserted more than once is reported once, with its nearest row: the scan asks for ``k`` + (live rows - live keys)
-        rows, which must not exceed 64.  Pending inserts are flushed first; removed rows are masked, not compacted."""
+        rows, which must not exceed 64.  Pending inserts are flushed first; removed rows are masked, not compacted.  An index
+        of WeightedMinHash signatures takes ``[M, S, 2]`` probes and ranks by ``WeightedMinHash.jaccard``; probes of the other
+        kind than the index's are a ``ValueError``."""
         mat, words = lsh_bulk._words_matrix(signatures)
-        if words != 1 or self._words == 2:
-            raise ValueError("nearest neighbours are defined for MinHash signatures, not WeightedMinHash ones")
+        if self._words is not None and words != self._words:
+            raise ValueError("Cannot compare MinHash and WeightedMinHash signatures: the index holds %s ones"
+                             % ("WeightedMinHash" if self._words == 2 else "MinHash"))
         m, kw = mat.shape
-        if kw != self.h:
-            raise ValueError("Expecting minhash with length %d, got %d" % (self.h, kw))
+        if kw != self.h * words:
+            raise ValueError("Expecting minhash with length %d, got %d" % (self.h, kw // words))
         k = lsh_bulk._check_topk(k)
         self._sync()
         n = self._n_flushed
@@ -532,7 +535,7 @@ class MinHashLSH:
         if lsh_bulk.needs_widening(backend.dtype, mat):
             backend.widen()  # a probe value no uint32 row can hold: compare on the full width
         rows, counts = lsh_bulk.rows_nearest(backend, np.ascontiguousarray(mat, dtype=backend.dtype), want, threshold,
-                                             None if self._n_dead == 0 else live)
+                                             None if self._n_dead == 0 else live, words=words)
         out = []
         for row, count in zip(rows.tolist(), counts.tolist()):
             seen, best = set(), []
@@ -552,20 +555,17 @@ class MinHashLSH:
         if len(minhash) != self.h:
             raise ValueError("Expecting minhash with length %d, got %d" % (self.h, len(minhash)))
         hv = np.asarray(minhash.hashvalues)
-        if hv.ndim != 1:
-            raise ValueError("nearest neighbours are defined for MinHash signatures, not WeightedMinHash ones")
-        return self.nearest_bulk(hv.reshape(1, -1), k, threshold)[0]
+        return self.nearest_bulk(hv[None], k, threshold)[0]
 
     def duplicate_clusters(self, threshold: Optional[float] = None, min_size: int = 2) -> List[list]:
         """The near-duplicate clusters of the indexed keys: lists of keys (as :meth:`query` returns them) of at least
         ``min_size`` keys each (``min_size=1`` includes the keys that are alone).  ``threshold=None``: keys are one cluster when
         a chain of shared band keys joins them -- the connected components of what :meth:`query` reports for the keys
         themselves.  With a ``threshold`` two rows that share a band key are joined only when their ``MinHash.jaccard`` estimate
-        is ``>= threshold`` (MinHash signatures only), as ``lsh_bulk.duplicate_clusters`` does.  A key inserted more than once
+        is ``>= threshold`` (on an index of WeightedMinHash signatures: their ``WeightedMinHash.jaccard``, as
+        ``lsh_bulk.weighted_duplicate_clusters`` does), as ``lsh_bulk.duplicate_clusters`` does.  A key inserted more than once
         joins the clusters of all its rows.  Clusters come ordered by their first inserted key, the keys inside a cluster in
         insertion order (by slot).  Calls :meth:`compact` first: removed keys are gone before anything is linked."""
-        if threshold is not None and self._words == 2:
-            raise ValueError("a threshold is defined for MinHash signatures, not WeightedMinHash ones")
         min_size = int(min_size)
         if min_size < 1:
             raise ValueError("min_size must be at least 1")
@@ -574,7 +574,7 @@ class MinHashLSH:
         if self._backend is None or n == 0:
             return []
         extra = [(int(self._kid_slot[kid]), s) for kid, slots in self._extra.items() for s in slots]
-        labels = self._backend.clusters(threshold, np.asarray(extra, dtype=np.int64).reshape(-1, 2))
+        labels = self._backend.clusters(threshold, np.asarray(extra, dtype=np.int64).reshape(-1, 2), self._words)
         kids = self._slot_kid[:n]
         first = np.flatnonzero(self._kid_slot[kids] == np.arange(n))  # one slot per key: its first
         order = first[np.argsort(labels[first], kind="stable")]       # by (cluster's smallest slot, slot)

@@ -28,9 +28,12 @@ Python round trips:
   ``labels[i]`` = the smallest row of ``i``'s connected component, by a lock-free union-find on the device that reads listed
   pairs or the sorted bands themselves (:meth:`SortedBandsIndex.clusters`, ``MinHashLSH.duplicate_clusters``).
 
-Every helper except :func:`jaccard_pairs` also takes a WeightedMinHash matrix ``[N, S, 2]`` int64
-(``WeightedMinHashGenerator.minhash_many_arrays``): its band keys are the reference's too
-(16*r bytes per band); :func:`weighted_jaccard_pairs` is ``WeightedMinHash.jaccard`` for pairs.
+The banding helpers also take a WeightedMinHash matrix ``[N, S, 2]`` int64 (``WeightedMinHashGenerator.minhash_many_arrays``):
+its band keys are the reference's too (16*r bytes per band).  The Jaccard steps have weighted twins of their own, since a position
+of such a row is a ``(k, t)`` pair: :func:`weighted_jaccard_pairs`, :func:`weighted_jaccard_matrix`, :func:`weighted_similar_pairs`,
+:func:`weighted_nearest_neighbors` and :func:`weighted_duplicate_clusters` are ``WeightedMinHash.jaccard`` (ref:
+weighted_minhash.py:45-60) for listed pairs, every pair, the pairs at a threshold, the ``k`` nearest and the clusters;
+:class:`SortedBandsIndex` and ``MinHashLSH`` built on weighted rows answer ``nearest`` and thresholded clusters with them.
 """
 from __future__ import annotations
 
@@ -377,21 +380,26 @@ class SortedBandsIndex:
     ``M x b`` probe digests, candidates confirmed by comparing the band's ``r`` hash values themselves (so the
     answer is the reference's even under a 64-bit digest collision), sort + unique across bands.  Rows are
     numbers ``0 .. N-1`` of the indexed matrix; map them to keys with your own array.  uint32 signature
-    matrices (the compact / all-gathered form) are taken as they are."""
+    matrices (the compact / all-gathered form) are taken as they are.  A WeightedMinHash matrix ``[N, S, 2]`` int64 makes a
+    weighted index: it is held as ``[N, 2 S]`` words, a band is ``r`` ``(k, t)`` pairs, probes are ``[M, S, 2]`` too, and
+    :meth:`nearest` / :meth:`clusters` rank and filter by ``WeightedMinHash.jaccard``."""
 
     def __init__(self, signatures, b: int, r: int, device: Optional[int] = None):
         sig = np.asarray(signatures)
-        if sig.ndim != 2:
+        self.words = 2 if sig.ndim == 3 and sig.shape[2] == 2 else 1
+        if self.words == 2:
+            sig = _matrix(sig)
+        elif sig.ndim != 2:
             raise ValueError("signatures must be an [N, K] matrix")
-        if sig.dtype != np.uint32:
+        elif sig.dtype != np.uint32:
             sig = np.ascontiguousarray(sig, dtype=np.uint64)
         sig = np.ascontiguousarray(sig)
-        _check_params(sig.shape[1], b, r)
+        _check_params(sig.shape[1], b, r * self.words)
         if not _native.gpu_available():
             raise RuntimeError("SortedBandsIndex needs an MI355X / libmhx.so")
         self.ctx = _native.context(device)
-        self.k = sig.shape[1]
-        self.b, self.r = int(b), int(r)
+        self.k = sig.shape[1]                              # words per row
+        self.b, self.r = int(b), int(r) * self.words       # r: words per band
         self.dtype = sig.dtype
         self._rows = DeviceRows(self.ctx, self.k, sig.dtype)
         self._rows.upload(sig)
@@ -407,6 +415,20 @@ class SortedBandsIndex:
         if self.n:
             self.ctx.lsh_sort_bands_dev(self._rows.d_sig.ptr, self._rows.code, self.n, self.k, self.b, self.r, self._d_dig.ptr,
                                         self._d_rows.ptr)
+
+    def _rows_arg(self, signatures) -> np.ndarray:
+        """Probes or further rows as a matrix of the index's words: ``[M, K]``, or ``[M, S, 2]`` for a weighted index."""
+        q = np.asarray(signatures)
+        if (q.ndim == 3) != (self.words == 2):
+            raise ValueError("Cannot compare MinHash and WeightedMinHash signatures: this index holds %s rows"
+                             % ("WeightedMinHash [N, S, 2]" if self.words == 2 else "MinHash [N, K]"))
+        if self.words == 2:
+            if q.shape[2] != 2 or 2 * q.shape[1] != self.k:
+                raise ValueError("Expecting minhash with length %d, got %d" % (self.k // 2, q.shape[1]))
+            return _matrix(q)
+        if q.ndim != 2 or q.shape[1] != self.k:
+            raise ValueError("Expecting minhash with length %d, got %d" % (self.k, q.shape[-1]))
+        return self._as_index_dtype(q)
 
     def _as_index_dtype(self, sig: np.ndarray) -> np.ndarray:
         """``sig`` in the index's signature type; a wider matrix must fit (a wrapped value would match band keys the
@@ -424,10 +446,7 @@ class SortedBandsIndex:
         numbers ``range(old N, new N)``.  The matrix grows on the device (the rows already there are not uploaded
         again; the first build allocates room for its own rows, 1024 at least, and the capacity at least doubles whenever it runs
         out, so most calls copy nothing) and the bands are sorted afresh -- 40 ms per 10^6 rows, so add in batches."""
-        more = np.asarray(signatures)
-        if more.ndim != 2 or more.shape[1] != self.k:
-            raise ValueError("Expecting minhash with length %d, got %d" % (self.k, more.shape[-1]))
-        more = self._as_index_dtype(more)
+        more = self._rows_arg(signatures)
         first, m = self.n, more.shape[0]
         if m == 0:
             return range(first, first)
@@ -439,10 +458,7 @@ class SortedBandsIndex:
     def query(self, signatures, capacity: Optional[int] = None):
         """``(offsets int64[M+1], rows int64[...])``: the index rows sharing at least one band key with probe
         ``i`` are ``rows[offsets[i]:offsets[i+1]]``, ascending."""
-        q = np.asarray(signatures)
-        if q.ndim != 2 or q.shape[1] != self.k:
-            raise ValueError("Expecting minhash with length %d, got %d" % (self.k, q.shape[-1]))
-        q = self._as_index_dtype(q)
+        q = self._rows_arg(signatures)
         if q.shape[0] == 0 or self.n == 0:
             return np.zeros(q.shape[0] + 1, dtype=np.int64), np.empty(0, dtype=np.int64)
         return self.ctx.lsh_query_dev(self._d_dig.ptr, self._d_rows.ptr, self.n, self.b, self.r, self._rows.d_sig.ptr, self._rows.code,
@@ -450,19 +466,17 @@ class SortedBandsIndex:
 
     def nearest(self, signatures, k: int, threshold: Optional[float] = None):
         """``(rows int64 [M, k], jaccard float64 [M, k])``: the ``k`` indexed rows nearest to every probe by ``MinHash.jaccard``,
-        as :func:`nearest_neighbors` -- an exact scan of the resident matrix, only the probes are uploaded."""
-        q = np.asarray(signatures)
-        if q.ndim != 2 or q.shape[1] != self.k:
-            raise ValueError("Expecting minhash with length %d, got %d" % (self.k, q.shape[-1]))
-        q = self._as_index_dtype(q)
+        as :func:`nearest_neighbors` -- an exact scan of the resident matrix, only the probes are uploaded.  (A weighted index:
+        by ``WeightedMinHash.jaccard``, as :func:`weighted_nearest_neighbors`.)"""
+        q = self._rows_arg(signatures)
         k = _check_topk(k)
-        rows, counts = rows_nearest(self._rows, q, k, threshold)
-        return rows, _jaccard_of(rows, counts, self.k)
+        rows, counts = rows_nearest(self._rows, q, k, threshold, words=self.words)
+        return rows, _jaccard_of(rows, counts, self.k // self.words)
 
     def clusters(self, threshold: Optional[float] = None) -> np.ndarray:
         """``labels int64 [N]`` as :func:`duplicate_clusters` gives them, over the resident matrix and bands: nothing is
         uploaded, only the labels come down."""
-        return rows_clusters(self._rows, self._d_dig.ptr, self._d_rows.ptr, self.b, self.k, threshold)
+        return rows_clusters(self._rows, self._d_dig.ptr, self._d_rows.ptr, self.b, self.k, threshold, words=self.words)
 
 
 def sorted_bands(signatures, b: int, r: int, gpu_mode: str = "detect"):
@@ -528,17 +542,149 @@ def jaccard_pairs(signatures, pairs, gpu_mode: str = "detect") -> np.ndarray:
     return counts.astype(np.float64) / float(sig.shape[1])
 
 
-def weighted_jaccard_pairs(signatures, pairs) -> np.ndarray:
+def weighted_jaccard_pairs(signatures, pairs, gpu_mode: str = "detect") -> np.ndarray:
     """``WeightedMinHash.jaccard`` (ref: weighted_minhash.py:41-60) of rows ``pairs[:, 0]`` and ``pairs[:, 1]`` of an
-    ``[N, S, 2]`` matrix: the fraction of samples whose ``(k, t)`` pairs are equal."""
+    ``[N, S, 2]`` matrix: the fraction of samples whose ``(k, t)`` pairs are equal (on the device: mhx_weighted_jaccard_pairs)."""
+    _check_gpu_mode(gpu_mode)
     sig = np.asarray(signatures, dtype=np.int64)
     if sig.ndim != 3 or sig.shape[2] != 2:
         raise ValueError("signatures must be [N, S, 2]")
     pairs = np.ascontiguousarray(pairs, dtype=np.int64).reshape(-1, 2)
     if pairs.size and (pairs.min() < 0 or pairs.max() >= sig.shape[0]):
         raise ValueError("pair index out of range")
-    same = np.all(sig[pairs[:, 0]] == sig[pairs[:, 1]], axis=2)
-    return np.count_nonzero(same, axis=1).astype(np.float64) / float(sig.shape[1])
+    if _use_gpu(gpu_mode) and pairs.size and sig.shape[1]:
+        counts = _native.context().weighted_jaccard_pairs(sig, pairs)
+    else:
+        counts = _equal_samples(sig[pairs[:, 0]], sig[pairs[:, 1]])
+    return counts.astype(np.float64) / float(sig.shape[1])
+
+
+# ---- WeightedMinHash.jaccard of every pair: the weighted twins of jaccard_matrix, similar_pairs, nearest_neighbors and
+# duplicate_clusters.  One definition throughout: count(x, y) = the samples s with x[s, 0] == y[s, 0] and x[s, 1] == y[s, 1], the
+# estimate float(count) / float(S) (ref: weighted_minhash.py:45-60).  The numpy forms below are that definition.
+def _equal_samples(x: np.ndarray, y: np.ndarray) -> np.ndarray:
+    """Samples at which rows ``x[..., S, 2]`` and ``y[..., S, 2]`` (broadcast against each other) hold the same ``(k, t)``."""
+    return np.count_nonzero(np.all(x == y, axis=-1), axis=-1)
+
+
+def _weighted_rows(x, name: str):
+    """(int64 [N, S, 2] matrix, seed or None) of a WeightedMinHash matrix or a sequence of WeightedMinHash objects."""
+    if isinstance(x, np.ndarray) or (not hasattr(x, "__len__") or not len(x) or not hasattr(x[0], "hashvalues")):
+        sig = np.asarray(x)
+    else:
+        seed, s = x[0].seed, len(x[0])
+        for m in x:
+            if m.seed != seed:
+                raise ValueError("Cannot compute Jaccard given WeightedMinHash objects with different seeds")
+            if len(m) != s:
+                raise ValueError("Cannot compute Jaccard given WeightedMinHash objects with different numbers of hash values")
+        sig = np.stack([np.asarray(m.hashvalues) for m in x])
+        if sig.ndim == 3 and sig.shape[2] == 2:
+            return np.ascontiguousarray(sig, dtype=np.int64), seed
+    if sig.ndim != 3 or sig.shape[2] != 2:
+        raise ValueError("%s must be an [N, S, 2] WeightedMinHash matrix or a sequence of WeightedMinHash, not MinHash [N, K] rows" % name)
+    return np.ascontiguousarray(sig, dtype=np.int64), None
+
+
+def _weighted_inputs(a, b):
+    sa, seed_a = _weighted_rows(a, "a")
+    if b is None:
+        return sa, None
+    sb, seed_b = _weighted_rows(b, "b")
+    if seed_a is not None and seed_b is not None and seed_a != seed_b:
+        raise ValueError("Cannot compute Jaccard given WeightedMinHash objects with different seeds")
+    if sa.shape[1] != sb.shape[1]:
+        raise ValueError("Cannot compute Jaccard given WeightedMinHash objects with different numbers of hash values")
+    return sa, sb
+
+
+def _equal_samples_blocks(va: np.ndarray, vb: Optional[np.ndarray]):
+    """The weighted :func:`_equal_counts_blocks`: yields (first row, int64 [rows, n_b]) over ``[n, S, 2]`` matrices."""
+    other = va if vb is None else vb
+    n_b, s = other.shape[:2]
+    step = max(1, _FALLBACK_ELEMS // max(1, 2 * n_b * s))
+    for i0 in range(0, va.shape[0], step):
+        yield i0, _equal_samples(va[i0 : i0 + step, None], other[None])
+
+
+def weighted_jaccard_matrix(a, b=None, gpu_mode: str = "detect") -> np.ndarray:
+    """``WeightedMinHash.jaccard`` of every row of ``a`` against every row of ``b``: float64 ``[M, N]``, equal samples / S.
+    ``a`` / ``b``: ``[N, S, 2]`` int64 matrices (``WeightedMinHashGenerator.minhash_many_arrays``) or sequences of
+    WeightedMinHash (seeds and lengths must agree, as ``WeightedMinHash.jaccard`` requires).  ``b=None``: ``a`` against itself."""
+    _check_gpu_mode(gpu_mode)
+    sa, sb = _weighted_inputs(a, b)
+    s = sa.shape[1]
+    n_b = sa.shape[0] if sb is None else sb.shape[0]
+    if sa.shape[0] == 0 or n_b == 0 or s == 0:
+        return np.zeros((sa.shape[0], n_b), dtype=np.float64)
+    if _use_gpu(gpu_mode):
+        counts = _native.context().weighted_jaccard_matrix(sa, sb)
+    else:
+        counts = _matrix_from_blocks(_equal_samples_blocks(sa, sb), sa.shape[0], n_b)
+    return counts.astype(np.float64) / float(s)
+
+
+def weighted_similar_pairs(a, b=None, threshold: float = 0.5, gpu_mode: str = "detect"):
+    """Every pair whose ``WeightedMinHash.jaccard`` is ``>= threshold``: ``(pairs int64 [P, 2], jaccard float64 [P])`` as
+    :func:`similar_pairs` gives them -- ascending by ``(i, j)``, with ``b=None`` the pairs ``i < j`` of ``a``; the threshold
+    becomes the smallest count ``c`` with ``float(c) / float(S) >= threshold``."""
+    _check_gpu_mode(gpu_mode)
+    sa, sb = _weighted_inputs(a, b)
+    s = sa.shape[1]
+    n_b = sa.shape[0] if sb is None else sb.shape[0]
+    if sa.shape[0] == 0 or n_b == 0 or s == 0:
+        return np.empty((0, 2), dtype=np.int64), np.empty(0, dtype=np.float64)
+    c = _threshold_count(s, threshold)
+    if c > s:
+        return np.empty((0, 2), dtype=np.int64), np.empty(0, dtype=np.float64)
+    if _use_gpu(gpu_mode):
+        pairs, counts = _native.context().weighted_jaccard_threshold_pairs(sa, sb, c)
+    else:
+        pairs, counts = _pairs_from_blocks(_equal_samples_blocks(sa, sb), c, sb is None)
+    return pairs, counts.astype(np.float64) / float(s)
+
+
+def weighted_nearest_neighbors(a, b=None, k: int = 10, threshold: Optional[float] = None, gpu_mode: str = "detect"):
+    """The ``k`` nearest rows of ``b`` for every row of ``a`` by ``WeightedMinHash.jaccard``: ``(rows int64 [M, k], jaccard
+    float64 [M, k])`` as :func:`nearest_neighbors` gives them -- best first, ties by the smaller row, padded with ``-1`` /
+    ``nan``; ``b=None``: the rows of ``a`` among themselves, never a row itself; ``1 <= k <= 64``."""
+    _check_gpu_mode(gpu_mode)
+    sa, sb = _weighted_inputs(a, b)
+    k = _check_topk(k)
+    s = sa.shape[1]
+    n_b = sa.shape[0] if sb is None else sb.shape[0]
+    c = 0 if threshold is None else _threshold_count(max(s, 1), threshold)
+    if sa.shape[0] == 0 or n_b == 0 or s == 0 or c > s:
+        rows = counts = np.full((sa.shape[0], k), -1, dtype=np.int64)
+    elif _use_gpu(gpu_mode):
+        rows, counts = _native.context().weighted_jaccard_topk(sa, sb, k, c)
+    else:
+        rows, counts = _topk_from_blocks(_equal_samples_blocks(sa, sb), sa.shape[0], k, c, sb is None)
+    return rows, _jaccard_of(rows, counts, max(s, 1))
+
+
+def weighted_duplicate_clusters(signatures, b: int, r: int, threshold: Optional[float], gpu_mode: str = "detect") -> np.ndarray:
+    """:func:`duplicate_clusters` of a WeightedMinHash matrix ``[N, S, 2]`` (or a sequence of WeightedMinHash) with a
+    ``threshold``: ``labels int64 [N]`` of ``connected_components(pairs[weighted_jaccard_pairs(signatures, pairs) >= threshold],
+    N)`` with ``pairs = candidate_pairs(signatures, b, r)``.  On the device the candidate pairs, their counts
+    (mhx_weighted_jaccard_pairs_dev) and the union-find stay there and only the labels come down.  ``threshold=None``: the
+    components of the candidate graph, as :func:`duplicate_clusters` gives them."""
+    _check_gpu_mode(gpu_mode)
+    sig, _ = _weighted_rows(signatures, "signatures")
+    mat = _matrix(sig)
+    n, k = mat.shape
+    _check_params(k, b, 2 * r)
+    if n == 0:
+        return np.empty(0, dtype=np.int64)
+    if not _use_gpu(gpu_mode):
+        dig, rows = sorted_bands(mat, b, 2 * r, gpu_mode="disable")
+        return bands_clusters_host(mat, dig, rows, threshold, words=2)
+    ctx = _native.context()
+    store = DeviceRows(ctx, k, mat.dtype)
+    store.upload(mat)
+    d_dig, d_rows = ctx.alloc(n * b * 8), ctx.alloc(n * b * 4)
+    ctx.lsh_sort_bands_dev(store.d_sig.ptr, store.code, n, k, b, 2 * r, d_dig.ptr, d_rows.ptr)
+    return rows_clusters(store, d_dig.ptr, d_rows.ptr, b, k, threshold, words=2)
 
 
 # rows of A per numpy block of the all-pairs fallback: about 2^24 compared elements at a time
@@ -718,23 +864,32 @@ def live_bits(live: np.ndarray) -> np.ndarray:
     return words.view(np.uint32)
 
 
-def rows_nearest(store, probes: np.ndarray, k: int, threshold, live: Optional[np.ndarray] = None):
+def rows_nearest(store, probes: np.ndarray, k: int, threshold, live: Optional[np.ndarray] = None, words: int = 1):
     """(rows, counts) of the ``k`` best rows of an index's signature matrix (``DeviceRows`` / ``HostRows``) per probe (of the
-    store's dtype); ``live``: bool per row, dead rows are no candidates."""
-    m, num_perm, n = probes.shape[0], store.kw, store.n
+    store's dtype); ``live``: bool per row, dead rows are no candidates.  ``words=2``: the rows are WeightedMinHash signatures as
+    :func:`_matrix` views them, ``[n, 2 S]`` words, and a position is a ``(k, t)`` sample."""
+    m, num_perm, n = probes.shape[0], store.kw // words, store.n
     c = 0 if threshold is None else _min_count(np.arange(num_perm + 1, dtype=np.float64) / float(num_perm), float(threshold))
     if isinstance(store, HostRows):
         if m == 0 or n == 0 or c > num_perm:
             return np.full((m, k), -1, dtype=np.int64), np.full((m, k), -1, dtype=np.int64)
-        return _topk_from_blocks(_equal_counts_blocks(probes, store.sig), m, k, c, False, live)
+        if words == 2:
+            blocks = _equal_samples_blocks(probes.reshape(m, num_perm, 2), store.sig.reshape(n, num_perm, 2))
+        else:
+            blocks = _equal_counts_blocks(probes, store.sig)
+        return _topk_from_blocks(blocks, m, k, c, False, live)
     if m == 0:
         return np.empty((0, k), dtype=np.int64), np.empty((0, k), dtype=np.int64)
     ctx = store.ctx
     d_q = ctx.to_device(probes)
     d_bits = None if live is None or n == 0 else ctx.to_device(live_bits(live))
     d_rows, d_counts = ctx.alloc(8 * m * k), ctx.alloc(4 * m * k)
-    ctx.jaccard_topk_dev(d_q.ptr, m, store.d_sig.ptr if n else d_q.ptr, n, store.code, num_perm, None if d_bits is None else d_bits.ptr,
-                         c, k, d_rows.ptr, d_counts.ptr)
+    if words == 2:
+        ctx.weighted_jaccard_topk_dev(d_q.ptr, m, store.d_sig.ptr if n else d_q.ptr, n, num_perm, None if d_bits is None else d_bits.ptr,
+                                      c, k, d_rows.ptr, d_counts.ptr)
+    else:
+        ctx.jaccard_topk_dev(d_q.ptr, m, store.d_sig.ptr if n else d_q.ptr, n, store.code, num_perm, None if d_bits is None else d_bits.ptr,
+                             c, k, d_rows.ptr, d_counts.ptr)
     return d_rows.download((m, k), np.int64), d_counts.download((m, k), np.int32).astype(np.int64)
 
 
@@ -797,15 +952,19 @@ def _threshold_count(num_perm: int, threshold: float) -> int:
     return _min_count(np.arange(num_perm + 1, dtype=np.float64) / float(num_perm), float(threshold))
 
 
-def bands_clusters_host(sig: np.ndarray, dig: np.ndarray, rows: np.ndarray, threshold, extra=None) -> np.ndarray:
+def bands_clusters_host(sig: np.ndarray, dig: np.ndarray, rows: np.ndarray, threshold, extra=None, words: int = 1) -> np.ndarray:
     """The numpy twin of :func:`rows_clusters`: ``sig`` the ``[n, K]`` matrix, ``dig`` / ``rows`` its sorted bands."""
     n = sig.shape[0]
     if threshold is None:
         u, v = _run_edges(dig, rows)
     else:
         pairs = _pairs_of_bands(dig, rows)
-        counts = np.count_nonzero(sig[pairs[:, 0]] == sig[pairs[:, 1]], axis=1)
-        pairs = pairs[counts >= _threshold_count(sig.shape[1], threshold)]
+        if words == 2:
+            samples = sig.reshape(n, -1, 2)
+            counts = _equal_samples(samples[pairs[:, 0]], samples[pairs[:, 1]])
+        else:
+            counts = np.count_nonzero(sig[pairs[:, 0]] == sig[pairs[:, 1]], axis=1)
+        pairs = pairs[counts >= _threshold_count(sig.shape[1] // words, threshold)]
         u, v = pairs[:, 0], pairs[:, 1]
     if extra is not None and len(extra):
         extra = np.asarray(extra, dtype=np.int64).reshape(-1, 2)
@@ -813,11 +972,11 @@ def bands_clusters_host(sig: np.ndarray, dig: np.ndarray, rows: np.ndarray, thre
     return _components_host(u, v, n)
 
 
-def rows_clusters(store, d_dig: int, d_rows: int, b: int, num_perm: int, threshold, extra=None) -> np.ndarray:
+def rows_clusters(store, d_dig: int, d_rows: int, b: int, num_perm: int, threshold, extra=None, words: int = 1) -> np.ndarray:
     """``labels int64 [n]`` of a resident signature matrix (``DeviceRows``) and its resident sorted bands.  ``threshold=None``:
     init, link bands, finish -- no pair is formed.  Else: candidate pairs on the device, their counts, link pairs with the
     threshold's count, finish.  ``extra``: further edges ``[E, 2]`` from the host, linked by one more call.  Only the labels
-    come down."""
+    come down.  ``words=2``: weighted rows of ``num_perm`` words, ``num_perm / 2`` samples, counted sample by sample."""
     ctx, n = store.ctx, store.n
     if n == 0:
         return np.empty(0, dtype=np.int64)
@@ -830,8 +989,11 @@ def rows_clusters(store, d_dig: int, d_rows: int, b: int, num_perm: int, thresho
         d_pairs, found = ctx.lsh_candidate_pairs_dev(d_dig, d_rows, n, b)
         if found:
             d_counts = ctx.alloc(4 * found)
-            ctx.jaccard_pairs_dev(store.d_sig.ptr, store.d_sig.ptr, store.code, num_perm, d_pairs.ptr, found, d_counts.ptr)
-            ctx.cc_link_pairs_dev(d_labels.ptr, n, d_pairs.ptr, found, d_counts.ptr, _threshold_count(num_perm, threshold), d_bad.ptr)
+            if words == 2:
+                ctx.weighted_jaccard_pairs_dev(store.d_sig.ptr, store.d_sig.ptr, num_perm // 2, d_pairs.ptr, found, d_counts.ptr)
+            else:
+                ctx.jaccard_pairs_dev(store.d_sig.ptr, store.d_sig.ptr, store.code, num_perm, d_pairs.ptr, found, d_counts.ptr)
+            ctx.cc_link_pairs_dev(d_labels.ptr, n, d_pairs.ptr, found, d_counts.ptr, _threshold_count(num_perm // words, threshold), d_bad.ptr)
     if extra is not None and len(extra):
         extra = np.ascontiguousarray(extra, dtype=np.int64).reshape(-1, 2)
         d_extra = ctx.to_device(extra)

@@ -968,4 +968,9 @@ MHX_API int mhx_comm_exchange_dev(mhx_comm *comm, const void *d_send, void *d_re
 #ifdef __cplusplus
 }
 #endif
+
+/* ---- Weighted Jaccard: pairs, all pairs, thresholded and top-k on WeightedMinHash rows ------------------------------------
+ * mhx_weighted_jaccard_pairs, _matrix, _threshold_pairs, _topk and their "_dev" forms: declared in a header of their own. */
+#include "mhx_weighted_jaccard.h"
+
 #endif /* MHX_H_ */
