@@ -453,45 +453,86 @@ int mhx_ctx_device_info(mhx_ctx *ctx, char *name, int name_len, int *cus, int64_
     return MHX_OK;
 }
 
+// The values an option takes (tests/option_cases.py DOMAIN restates this table; tests/test_option_ledger.py compares the keys): a set of
+// values where the text of mhx.h lists them, else a range [lo, hi] -- `step` != 0: 0 or a multiple of step in the range.  `text` is what
+// a refusal says after "<key> must be ".
+namespace {
+struct OptionDomain {
+    int n_values;
+    int64_t values[9];
+    int64_t lo, hi, step;
+    const char *text;
+};
+constexpr int64_t kAny = INT64_MAX;
+const OptionDomain kFlag{2, {0, 1}, 0, 0, 0, "0 or 1"};
+const OptionDomain kThree{3, {0, 1, 2}, 0, 0, 0, "0, 1 or 2"};
+// blocks_per_cu: the launchers that read it size grids of min(work, CUs * n) workgroups of at most 512 threads (minhash_kernels.hip
+// launch_typed: 256; weighted_kernels.hip launch_weighted_dense_walk: 64 * waves <= 512 and 256, launch_weighted_csr_walk: 256), and a
+// launch takes fewer than 2^32 threads along x: n <= (2^32 - 1) / (512 * CUs), 32767 at the MI355X's 256 CUs (it also fits launch_typed's int)
+int64_t max_blocks_per_cu(const mhx_ctx *ctx) { return (int64_t)0xFFFFFFFFll / (512 * (int64_t)std::max(1, ctx->hw_cus)); }
+}  // namespace
+
 int mhx_ctx_set_option(mhx_ctx *ctx, const char *key, int64_t value) {
     static const struct {
         const char *key;
         int64_t mhx_ctx::*field;
+        OptionDomain domain;
     } options[] = {
-        {"minhash.path", &mhx_ctx::opt_minhash_path},       {"minhash.split", &mhx_ctx::opt_minhash_split},
-        {"minhash.packed", &mhx_ctx::opt_minhash_packed},   {"minhash.ties", &mhx_ctx::opt_minhash_ties},
-        {"minhash.p3", &mhx_ctx::opt_minhash_p3},           {"minhash.share", &mhx_ctx::opt_minhash_share},
-        {"minhash.adapt", &mhx_ctx::opt_minhash_adapt},     {"blocks_per_cu", &mhx_ctx::opt_blocks_per_cu},
-        {"minhash.alias", &mhx_ctx::opt_minhash_alias},     {"minhash.prefetch", &mhx_ctx::opt_minhash_prefetch},
-        {"weighted.path", &mhx_ctx::opt_weighted_path},     {"weighted.direct", &mhx_ctx::opt_weighted_direct},
-        {"weighted.split", &mhx_ctx::opt_weighted_split},   {"weighted.tail", &mhx_ctx::opt_weighted_tail},
-        {"weighted.debug", &mhx_ctx::opt_weighted_debug},   {"weighted.kernel", &mhx_ctx::opt_weighted_kernel},
-        {"weighted.plan", &mhx_ctx::opt_weighted_plan},     {"weighted.rescue", &mhx_ctx::opt_weighted_rescue},
-        {"weighted.min_dim", &mhx_ctx::opt_weighted_min_dim}, {"host.chunk_bytes", &mhx_ctx::opt_host_chunk_bytes},
-        {"lsh.sort_bits", &mhx_ctx::opt_lsh_sort_bits},     {"lsh.gather", &mhx_ctx::opt_lsh_gather},
-        {"lsh.sort", &mhx_ctx::opt_lsh_sort},               {"lsh.levels", &mhx_ctx::opt_lsh_levels},
-        {"lsh.chunk", &mhx_ctx::opt_lsh_chunk},             {"lsh.team", &mhx_ctx::opt_lsh_team},
-        {"lsh.bigbins", &mhx_ctx::opt_lsh_bigbins},         {"pack.fused", &mhx_ctx::opt_pack_fused},
-        {"weighted.refill", &mhx_ctx::opt_weighted_refill}, {"lsh.prehash", &mhx_ctx::opt_lsh_prehash},
-        {"lsh.merge_items", &mhx_ctx::opt_lsh_merge_items}, {"hll.split_tokens", &mhx_ctx::opt_hll_split_tokens},
-        {"bloom.lanes", &mhx_ctx::opt_bloom_lanes},         {"jaccard.topk_path", &mhx_ctx::opt_jaccard_topk_path},
-        {"jaccard.topk_segments", &mhx_ctx::opt_jaccard_topk_segments}, {"debug.cus", &mhx_ctx::opt_debug_cus},
-        {"overlap.bins", &mhx_ctx::opt_overlap_bins},
+        {"minhash.path", &mhx_ctx::opt_minhash_path, kThree},
+        {"minhash.split", &mhx_ctx::opt_minhash_split, kThree},
+        {"minhash.packed", &mhx_ctx::opt_minhash_packed, kThree},
+        {"minhash.ties", &mhx_ctx::opt_minhash_ties, kFlag},
+        {"minhash.p3", &mhx_ctx::opt_minhash_p3, kFlag},
+        {"minhash.share", &mhx_ctx::opt_minhash_share, kFlag},
+        {"minhash.adapt", &mhx_ctx::opt_minhash_adapt, kFlag},
+        {"blocks_per_cu", &mhx_ctx::opt_blocks_per_cu, {0, {}, 0, 0, 0, nullptr}},  // 0 .. max_blocks_per_cu(ctx), below
+        {"minhash.alias", &mhx_ctx::opt_minhash_alias, {0, {}, -1, kAny, 0, ">= -1"}},
+        {"minhash.prefetch", &mhx_ctx::opt_minhash_prefetch, kThree},
+        {"weighted.path", &mhx_ctx::opt_weighted_path, kThree},
+        {"weighted.direct", &mhx_ctx::opt_weighted_direct, {0, {}, 0, 1000, 0, "in [0, 1000] (per mille of the columns)"}},
+        {"weighted.split", &mhx_ctx::opt_weighted_split, kFlag},
+        {"weighted.tail", &mhx_ctx::opt_weighted_tail, {0, {}, 0, 5, 0, "in [0, 5]"}},
+        {"weighted.debug", &mhx_ctx::opt_weighted_debug, {5, {0, 1, 2, 4, 8}, 0, 0, 0, "0, 1, 2, 4 or 8"}},
+        {"weighted.kernel", &mhx_ctx::opt_weighted_kernel, kThree},
+        {"weighted.plan", &mhx_ctx::opt_weighted_plan, kFlag},
+        {"weighted.rescue", &mhx_ctx::opt_weighted_rescue, {0, {}, -kAny - 1, 64, 0, "<= 64 (the lanes of a wave; < 0 = never)"}},
+        {"weighted.min_dim", &mhx_ctx::opt_weighted_min_dim, {0, {}, 0, 4096, 4, "0 or a multiple of 4 in [4, 4096]"}},
+        {"host.chunk_bytes", &mhx_ctx::opt_host_chunk_bytes, {0, {}, -kAny - 1, kAny, 0, "an int64"}},
+        {"lsh.sort_bits", &mhx_ctx::opt_lsh_sort_bits, {0, {}, 0, 64, 0, "in [0, 64]"}},
+        {"lsh.gather", &mhx_ctx::opt_lsh_gather, kFlag},
+        {"lsh.sort", &mhx_ctx::opt_lsh_sort, kFlag},
+        {"lsh.levels", &mhx_ctx::opt_lsh_levels, {2, {0, 2}, 0, 0, 0, "0 or 2"}},
+        {"lsh.chunk", &mhx_ctx::opt_lsh_chunk, {2, {0, 8}, 0, 0, 0, "0 or 8"}},
+        {"lsh.team", &mhx_ctx::opt_lsh_team, {3, {0, 256, 1024}, 0, 0, 0, "0, 256 or 1024"}},
+        {"lsh.bigbins", &mhx_ctx::opt_lsh_bigbins, kThree},
+        {"pack.fused", &mhx_ctx::opt_pack_fused, kFlag},
+        {"weighted.refill", &mhx_ctx::opt_weighted_refill, {9, {0, 1, 2, 3, 5, 6, 8, 9, 13}, 0, 0, 0, "0, 1, 2, 3, 5, 6, 8, 9 or 13"}},
+        {"lsh.prehash", &mhx_ctx::opt_lsh_prehash, kFlag},
+        {"lsh.merge_items", &mhx_ctx::opt_lsh_merge_items, {3, {0, 8, 16}, 0, 0, 0, "0, 8 or 16"}},
+        {"hll.split_tokens", &mhx_ctx::opt_hll_split_tokens, {0, {}, 0, kAny, 0, ">= 0"}},
+        {"bloom.lanes", &mhx_ctx::opt_bloom_lanes, {3, {0, 1, 16}, 0, 0, 0, "0, 1 or 16"}},
+        {"jaccard.topk_path", &mhx_ctx::opt_jaccard_topk_path, kThree},
+        {"jaccard.topk_segments", &mhx_ctx::opt_jaccard_topk_segments, {0, {}, 0, kAny, 0, ">= 0"}},
+        {"debug.cus", &mhx_ctx::opt_debug_cus, {0, {}, 0, 0, 0, nullptr}},  // 0 .. the device's CU count, below
+        {"overlap.bins", &mhx_ctx::opt_overlap_bins, kThree},
     };
     if (!ctx || !key) return fail(MHX_ERR_INVALID, "ctx/key is NULL");
     MHX_GUARD(ctx);
     for (const auto &o : options) {
         if (strcmp(key, o.key)) continue;
-        if (o.field == &mhx_ctx::opt_lsh_merge_items)
-            MHX_REQUIRE(value == 0 || value == 8 || value == 16, "lsh.merge_items must be 0, 8 or 16");
-        if (o.field == &mhx_ctx::opt_hll_split_tokens) MHX_REQUIRE(value >= 0, "hll.split_tokens must be >= 0");
-        if (o.field == &mhx_ctx::opt_bloom_lanes) MHX_REQUIRE(value == 0 || value == 1 || value == 16, "bloom.lanes must be 0, 1 or 16");
-        if (o.field == &mhx_ctx::opt_jaccard_topk_path) MHX_REQUIRE(value >= 0 && value <= 2, "jaccard.topk_path must be 0, 1 or 2");
-        if (o.field == &mhx_ctx::opt_jaccard_topk_segments) MHX_REQUIRE(value >= 0, "jaccard.topk_segments must be >= 0");
-        if (o.field == &mhx_ctx::opt_overlap_bins) MHX_REQUIRE(value >= 0 && value <= 2, "overlap.bins must be 0, 1 or 2");
-        if (o.field == &mhx_ctx::opt_debug_cus)
+        const OptionDomain &d = o.domain;
+        if (o.field == &mhx_ctx::opt_debug_cus) {
             MHX_REQUIRE(value >= 0 && value <= ctx->hw_cus, "debug.cus must be 0 (the device's %d CUs) or in [1, %d], got %lld", ctx->hw_cus, ctx->hw_cus,
                         (long long)value);
+        } else if (o.field == &mhx_ctx::opt_blocks_per_cu) {
+            MHX_REQUIRE(value >= 0 && value <= max_blocks_per_cu(ctx), "blocks_per_cu must be in [0, %lld] (a grid of this device's %d CUs x 512 threads stays below 2^32), got %lld",
+                        (long long)max_blocks_per_cu(ctx), ctx->hw_cus, (long long)value);
+        } else {
+            bool ok = false;
+            for (int i = 0; i < d.n_values; ++i) ok = ok || value == d.values[i];
+            if (!d.n_values) ok = value >= d.lo && value <= d.hi && (d.step == 0 || value % d.step == 0);
+            MHX_REQUIRE(ok, "%s must be %s", o.key, d.text);
+        }
         ctx->*o.field = value;
         if (o.field == &mhx_ctx::opt_debug_cus) ctx->num_cus = value ? (int)value : ctx->hw_cus;
         return MHX_OK;

@@ -82,7 +82,9 @@ MHX_API int mhx_ctx_device_info(mhx_ctx *ctx, char *name, int name_len, int *cus
  * 1 = exact fold for every pair, 2 = fast fold with exact redo), ("minhash.split", 0 auto,
  * 1 wave per set, 2 split sets over waves), ("minhash.packed", 0 auto: several sets per wave when
  * num_perm <= 96, 1 = always one set per wave, 2 = several sets per wave up to num_perm 128), ("minhash.ties", 0 auto: the second launch tries the
- * tie-tolerant sieve before the dedup pass, 1 = dedup pass only), ("blocks_per_cu", n), ("minhash.prefetch", 0/1/2: never / auto / always),
+ * tie-tolerant sieve before the dedup pass, 1 = dedup pass only), ("blocks_per_cu", n: workgroups per CU of the capped grids of the MinHash and weighted
+ * launchers, 0 auto; n <= (2^32 - 1) / (512 * the device's CUs) -- 32767 on the MI355X's 256 --, so that a grid of CUs * n workgroups of up to 512
+ * threads stays below the 2^32 threads a launch takes), ("minhash.prefetch", 0/1/2: never / auto / always),
  * ("debug.cus", tests only: 0 = the device's own compute-unit count, 1 .. that count = every launcher sizes its grid, chunks and segments as if
  * the device had so many (a grid can only shrink, so that small shapes reach the later trips of the grid-stride loops); any other value is
  * MHX_ERR_INVALID; results unaffected, mhx_ctx_device_info keeps reporting the device's count),
@@ -125,7 +127,22 @@ MHX_API int mhx_ctx_device_info(mhx_ctx *ctx, char *name, int name_len, int *cus
  * mapping of each; 1 / 16 = both operations that way; results unaffected),
  * ("overlap.bins", mhx_overlap_*: 0 auto = pairs whose table fits LDS are binned by table size, each bin is a launch with that
  * much dynamic LDS and the pairs of the smallest bin get one wave each, 1 = one launch sized for the largest table of the call,
- * 2 = the bins of 0 with a workgroup per pair in every bin; results unaffected). */
+ * 2 = the bins of 0 with a workgroup per pair in every bin; results unaffected),
+ * ("lsh.levels", bucketing of mhx_lsh_sort_bands: 0 auto = two scatter levels beyond 2^10 bins per band, 2 = two levels whenever there are at least
+ * 4 bins (tests)), ("lsh.chunk", bucketing: rows per thread of a scatter pass over a unit-stride source, 0 auto = 16, 8 = eight (A/B)),
+ * ("pack.fused", mhx_bbit_pack_band_digests_dev: 0 auto = one read of the matrix where the shape allows, 1 = always the two kernels),
+ * ("jaccard.topk_path", mhx_*jaccard_topk*: 0 auto = the stream kernel for dense and weighted rows and few probes, 1 = the strip kernel,
+ * 2 = the stream kernel wherever it exists; b-bit rows always take the strip kernel),
+ * ("jaccard.topk_segments", mhx_*jaccard_topk*: segments B is cut into, 0 auto = enough to fill the machine, n >= 1 = n, clamped to the number of
+ * 128-row tiles of B).
+ * Values: a key whose text lists its values takes those and no others ("weighted.refill": 0, 1, 2, 3, 5, 6, 8, 9, 13; "lsh.team": 0, 256, 1024;
+ * "weighted.debug": 0, 1, 2, 4, 8; the 0 / 1 keys: 0 or 1); "weighted.direct" 0 .. 1000, "weighted.tail" 0 .. 5, "weighted.min_dim" 0 or a multiple
+ * of 4 in 4 .. 4096, "lsh.sort_bits" 0 .. 64, "weighted.rescue" any value up to 64 (the lanes of a wave), "minhash.alias" >= -1,
+ * "hll.split_tokens" and "jaccard.topk_segments" >= 0, "host.chunk_bytes" any value.  Anything else is MHX_ERR_INVALID with a message that
+ * names the key and its values, and the option keeps the value it had.  Except for the profiling keys "weighted.debug" 1 / 2 / 4 and
+ * "minhash.alias" >= 0, timings depend on an option, results never: tests/test_gpu_options.py (cases in tests/option_cases.py) runs every
+ * value -- both ends and the middle of a range -- at a shape whose launcher reads it and compares with the reference byte for byte, and
+ * tests/test_option_ledger.py fails when a key or a place that reads one has no case. */
 MHX_API int mhx_ctx_set_option(mhx_ctx *ctx, const char *key, int64_t value);
 /* Kernel event counters since the last call (synchronises the stream, then resets them):
  *   out[0] sets the sieve launch left to the full launch (failed proof, or skipped by the back-off),

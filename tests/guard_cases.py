@@ -138,6 +138,34 @@ def minhash_cases(ctx):
         ctx.minhash_bulk_dev(perms, d_hv.ptr, MHX_U64, None, t, n, n * t, None, 0, d_out.ptr, MHX_U64)
         _expect(d_out.download((n, k), np.uint64), O.c_minhash_bulk_dense(hv, perms[0], perms[1]), ("repeats", k))
         _done(f"minhash repeats K={k}")
+    # minhash.prefetch 2 (always): the warm-up load of the NEXT set -- one aligned dword per lane at byte 128 * lane of that set, inside
+    # its own bytes, and only when there is a next set (minhash_kernels.hip, `warm`) -- on fixed lengths of 256 and more, where auto
+    # leaves it out, and on CSR sets whose last one ends at the end of the token array; launchers that see one CU (debug.cus), so that
+    # 67 sets of 256 tokens get a wave each instead of being split over waves
+    ctx.set_option("minhash.prefetch", 2)
+    ctx.set_option("debug.cus", 1)
+    try:
+        for tok_dtype in (np.uint64, np.uint32):
+            for k in (128, 144):
+                for fixed in (256, 300):
+                    n = 67
+                    perms = O.np_init_permutations(k, 4)
+                    hv = rng.randint(0, 2**32, size=(n, fixed), dtype=np.uint64)
+                    d_hv, d_out = _dev(ctx, hv.astype(tok_dtype)), _alloc(ctx, n * k * 8)
+                    ctx.minhash_bulk_dev(perms, d_hv.ptr, MHX_U32 if tok_dtype == np.uint32 else MHX_U64, None, fixed, n, n * fixed, None, 0, d_out.ptr, MHX_U64)
+                    _expect(d_out.download((n, k), np.uint64), O.c_minhash_bulk_dense(hv, perms[0], perms[1]), ("prefetch always", fixed, k))
+                    _done(f"minhash prefetch always {n}x{fixed} K={k} {np.dtype(tok_dtype).name}")
+                lens = rng.randint(1, 300, size=257)
+                lens[-1] = 33  # the last set: 33 tokens, its last lane's dword is the array's last
+                offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+                hv = rng.randint(0, 2**32, size=int(offsets[-1]), dtype=np.uint64)
+                d_hv, d_off, d_out = _dev(ctx, hv.astype(tok_dtype)), _dev(ctx, offsets), _alloc(ctx, 257 * k * 8)
+                ctx.minhash_bulk_dev(perms, d_hv.ptr, MHX_U32 if tok_dtype == np.uint32 else MHX_U64, d_off.ptr, 0, 257, hv.size, None, 0, d_out.ptr, MHX_U64)
+                _expect(d_out.download((257, k), np.uint64), O.c_minhash_bulk(hv, offsets, perms[0], perms[1]), ("prefetch always csr", k))
+                _done(f"minhash prefetch always csr K={k} {np.dtype(tok_dtype).name}")
+    finally:
+        ctx.set_option("minhash.prefetch", 1)
+        ctx.set_option("debug.cus", 0)
     # merge: odd counts
     for count in (1, 2, 3, 127, 128 * 33 + 1):
         x, y = rng.randint(0, 2**32, size=count, dtype=np.uint64), rng.randint(0, 2**32, size=count, dtype=np.uint64)

@@ -568,6 +568,7 @@ OPTIONS = {
     "host.chunk_bytes": 0, "lsh.sort_bits": 0, "lsh.gather": 0, "lsh.sort": 0, "lsh.levels": 0, "lsh.chunk": 0, "lsh.team": 0, "lsh.bigbins": 0,
     "pack.fused": 0, "weighted.refill": 0, "lsh.prehash": 0, "lsh.merge_items": 0, "hll.split_tokens": 0, "bloom.lanes": 0,
     "jaccard.topk_path": 0, "jaccard.topk_segments": 0,
+    "overlap.bins": 0,
     "debug.cus": 0,  # tests only: 0 = the device's own CU count, 1 .. that count = what every launcher sizes its grid from
 }
 
